@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: 6-view scenes/sec, roadmap model, fwd + bwd + Adam, bs = 32 per GPU, fp32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config C]
+
+A plain run sets up, warms up, times the K steps and prints the line.  ``--full`` adds, on one GPU for config 2, what the
+headline figure does not need: the other configurations' step timings (``others``), the live HBM-traffic passes of the
+dominant kernel and the CPU baseline (``cpu_baseline``); ``--no-others`` / ``--no-cpu-baseline`` drop parts of that again.
+``--dump-outputs DIR`` writes what the last timed step computed -- its loss and the parameters and buffers it left, a fixed
+seeded sample of every tensor over DUMP_SAMPLE elements, 64 MB at most -- as DIR/<name>.npy, so that two builds can be
+compared output for output (the inputs are seeded: the same arguments give the same inputs).
 
 ``--config`` selects the BASELINE.json entry (default 2 = configs[1], the one the metric is quoted on): 3 = box head on the
 frozen encoder (bs 32 per GPU), 4 = joint roadmap + box step (bs 32 per GPU: 256 on 8 GPUs), 5 = bf16 at 2x resolution (bs 16
@@ -45,6 +52,8 @@ PEAK_HBM_GBS = 8000.0               # same guide: HBM3E peak
 C2_FLOP_PER_SCENE = 2.0 * 256 * 1836 * 32 * 288
 C1_WGRAD_FLOP_PER_SCENE = 2.0 * 256 * 1836 * 32 * 27
 PIXELS_PER_SCENE = 256 * 1836
+DUMP_SAMPLE = 1 << 20               # --dump-outputs: elements kept of a larger tensor (a fixed, seeded sample)
+DUMP_LIMIT = 64 << 20               # --dump-outputs: bytes in all
 
 
 def parse_args():
@@ -54,8 +63,13 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5), help="BASELINE.json configs[N-1]: 2 roadmap (the headline), "
                     "3 box head on the frozen encoder, 4 joint roadmap + box, 5 bf16 at 2x resolution")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the config-1 / config-3 / config-5 step timings after the headline")
+    ap.add_argument("--full", action="store_true", help="after the headline line's own timing, also measure what the headline figure does not "
+                    "need (one GPU, config 2): the other configurations' step timings, the live HBM-traffic passes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(its loss and the model state it left: parameters and buffers, a fixed seeded sample of every tensor over "
+                    f"{DUMP_SAMPLE:,} elements) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip the config-1 / config-3 / config-5 step timings after the headline")
     ap.add_argument("--adam-overlap", choices=("auto", "on", "off"), default="auto",
                     help="optimizer passes of the big tensors on a side stream beside the backward (on) or after it (off).  auto = TrainStep's "
                     "choice: beside the backward for the fp32 models (config 2, same box, on / off: 7.51-7.62 / 7.86-7.93 ms), after it with four "
@@ -385,6 +399,46 @@ def time_steps(step, steps, warmup):
         step(warmup + i)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+def dump_outputs(out_dir, step_out, model):
+    """--dump-outputs: the tensors of the last timed step's ``training_step`` dict (``loss``, ``log.*``) and the model's state after
+    it (``state.<parameter or buffer>``) -> ``out_dir/<name>.npy``, float32 (float64 for fp64 / integer tensors).  A tensor of more
+    than DUMP_SAMPLE elements is written as the DUMP_SAMPLE elements at fixed indices (seeded by its name and size: the same in
+    every run and every build) and named ``<name>.sample``."""
+    import zlib
+
+    import numpy as np
+    import torch
+    tensors = []
+
+    def walk(prefix, obj):
+        if isinstance(obj, torch.Tensor):
+            tensors.append((prefix, obj))
+        elif isinstance(obj, dict):
+            for k, v in obj.items():
+                walk(f"{prefix}.{k}" if prefix else str(k), v)
+    walk("", step_out)
+    walk("state", model.state_dict())
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in tensors:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()) ^ flat.numel())
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            name += ".sample"
+            arr = flat.cpu()
+        else:
+            arr = t.detach().cpu()
+        dt = torch.float64 if arr.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32
+        arr = arr.to(dt).numpy()
+        total += arr.nbytes
+        if total > DUMP_LIMIT:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return total
 
 
 _T0 = time.perf_counter()
@@ -1133,17 +1187,21 @@ def run_rank(a):
         if preflight is not None:
             line["preflight"] = preflight
         _phase("headline")
-        if world == 1 and a.config == 2 and not a.no_others and not a.simulate_shard:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, ts.last, model)
+            _phase("dump_outputs")
+        # --full: what the headline figure does not need (runs of their own, after the line's timing)
+        if a.full and world == 1 and a.config == 2 and not a.no_others and not a.simulate_shard:
             ts.close()
             timer.uninstall()
             del model, ts, batch, cfg
             torch.cuda.empty_cache()
             line["others"] = other_configs(a, dev)
-        if world == 1 and a.config == 2 and pmc is not None and not a.no_others and not a.simulate_shard:
+        if a.full and world == 1 and a.config == 2 and pmc is not None and not a.no_others and not a.simulate_shard:
             torch.cuda.empty_cache()      # this process's models are gone by now (deleted before `others`): the children get the GPU to themselves
             refresh_traffic(roof, pmc)
         _phase("traffic")
-        if not a.no_cpu_baseline and world == 1 and a.config == 2 and not a.simulate_shard:
+        if a.full and not a.no_cpu_baseline and world == 1 and a.config == 2 and not a.simulate_shard:
             line["cpu_baseline"] = cpu_baseline()
             _phase("cpu_baseline")
         print(json.dumps(line), flush=True)

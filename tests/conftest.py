@@ -21,10 +21,34 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "slow: CPU oracle at full size (tens of seconds each; still part of -m 'not gpu')")
 
 
+class GoldenParts:
+    """One fixture stored as ``<name>.npz`` plus ``<name>.part1.npz``, ``<name>.part2.npz``, ... (no committed file over 1 MiB):
+    the arrays of all parts under one ``.files`` / ``[key]`` interface, as ``np.load`` of a single file gives them."""
+
+    def __init__(self, parts):
+        self._parts = parts
+        self.files = [k for p in parts for k in p.files]
+
+    def __getitem__(self, key):
+        for p in self._parts:
+            if key in p.files:
+                return p[key]
+        raise KeyError(key)
+
+    def __contains__(self, key):
+        return key in self.files
+
+    def __iter__(self):
+        return iter(self.files)
+
+
 @pytest.fixture(scope="session")
 def golden():
     import numpy as np
 
     def load(name):
-        return np.load(os.path.join(GOLDEN, name + ".npz"))
+        parts = [np.load(os.path.join(GOLDEN, name + ".npz"))]
+        while os.path.exists(os.path.join(GOLDEN, f"{name}.part{len(parts)}.npz")):
+            parts.append(np.load(os.path.join(GOLDEN, f"{name}.part{len(parts)}.npz")))
+        return parts[0] if len(parts) == 1 else GoldenParts(parts)
     return load

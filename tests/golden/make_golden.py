@@ -37,6 +37,27 @@ from src.bounding_box_model.spatial_bb.components import (  # noqa: E402  (refer
 torch.set_num_threads(8)
 
 
+PART_BYTES = 900_000        # no committed file over 1 MiB: a larger fixture is written as <name>.npz + <name>.part1.npz, ... (tests/conftest.py joins them)
+
+
+def _save(out, res):
+    import io
+    import zipfile
+    stem = out[:-len(".npz")]
+    part, parts, size = {}, [], 0
+    for k, v in res.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, v=v)
+        n = zipfile.ZipFile(buf).infolist()[0].compress_size
+        if part and size + n > PART_BYTES:
+            parts.append(part)
+            part, size = {}, 0
+        part[k], size = v, size + n
+    parts.append(part)
+    for i, p in enumerate(parts):
+        np.savez_compressed(out if i == 0 else f"{stem}.part{i}.npz", **p)
+
+
 def _np(t):
     return t.detach().cpu().numpy()
 
@@ -87,7 +108,7 @@ def tiny_encoder(out):
         # eval mode: BN uses running statistics (dropout p = 0 here)
         enc.eval()
         res[f"z_eval_{tag}"] = _np(enc(x))
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def tiny_decoder(out):
@@ -104,7 +125,7 @@ def tiny_decoder(out):
         res[f"grad.z_{tag}"] = _np(z.grad)
         for k, g in _grads(dec).items():
             res[f"grad.{k}_{tag}"] = _np(g)
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def default_init(out):
@@ -123,7 +144,7 @@ def default_init(out):
         for k, v in m.state_dict().items():
             v = v.double().reshape(-1)
             res[f"{name}.{k}"] = np.array([v.sum().item(), v.abs().sum().item(), v[0].item(), v[-1].item()])
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def full_roadmap(out, b=2, hidden=128, latent=64):
@@ -169,7 +190,7 @@ def full_roadmap(out, b=2, hidden=128, latent=64):
         res[f"feat_samp_{tag}"], res["feat_idx"] = _sample(feat, 512)
         res[f"feat_sum_{tag}"] = np.array([feat.double().sum().item(), feat.double().abs().sum().item()])
         del enc, head, feat
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def full_roadmap_b32(out):
@@ -207,7 +228,7 @@ def full_decoder(out):
             if v.numel() > 1:
                 res[f"bufsamp.{k}_{tag}"], res[f"bufidx.{k}"] = _sample(v, 512)
         del dec
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def full_ae_step(out):
@@ -242,7 +263,7 @@ def full_ae_step(out):
                 res[f"gradsum.{name}.{k}_{tag}"] = np.array([g.double().sum().item(), g.double().abs().sum().item()])
         del enc, dec, loss, y_hat
     res["mask_slot"] = np.array(t)
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def merge_signed(out):
@@ -272,7 +293,7 @@ def merge_signed(out):
                     res[f"grad.{name}.{k}_{tag}"] = _np(g)
                 else:
                     res[f"gradsamp.{name}.{k}_{tag}"], res[f"gradidx.{name}.{k}"] = _sample(g, 512)
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def tiny_decoder_v2(out):
@@ -300,7 +321,7 @@ def tiny_decoder_v2(out):
         dec.eval()
         with torch.no_grad():
             res[f"y_eval_{tag}"] = _np(dec(z))
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def full_decoder_v2(out):
@@ -330,7 +351,7 @@ def full_decoder_v2(out):
             if 1 < v.numel() <= 64:
                 res[f"buf.{k}_{tag}"] = _np(v)
         del dec
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def _reference_encoder_v2(hidden_dim, latent_dim, in_channels, input_height, input_width):
@@ -412,14 +433,14 @@ def tiny_encoder_v2(out):
     res = {}
     for h, w in ((16, 22), (16, 70)):
         _encoder_v2_case(res, f"h{h}w{w}.", h, w, 4, 41, "v2x", "v2w", "v2f", full=False)
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def full_encoder_v2(out):
     """components_v2.Encoder(16, 8, 3, 256, 1836) at B = 4: BatchNorm2d statistics over 1.9 M / 470 k pixels per channel."""
     res = {}
     _encoder_v2_case(res, "", 256, 1836, 4, 43, "v2x_full", "v2w_full", "v2f_full", full=True)
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def tiny_ae_ckpt(out):
@@ -448,7 +469,7 @@ def tiny_ae_ckpt(out):
         z = e(x.to(dt))
         res[f"z_{tag}"] = _np(z)
         res[f"y_{tag}"] = _np(d(z))
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def spatial_heads(out):
@@ -483,7 +504,7 @@ def spatial_heads(out):
             pred2 = bm(ssr0.to(dt), space.detach())
         res[f"pred_nomap_samp_{tag}"], res["pred_nomap_idx"] = _sample(pred2, 512)
         res[f"pred_nomap_sum_{tag}"] = np.array([pred2.double().sum().item(), pred2.double().abs().sum().item()])
-    np.savez_compressed(out, **res)
+    _save(out, res)
 
 
 def box_raster(out):
@@ -506,7 +527,23 @@ def box_raster(out):
         res[f"{name}_boxes"] = _np(boxes)
         res[f"{name}_map_bits"] = np.packbits(m.astype(np.uint8), axis=1)
         res[f"{name}_ones"] = np.array(int(m.sum()))
-    np.savez_compressed(out, **res)
+    _save(out, res)
+
+
+def reference_state_dicts(out):
+    """The layout of the reference modules' ``state_dict()`` -- key names in order, shapes, dtypes; no values -- for the drop-in
+    modules the product ships: tests/test_oracle_golden.py holds the product's ``state_dict()`` to it (the product -> reference
+    direction of the checkpoint contract: what ``load_state_dict(strict=True)`` of the reference module checks)."""
+    from src.autoencoder.components_v2 import Decoder as DecoderV2  # reference
+    res = {}
+    mods = [Encoder(16, 8, 3, 16, 22), Decoder(16, 8, 3, 16, 22), DecoderV2(16, 8, 3, 16, 22), SpatialMappingCNN(), BoxesMergingCNN(),
+            RoadMapBoxesMergingCNN()]
+    for i, m in enumerate(mods):
+        sd = m.state_dict()
+        res[f"m{i}_keys"] = np.array(list(sd))
+        res[f"m{i}_shapes"] = np.array([",".join(str(d) for d in v.shape) for v in sd.values()])
+        res[f"m{i}_dtypes"] = np.array([str(v.dtype) for v in sd.values()])
+    _save(out, res)
 
 
 CASES = {
@@ -526,6 +563,7 @@ CASES = {
     "tiny_ae_ckpt": tiny_ae_ckpt,
     "spatial_heads": spatial_heads,
     "box_raster": box_raster,
+    "reference_state_dicts": reference_state_dicts,
 }
 
 if __name__ == "__main__":

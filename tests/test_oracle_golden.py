@@ -365,31 +365,21 @@ def test_checkpoint_contract(golden, tmp_path):
         assert torch.equal(v, ck["state_dict"][k]), k
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/src"), reason="needs the reference checkout (build container only)")
-def test_product_state_dict_loads_into_reference_modules():
+def test_product_state_dict_loads_into_reference_modules(golden):
     """Product -> reference direction of the checkpoint contract: ``state_dict()`` of the drop-in modules loads into the
-    reference's own nn.Modules with ``strict=True`` (names, shapes and layouts all match)."""
-    import sys
-    sys.path.insert(0, "/root/reference")
-    try:
-        from src.autoencoder.components import Decoder as RefDecoder, Encoder as RefEncoder
-        from src.autoencoder.components_v2 import Decoder as RefDecoderV2
-        from src.bounding_box_model.spatial_bb.components import (BoxesMergingCNN as RefBM, RoadMapBoxesMergingCNN as RefRB,
-                                                                  SpatialMappingCNN as RefSM)
-    finally:
-        sys.path.remove("/root/reference")
+    reference's own nn.Modules with ``strict=True``: the same key names in the same order, the same shapes and dtypes as the
+    reference modules' own ``state_dict()`` (tests/golden/reference_state_dicts.npz, recorded from them by make_golden.py) --
+    everything a strict ``load_state_dict`` checks."""
     from driving_dirty_amd import components, components_v2, spatial
-    pairs = [(components.Encoder(16, 8, 3, 16, 22), RefEncoder(16, 8, 3, 16, 22)),
-             (components.Decoder(16, 8, 3, 16, 22), RefDecoder(16, 8, 3, 16, 22)),
-             (components_v2.Decoder(16, 8, 3, 16, 22), RefDecoderV2(16, 8, 3, 16, 22)),
-             (spatial.SpatialMappingCNN(), RefSM()), (spatial.BoxesMergingCNN(), RefBM()),
-             (spatial.RoadMapBoxesMergingCNN(), RefRB())]
-    for i, (mine, ref) in enumerate(pairs):
+    g = golden("reference_state_dicts")
+    mods = [components.Encoder(16, 8, 3, 16, 22), components.Decoder(16, 8, 3, 16, 22), components_v2.Decoder(16, 8, 3, 16, 22),
+            spatial.SpatialMappingCNN(), spatial.BoxesMergingCNN(), spatial.RoadMapBoxesMergingCNN()]
+    for i, mine in enumerate(mods):
         synth.fill_module(mine, seed=50 + i)
-        res = ref.load_state_dict(mine.state_dict(), strict=True)
-        assert not res.missing_keys and not res.unexpected_keys
-        for k, v in ref.state_dict().items():
-            assert torch.equal(v, mine.state_dict()[k]), k
+        sd = mine.state_dict()
+        assert list(sd) == list(g[f"m{i}_keys"]), (type(mine).__name__, sorted(set(sd) ^ set(g[f"m{i}_keys"])))
+        for k, shape, dtype in zip(g[f"m{i}_keys"], g[f"m{i}_shapes"], g[f"m{i}_dtypes"]):
+            assert ",".join(str(d) for d in sd[k].shape) == shape and str(sd[k].dtype) == dtype, (type(mine).__name__, k, tuple(sd[k].shape), shape)
 
 
 def test_branch_record_and_replay():

@@ -6,7 +6,7 @@ for i in 1 2; do
   for v in "$@"; do
     tag=$(echo "$v" | tr -c 'A-Za-z0-9' '_')
     log=gpurun_out/abo_${tag}_$i.log
-    env $v timeout -k 10 400 python bench.py --no-cpu-baseline --steps 10 --warmup 3 > $log 2>&1
+    env $v timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $log 2>&1
     rc=$?
     if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "[$v] killed (rc $rc): stopping"; exit $rc; fi
     python3 - "$v" $log <<'PY'
