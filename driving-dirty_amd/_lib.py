@@ -191,6 +191,17 @@ SIGNATURES = {
     "dd_pool4_idx_relu_bf16_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "dd_f32_to_bf16": (_i32, [_p, _p, _i64, _p]),
     "dd_bf16_to_f32": (_i32, [_p, _p, _i64, _p]),
+    "dd_stitch6_bf16_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
+    "dd_stitch6_bf16_ptrs_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
+    "dd_stitch6_bf16_u8_ptrs_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_split64": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_merge64": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_dc1_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_wgrad_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dd_dec_bf16_dc34_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_dc4_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_dec_bf16_dc3_dgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    "dd_dec_bf16_dc3_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "dd_adam_step": (_i32, [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
     "dd_adam_step_rankb": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
     "dd_column_sum": (_i32, [_p, _p, _i32, _i32, _p]),

@@ -27,6 +27,26 @@ class BasicAE(LightningModule):
                                          self.input_width)
         self.decoder = self.init_decoder(self.hidden_dim, self.latent_dim, self.in_channels, self.output_height,
                                          self.output_width)
+        self.precision = hparam(hparams, "precision", "fp32")
+
+    @property
+    def precision(self):
+        """"fp32" (the reference's arithmetic) or "bf16": both conv stacks in bf16 mixed precision -- the masked-view gather writes
+        the bf16 wide image (the target view stays fp32), the encoder and decoder convs run on bf16 operands with fp32
+        accumulation, the FC tails, the MSE, every parameter and the optimizer stay fp32 (ops_bf16.DecoderConvStackBf16 states the
+        contract).  Setting it sets the encoder's and the decoder's; a fine-tuning module built on this AE inherits the encoder's
+        (roadmap.RoadMapBCE) unless its own hparams name one."""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        value = str(value)
+        if value not in ("fp32", "bf16"):
+            raise ValueError(f"BasicAE: precision must be 'fp32' or 'bf16', got {value!r}")
+        for m in (self.encoder, self.decoder):
+            if m is not None:
+                m.precision = value          # the BatchNorm2d variants (components_v2) refuse "bf16"
+        self._precision = value
 
     def init_decoder(self, hidden_dim, latent_dim, in_channels, output_height, output_width):
         return Decoder(hidden_dim, latent_dim, in_channels, output_height, output_width)
@@ -58,7 +78,9 @@ class BasicAE(LightningModule):
         """autoencoder.py:78-93: mask one view, encode, decode, ``mse_loss(y, y_hat)``."""
         keeps = keeps or {}
         target_img_index = int(np.random.randint(0, 5))
-        wide4, y = ops.wide_image(batch, "fp32", mask_slot=target_img_index, want_target=True)      # fp32 views or uint8 frames
+        # fp32 views or uint8 frames -> the wide image in this module's precision (bf16: the encoder's mixed-precision conv stack reads
+        # it) and the fp32 target view
+        wide4, y = ops.wide_image(batch, self.precision, mask_slot=target_img_index, want_target=True)
         z = self.encoder.forward_nhwc4(wide4, keeps.get("enc", (None, None)))
         y_hat = self(z, keeps.get("dec", (None, None)))
         if self.logger is not None and batch_idx % self.hparams.output_img_freq == 0:
@@ -100,4 +122,5 @@ class BasicAE(LightningModule):
         p.add_argument("--in_channels", type=int, default=3)
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--output_img_freq", type=int, default=500)
+        p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16"))     # not a reference flag: bf16 mixed precision
         return p

@@ -72,11 +72,19 @@ class Decoder(nn.Module):
         self.dc2 = nn.ConvTranspose2d(32, 32, kernel_size=3, padding=1)
         self.dc3 = nn.ConvTranspose2d(32, 32, kernel_size=2, stride=2)
         self.dc4 = nn.ConvTranspose2d(32, in_channels, kernel_size=1, stride=1)
+        # "fp32" (the reference's arithmetic) or "bf16": the conv stack in bf16 mixed precision (ops_bf16.DecoderConvStackBf16); the
+        # DenseBlocks and every parameter stay fp32 either way.  A plain attribute: never a state_dict key
+        self.precision = "fp32"
 
     def forward(self, z, keeps=(None, None)):
         from .heads import DecoderConvStack
         _require_gpu(z, "Decoder")
+        if self.precision not in ("fp32", "bf16"):
+            raise ValueError(f"Decoder: precision must be 'fp32' or 'bf16', got {self.precision!r}")
         h = self.fc2(self.fc1(z, keeps[0]), keeps[1])
+        if self.precision == "bf16":
+            from . import ops_bf16
+            return ops_bf16.decoder_conv_stack(h, self.deconv_dim_h, self.deconv_dim_w, self.dc1, self.dc2, self.dc3, self.dc4)
         return DecoderConvStack.apply(h, self.deconv_dim_h, self.deconv_dim_w, self.dc1.weight, self.dc1.bias, self.dc2.weight,
                                       self.dc2.bias, self.dc3.weight, self.dc3.bias, self.dc4.weight, self.dc4.bias)
 

@@ -126,6 +126,16 @@ class EncoderV2ConvStack(torch.autograd.Function):
 class Encoder(nn.Module):
     """components_v2.Encoder with ``bn3 = BatchNorm2d(32)``: same constructor signature and parameter names."""
 
+    # the BatchNorm2d variants have no mixed-precision mode: asking for one is an error, not a quiet fp32 run
+    @property
+    def precision(self):
+        return "fp32"
+
+    @precision.setter
+    def precision(self, value):
+        if value != "fp32":
+            raise ValueError(f"components_v2.Encoder: only precision 'fp32' is implemented (got {value!r})")
+
     def __init__(self, hidden_dim, latent_dim, in_channels, input_height, input_width):
         super().__init__()
         if in_channels != 3:
@@ -233,6 +243,16 @@ class DecoderV2ConvStack(torch.autograd.Function):
 
 class Decoder(nn.Module):
     """components_v2.Decoder (components_v2.py:59-98): same constructor signature, parameter names and RNG consumption."""
+
+    # the BatchNorm2d variants have no mixed-precision mode: asking for one is an error, not a quiet fp32 run
+    @property
+    def precision(self):
+        return "fp32"
+
+    @precision.setter
+    def precision(self, value):
+        if value != "fp32":
+            raise ValueError(f"components_v2.Decoder: only precision 'fp32' is implemented (got {value!r})")
 
     def __init__(self, hidden_dim, latent_dim, in_channels, output_height, output_width):
         super().__init__()

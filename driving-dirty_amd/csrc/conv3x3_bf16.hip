@@ -663,8 +663,19 @@ __global__ void bf_pack_kernel(const float* __restrict__ w, unsigned short* __re
 // ------------------------------------------------------------------------------------------------
 __constant__ int kViewOrderBf[6] = {0, 1, 2, 5, 4, 3};
 
+// masked-view task of BasicAE (autoencoder.py:59-73), as stitch6_kernel / stitch6_u8_ptrs_kernel do it for fp32: wide slot `mask_slot`
+// (-1: none) is blanked and its fp32 values -- the same expressions, so the same bits as the fp32 path's target -- go to `target` [B,3,H,W]
+__device__ __forceinline__ void bf_stitch_target(float* __restrict__ target, int b, int yy, int xx, int H, int W, float c0, float c1,
+                                                 float c2) {
+  if (!target) return;
+  const long plane = (long)H * W;
+  float* t = target + (long)b * 3 * plane + (long)yy * W + xx;
+  t[0] = c0; t[plane] = c1; t[2 * plane] = c2;
+}
+
 // [B,6,3,H,W] fp32 camera views -> wide NHWC4 bf16 (view order of wide_stitch_six_images, roadmap_bce_v2.py:53-64)
-__global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restrict__ views, u32x2* __restrict__ wide4, int B, int H, int W) {
+__global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restrict__ views, u32x2* __restrict__ wide4, float* __restrict__ target,
+                                                               int B, int H, int W, int mask_slot) {
   const long npx = (long)B * H * 6 * W;
   const long plane = (long)H * W;
   for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
@@ -676,6 +687,10 @@ __global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restri
     u32x2 o;
     o.x = pack_bf16(src[0], src[plane]);
     o.y = pack_bf16(src[2 * plane], 0.f);
+    if (slot == mask_slot) {
+      bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
+      o.x = 0u; o.y = 0u;
+    }
     wide4[px] = o;
   }
 }
@@ -684,7 +699,8 @@ __global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restri
 struct BfSamplePtrs {
   const float* p[64];
 };
-__global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePtrs samples, u32x2* __restrict__ wide4, int B, int H, int W) {
+__global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePtrs samples, u32x2* __restrict__ wide4, float* __restrict__ target,
+                                                                    int B, int H, int W, int mask_slot) {
   const long npx = (long)B * H * 6 * W;
   const long plane = (long)H * W;
   for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
@@ -696,6 +712,10 @@ __global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePt
     u32x2 o;
     o.x = pack_bf16(src[0], src[plane]);
     o.y = pack_bf16(src[2 * plane], 0.f);
+    if (slot == mask_slot) {
+      bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
+      o.x = 0u; o.y = 0u;
+    }
     wide4[px] = o;
   }
 }
@@ -706,7 +726,8 @@ __global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePt
 struct BfSamplePtrsU8 {
   const unsigned char* p[64];
 };
-__global__ __launch_bounds__(256) void stitch6_bf16_u8_ptrs_kernel(const BfSamplePtrsU8 samples, u32x2* __restrict__ wide4, int B, int H, int W) {
+__global__ __launch_bounds__(256) void stitch6_bf16_u8_ptrs_kernel(const BfSamplePtrsU8 samples, u32x2* __restrict__ wide4, float* __restrict__ target,
+                                                                       int B, int H, int W, int mask_slot) {
   const long npx = (long)B * H * 6 * W;
   for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
     const int xw = (int)(px % (6 * W));
@@ -714,9 +735,14 @@ __global__ __launch_bounds__(256) void stitch6_bf16_u8_ptrs_kernel(const BfSampl
     const int b = (int)(px / ((long)6 * W * H));
     const int slot = xw / W, xx = xw - slot * W;
     const unsigned char* src = samples.p[b] + (((long)kViewOrderBf[slot] * H + yy) * W + xx) * 3;
+    const float c0 = (float)src[0] / 255.0f, c1 = (float)src[1] / 255.0f, c2 = (float)src[2] / 255.0f;
     u32x2 o;
-    o.x = pack_bf16((float)src[0] / 255.0f, (float)src[1] / 255.0f);
-    o.y = pack_bf16((float)src[2] / 255.0f, 0.f);
+    o.x = pack_bf16(c0, c1);
+    o.y = pack_bf16(c2, 0.f);
+    if (slot == mask_slot) {
+      bf_stitch_target(target, b, yy, xx, H, W, c0, c1, c2);
+      o.x = 0u; o.y = 0u;
+    }
     wide4[px] = o;
   }
 }
@@ -1072,18 +1098,25 @@ int dd_conv_bf16_wgrad(const uint16_t* x, const uint16_t* dy, float* dweight, fl
   return launch_wgrad<32, 2>(x, dy, dweight, dbias, g, workspace, workspace_bytes, st);
 }
 
-int dd_stitch6_bf16(const float* views, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width, void* stream) {
+int dd_stitch6_bf16_masked(const float* views, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height, int32_t width,
+                           int32_t mask_slot, void* stream) {
   DD_REQUIRE(views && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16: bad argument");
+  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16: mask_slot %d", mask_slot);
   const long npx = (long)batch * height * 6 * width;
   hipLaunchKernelGGL(stitch6_bf16_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                     (hipStream_t)stream, views, (u32x2*)wide_nhwc4, batch, height, width);
+                     (hipStream_t)stream, views, (u32x2*)wide_nhwc4, target, batch, height, width, mask_slot);
   DD_LAUNCH_CHECK("stitch6_bf16");
   return 0;
 }
 
-int dd_stitch6_bf16_ptrs(const float* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
-                         void* stream) {
+int dd_stitch6_bf16(const float* views, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width, void* stream) {
+  return dd_stitch6_bf16_masked(views, wide_nhwc4, nullptr, batch, height, width, -1, stream);
+}
+
+int dd_stitch6_bf16_ptrs_masked(const float* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height,
+                                int32_t width, int32_t mask_slot, void* stream) {
   DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: bad argument");
+  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: mask_slot %d", mask_slot);
   for (int b0 = 0; b0 < batch; b0 += 64) {
     const int nb = min(64, batch - b0);
     BfSamplePtrs tab;
@@ -1091,15 +1124,22 @@ int dd_stitch6_bf16_ptrs(const float* const* sample_ptrs, uint16_t* wide_nhwc4, 
     for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: null sample pointer");
     const long npx = (long)nb * height * 6 * width;
     hipLaunchKernelGGL(stitch6_bf16_ptrs_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width, nb, height, width);
+                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width,
+                       target ? target + (long)b0 * 3 * height * width : nullptr, nb, height, width, mask_slot);
     DD_LAUNCH_CHECK("stitch6_bf16_ptrs");
   }
   return 0;
 }
 
-int dd_stitch6_bf16_u8_ptrs(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
-                            void* stream) {
+int dd_stitch6_bf16_ptrs(const float* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
+                         void* stream) {
+  return dd_stitch6_bf16_ptrs_masked(sample_ptrs, wide_nhwc4, nullptr, batch, height, width, -1, stream);
+}
+
+int dd_stitch6_bf16_u8_ptrs_masked(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch,
+                                   int32_t height, int32_t width, int32_t mask_slot, void* stream) {
   DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: bad argument");
+  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: mask_slot %d", mask_slot);
   for (int b0 = 0; b0 < batch; b0 += 64) {
     const int nb = min(64, batch - b0);
     BfSamplePtrsU8 tab;
@@ -1107,10 +1147,16 @@ int dd_stitch6_bf16_u8_ptrs(const unsigned char* const* sample_ptrs, uint16_t* w
     for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: null sample pointer");
     const long npx = (long)nb * height * 6 * width;
     hipLaunchKernelGGL(stitch6_bf16_u8_ptrs_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width, nb, height, width);
+                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width,
+                       target ? target + (long)b0 * 3 * height * width : nullptr, nb, height, width, mask_slot);
     DD_LAUNCH_CHECK("stitch6_bf16_u8_ptrs");
   }
   return 0;
+}
+
+int dd_stitch6_bf16_u8_ptrs(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
+                            void* stream) {
+  return dd_stitch6_bf16_u8_ptrs_masked(sample_ptrs, wide_nhwc4, nullptr, batch, height, width, -1, stream);
 }
 
 int dd_pool4_bf16_fwd(const uint16_t* feat, float* pooled, int32_t batch, int32_t h, int32_t w, int32_t c, void* stream) {

@@ -161,12 +161,13 @@ def wide_image(sample, precision="fp32", mask_slot=-1, want_target=False):
     roadmap_bce_v2.py:53-64), fp32 or bf16, in ONE pass:
       * fp32 [B,6,3,H,W] (autoencoder.py:53-57) or the collate's tuple of B fp32 [6,3,H,W] tensors (helper.py:22-23);
       * uint8 [B,6,H,W,3] or a tuple of B uint8 [6,H,W,3] decoded frames: ToTensor's /255 (data_helper.py:63-68) fused in.
-    ``mask_slot`` / ``want_target``: the masked-view task of BasicAE.six_to_one_task (fp32 image only) -> (wide4, target)."""
+    ``mask_slot`` / ``want_target``: the masked-view task of BasicAE.six_to_one_task -> (wide4, target); the target is the fp32 view
+    [B,3,H,W] in both precisions (bit for bit the same), the wide image fp32 or bf16."""
     per_sample = isinstance(sample, (tuple, list))
     if precision == "bf16":
         from . import ops_bf16
         if mask_slot >= 0 or want_target:
-            raise _lib.HotpathError("wide_image: the masked-view task is built for the fp32 image")
+            return ops_bf16.stitch6_bf16_masked(sample, mask_slot, want_target)
         if is_u8_frames(sample):
             return ops_bf16.stitch6_bf16_u8(sample)
         return ops_bf16.stitch6_bf16_samples([t.contiguous() for t in sample]) if per_sample else ops_bf16.stitch6_bf16(sample.contiguous())

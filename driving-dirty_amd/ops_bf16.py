@@ -228,3 +228,224 @@ class EncoderConvStackBf16(torch.autograd.Function):
 
 def encoder_conv_stack(x4, c1, c2, c3, pool=True):
     return EncoderConvStackBf16.apply(x4, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias, pool)
+
+
+# ------------------------------------------------------------------------------------------------ BasicAE pre-training in bf16
+def _masked_out(b, h, w, dev, want_target):
+    out = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.bfloat16)
+    tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
+    return out, tgt
+
+
+def _mask_arg(mask_slot):
+    if not -1 <= int(mask_slot) <= 5:
+        raise _lib.HotpathError(f"stitch6_bf16: mask_slot {mask_slot} outside [-1, 5]")
+    return int(mask_slot)
+
+
+def stitch6_bf16_masked(sample, mask_slot=-1, want_target=False):
+    """The masked-view task of BasicAE (autoencoder.py:59-73) on the bf16 image, in one pass: wide NHWC4 bf16 with wide slot
+    ``mask_slot`` blanked and, with ``want_target``, that view as fp32 [B,3,H,W] (the fp32 path's target bit for bit).  ``sample``:
+    fp32 [B,6,3,H,W], the collate's tuple of fp32 [6,3,H,W], or uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3])."""
+    slot = _mask_arg(mask_slot)
+    if ops.is_u8_frames(sample):
+        table, b, h, w, dev, _keep = ops.u8_table(sample, "stitch6_bf16_u8_masked")
+        out, tgt = _masked_out(b, h, w, dev, want_target)
+        check(_lib.lib().dd_stitch6_bf16_u8_ptrs_masked(table, _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_u8_ptrs_masked")
+    elif isinstance(sample, (tuple, list)):
+        samples = [t.contiguous() for t in sample]
+        if not samples:
+            raise _lib.HotpathError("stitch6_bf16_masked: empty batch")
+        n, c, h, w = samples[0].shape
+        if n != 6 or c != 3:
+            raise _lib.HotpathError(f"stitch6_bf16_masked: expected samples of [6,3,H,W], got {tuple(samples[0].shape)}")
+        for t in samples:
+            ops._dev(t, "sample", (6, 3, h, w))
+        b = len(samples)
+        table = (C.c_void_p * b)(*[t.data_ptr() for t in samples])
+        out, tgt = _masked_out(b, h, w, samples[0].device, want_target)
+        check(_lib.lib().dd_stitch6_bf16_ptrs_masked(table, _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_ptrs_masked")
+    else:
+        if sample.dim() != 5 or sample.shape[1] != 6 or sample.shape[2] != 3:
+            raise _lib.HotpathError(f"stitch6_bf16_masked: expected [B,6,3,H,W], got {tuple(sample.shape)}")
+        views = sample.contiguous()
+        ops._dev(views, "views")
+        b, _, _, h, w = views.shape
+        out, tgt = _masked_out(b, h, w, views.device, want_target)
+        check(_lib.lib().dd_stitch6_bf16_masked(_p(views), _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_masked")
+    return (out, tgt) if want_target else out
+
+
+def _dec_ws(layer, b, dh, dw, dev):
+    n = _lib.lib().dd_dec_bf16_wgrad_workspace_bytes(layer, b, dh, dw)
+    if n <= 0:
+        raise _lib.HotpathError(f"dec_bf16 wgrad: {_lib.lib().dd_last_error().decode()}")
+    return torch.empty(n, device=dev, dtype=torch.uint8), n
+
+
+def _bits(t, shape, who):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise _lib.HotpathError(f"{who}: relu_bits must be a contiguous int32 {tuple(shape)} device tensor")
+    return t
+
+
+def dec_split64(h, dh, dw):
+    """fc2's fp32 output [B, 64*dh*dw] (NCHW-flat) -> dc1's input as two bf16 NHWC images [B,dh,dw,32] (channels 0-31, 32-63)."""
+    b = h.shape[0]
+    ops._dev(h, "h", (b, 64 * dh * dw))
+    lo = torch.empty((b, dh, dw, 32), device=h.device, dtype=torch.bfloat16)
+    hi = torch.empty_like(lo)
+    check(_lib.lib().dd_dec_bf16_split64(_p(h), _p(lo), _p(hi), b, dh, dw, _stream()), "dd_dec_bf16_split64")
+    return lo, hi
+
+
+def dec_merge64(lo, hi):
+    """Two bf16 NHWC halves [B,dh,dw,32] -> fp32 [B, 64*dh*dw] in fc2's NCHW-flat layout."""
+    b, dh, dw, _ = lo.shape
+    _bf(lo, "lo", (b, dh, dw, 32))
+    _bf(hi, "hi", (b, dh, dw, 32))
+    gh = torch.empty((b, 64 * dh * dw), device=lo.device, dtype=torch.float32)
+    check(_lib.lib().dd_dec_bf16_merge64(_p(lo), _p(hi), _p(gh), b, dh, dw, _stream()), "dd_dec_bf16_merge64")
+    return gh
+
+
+def dec_dc1_fwd(x_lo, x_hi, w1, b1):
+    """dc1 on the bf16 matrix cores: a1 bf16 [B,dh,dw,32] = bf16(relu(dc1(x) + b1)) and its ReLU sign words [B,dh,dw]."""
+    b, dh, dw, _ = x_lo.shape
+    _bf(x_lo, "x_lo", (b, dh, dw, 32))
+    _bf(x_hi, "x_hi", (b, dh, dw, 32))
+    ops._dev(w1, "w1", (64, 32, 3, 3))
+    ops._dev(b1, "b1", (32,))
+    a1 = torch.empty((b, dh, dw, 32), device=x_lo.device, dtype=torch.bfloat16)
+    bits = torch.empty((b, dh, dw), device=x_lo.device, dtype=torch.int32)
+    check(_lib.lib().dd_dec_bf16_dc1_fwd(_p(x_lo), _p(x_hi), _p(w1), _p(b1), _p(a1), _p(bits), b, dh, dw, _stream()),
+          "dd_dec_bf16_dc1_fwd")
+    return a1, bits
+
+
+def dec_dc1_bwd(x_lo, x_hi, g1, w1, want_dx=True):
+    """dc1's backward from its bf16 pre-activation gradient g1 [B,dh,dw,32]: (gh fp32 [B, 64*dh*dw] bf16-rounded or None, dw1, db1).
+    The equivalent convolution Wc = _as_conv(w1) [32,64,3,3] splits into two 32 -> 32 layers on the input-channel halves, each the
+    encoder's c2 layer: the weight gradient is two fp32 sums (dd_conv_bf16_wgrad), the data gradient two bf16 outputs of disjoint
+    channels (dd_conv_bf16_dgrad with no ReLU mask) -- the same values the 64-channel layer gives."""
+    b, dh, dw, _ = g1.shape
+    d = conv_desc(b, dh, dw, 32, 1)
+    dlo, db1 = conv_wgrad(x_lo, g1, d)
+    dhi, _ = conv_wgrad(x_hi, g1, d)
+    dw1 = _as_conv(torch.cat((dlo, dhi), dim=1))              # [32,64,3,3] conv layout -> the ConvTranspose2d weight [64,32,3,3]
+    gh = None
+    if want_dx:
+        wc = _as_conv(w1)
+        ones = torch.full((b, dh, dw), -1, device=g1.device, dtype=torch.int32)
+        glo = conv_dgrad(g1, conv_pack(wc[:, :32].contiguous(), d, PACK_DGRAD_S1), ones, d)
+        ghi = conv_dgrad(g1, conv_pack(wc[:, 32:].contiguous(), d, PACK_DGRAD_S1), ones, d)
+        gh = dec_merge64(glo, ghi)
+    return gh, dw1, db1
+
+
+def dec_dc34_fwd(a2, w3, b3, w4, b4):
+    """a2 bf16 [B,dh,dw,32] -> a3 bf16 [B,2dh,2dw,32] = bf16(relu(dc3(a2))), y_hat fp32 [B,3,2dh,2dw] = bf16(dc4(a3))."""
+    b, dh, dw, _ = a2.shape
+    _bf(a2, "a2", (b, dh, dw, 32))
+    ops._dev(w3, "w3", (32, 32, 2, 2))
+    ops._dev(b3, "b3", (32,))
+    ops._dev(w4, "w4", (32, 3, 1, 1))
+    ops._dev(b4, "b4", (3,))
+    a3 = torch.empty((b, 2 * dh, 2 * dw, 32), device=a2.device, dtype=torch.bfloat16)
+    y = torch.empty((b, 3, 2 * dh, 2 * dw), device=a2.device, dtype=torch.float32)
+    check(_lib.lib().dd_dec_bf16_dc34_fwd(_p(a2), _p(w3), _p(b3), _p(w4), _p(b4), _p(a3), _p(y), b, dh, dw, _stream()),
+          "dd_dec_bf16_dc34_fwd")
+    return a3, y
+
+
+def dec_dc4_bwd(gy, a3, w4):
+    """-> g3 bf16 (dc3's pre-activation gradient), dw4 [32,3,1,1], db4 [3]."""
+    b, ho, wo, _ = a3.shape
+    if ho % 2 or wo % 2:
+        raise _lib.HotpathError(f"dec_dc4_bwd: a3 {tuple(a3.shape)} is not on a doubled grid")
+    _bf(a3, "a3", (b, ho, wo, 32))
+    ops._dev(gy, "gy", (b, 3, ho, wo))
+    ops._dev(w4, "w4", (32, 3, 1, 1))
+    ws, n = _dec_ws(4, b, ho // 2, wo // 2, a3.device)
+    g3 = torch.empty_like(a3)
+    dwt = torch.empty((32, 3, 1, 1), device=a3.device, dtype=torch.float32)
+    db = torch.empty(3, device=a3.device, dtype=torch.float32)
+    check(_lib.lib().dd_dec_bf16_dc4_bwd(_p(gy), _p(a3), _p(w4), _p(g3), _p(dwt), _p(db), b, ho // 2, wo // 2, _p(ws), n, _stream()),
+          "dd_dec_bf16_dc4_bwd")
+    return g3, dwt, db
+
+
+def dec_dc3_dgrad(g3, w3, bits2):
+    b, ho, wo, _ = g3.shape
+    if ho % 2 or wo % 2:
+        raise _lib.HotpathError(f"dec_dc3_dgrad: g3 {tuple(g3.shape)} is not on a doubled grid")
+    dh, dw = ho // 2, wo // 2
+    _bf(g3, "g3", (b, ho, wo, 32))
+    ops._dev(w3, "w3", (32, 32, 2, 2))
+    _bits(bits2, (b, dh, dw), "dec_dc3_dgrad")
+    g2 = torch.empty((b, dh, dw, 32), device=g3.device, dtype=torch.bfloat16)
+    check(_lib.lib().dd_dec_bf16_dc3_dgrad(_p(g3), _p(w3), _p(bits2), _p(g2), b, dh, dw, _stream()), "dd_dec_bf16_dc3_dgrad")
+    return g2
+
+
+def dec_dc3_wgrad(a2, g3):
+    b, dh, dw, _ = a2.shape
+    _bf(a2, "a2", (b, dh, dw, 32))
+    _bf(g3, "g3", (b, 2 * dh, 2 * dw, 32))
+    ws, n = _dec_ws(3, b, dh, dw, a2.device)
+    dwt = torch.empty((32, 32, 2, 2), device=a2.device, dtype=torch.float32)
+    db = torch.empty(32, device=a2.device, dtype=torch.float32)
+    check(_lib.lib().dd_dec_bf16_dc3_wgrad(_p(a2), _p(g3), _p(dwt), _p(db), b, dh, dw, _p(ws), n, _stream()), "dd_dec_bf16_dc3_wgrad")
+    return dwt, db
+
+
+def _as_conv(w):
+    """ConvTranspose2d weight [Cin,Cout,3,3] <-> the Conv2d weight [Cout,Cin,3,3] of the same stride-1 map (heads.DecoderConvStack._as_conv)."""
+    return w.permute(1, 0, 2, 3).flip(2, 3).contiguous()
+
+
+class DecoderConvStackBf16(torch.autograd.Function):
+    """heads.DecoderConvStack in bf16 mixed precision: same arguments, same fp32 NCHW-flat input [B, 64*dh*dw] and fp32 NCHW output
+    [B,3,2dh,2dw].  dc1 k3 p1 +ReLU, dc2 k3 p1 +ReLU, dc3 k2 s2 +ReLU, dc4 k1 (reference components.py:88-92).
+
+    Contract ("torch autocast equivalent", as oracle/bf16_parts.py states it for the encoder): every conv reads bf16-rounded inputs and
+    weights, accumulates in fp32 and rounds its output to bf16 once, after bias and ReLU; dc4's output y_hat is rounded to bf16 once and
+    returned as fp32.  Backward: dL/dy_hat and every pre-activation gradient are rounded to bf16 once, weight / bias gradients are fp32
+    sums of bf16 products, and the gradient handed back to fc2 is the bf16-rounded dL/d(input) in fc2's fp32 NCHW-flat layout.
+    Activations between the layers are NHWC bf16.  dc1's input is kept as two 32-channel bf16 halves: its forward is an MFMA kernel
+    of csrc/decoder_bf16.hip, its gradients and all of dc2 run on the encoder's bf16 c2 kernels (dd_conv_bf16_*), dc3 + dc4 on
+    csrc/decoder_bf16.hip.
+    """
+
+    @staticmethod
+    def forward(ctx, h, dh, dw, w1, b1, w2, b2, w3, b3, w4, b4):
+        b = h.shape[0]
+        x_lo, x_hi = dec_split64(h.contiguous(), dh, dw)
+        a1, s1 = dec_dc1_fwd(x_lo, x_hi, w1, b1)
+        d2 = conv_desc(b, dh, dw, 32, 1)
+        a2, s2 = conv_fwd(a1, conv_pack(_as_conv(w2), d2, PACK_FWD), b2, d2)
+        a3, y = dec_dc34_fwd(a2, w3.contiguous(), b3, w4.contiguous(), b4)
+        ctx.save_for_backward(x_lo, x_hi, a1, s1, a2, s2, a3, w1, w2, w3, w4)
+        ctx.dims = (dh, dw)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x_lo, x_hi, a1, s1, a2, s2, a3, w1, w2, w3, w4 = ctx.saved_tensors
+        dh, dw = ctx.dims
+        b = x_lo.shape[0]
+        g3, dw4, db4 = dec_dc4_bwd(gy.contiguous(), a3, w4.contiguous())
+        dw3, db3 = dec_dc3_wgrad(a2, g3)
+        g2 = dec_dc3_dgrad(g3, w3.contiguous(), s2)
+        del g3
+        d2 = conv_desc(b, dh, dw, 32, 1)
+        dwc, db2 = conv_wgrad(a1, g2, d2)
+        dw2 = _as_conv(dwc)                               # the map is its own inverse
+        g1 = conv_dgrad(g2, conv_pack(_as_conv(w2), d2, PACK_DGRAD_S1), s1, d2)
+        del g2
+        gh, dw1, db1 = dec_dc1_bwd(x_lo, x_hi, g1, w1.contiguous(), want_dx=ctx.needs_input_grad[0])
+        return gh, None, None, dw1, db1, dw2, db2, dw3, db3, dw4, db4
+
+
+def decoder_conv_stack(h, dh, dw, dc1, dc2, dc3, dc4):
+    return DecoderConvStackBf16.apply(h, dh, dw, dc1.weight, dc1.bias, dc2.weight, dc2.bias, dc3.weight, dc3.bias, dc4.weight, dc4.bias)

@@ -685,6 +685,43 @@ int dd_pool4_idx_relu_bf16_bwd(const float* dpooled, const uint16_t* idx, uint16
 int dd_f32_to_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);     /* n % 4 == 0, round to nearest even */
 int dd_bf16_to_f32(const uint16_t* src, float* dst, int64_t n, void* stream);
 
+/* ---- bf16 autoencoder pre-training (BasicAE precision "bf16") -------------------------------------------------------
+ * Masked-view gather (autoencoder.py:59-73) in bf16: dd_stitch6_bf16* plus `mask_slot` in [-1,5] (-1: none), whose slot of the wide
+ * image is blanked, and `target` (nullable) [B,3,H,W] fp32 that receives that view -- bit for bit the fp32 path's target. */
+int dd_stitch6_bf16_masked(const float* views, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height, int32_t width,
+                           int32_t mask_slot, void* stream);
+int dd_stitch6_bf16_ptrs_masked(const float* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height,
+                                int32_t width, int32_t mask_slot, void* stream);
+int dd_stitch6_bf16_u8_ptrs_masked(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch,
+                                   int32_t height, int32_t width, int32_t mask_slot, void* stream);
+/* The decoder conv stack (components.py:88-92) in the same contract, on the decoder grid dh x dw (dc3 doubles it).  Weights are the
+ * fp32 ConvTranspose2d tensors as the module holds them (w1 [64,32,3,3], w3 [32,32,2,2], w4 [32,3,1,1]); activations NHWC bf16 with
+ * 32 channels; relu_bits [B,dh,dw] uint32 as dd_conv_bf16_fwd writes them.  dc2 is dd_conv_bf16_* on the flipped, transposed weight.
+ *   split64    fc2's output h fp32 [B,64,dh,dw] -> x_lo, x_hi bf16 [B,dh,dw,32] (channels 0-31, 32-63), rounded once.  dc1's
+ *              weight and data gradients are then two dd_conv_bf16_wgrad / _dgrad launches each on the 32-channel halves of the
+ *              equivalent convolution (a data gradient with all-ones relu_bits), and merge64 writes the data gradient's two bf16
+ *              halves back as fp32 [B,64,dh,dw] for fc2.
+ *   dc1_fwd    x_lo, x_hi -> a1 = bf16(relu(dc1(x))) [B,dh,dw,32] on the bf16 matrix cores, relu_bits (nullable)
+ *   dc34_fwd   a2 -> a3 = bf16(relu(dc3(a2))) [B,2dh,2dw,32] and y = bf16(dc4(a3)) fp32 [B,3,2dh,2dw]
+ *   dc4_bwd    gy fp32 [B,3,2dh,2dw] (rounded on load) -> g3 = bf16((a3 > 0) * dc4'(gy)) and dweight [32,3,1,1], dbias [3]
+ *   dc3_dgrad  g3 -> g2 = bf16(bit(relu_bits of a2) * dc3'(g3)) [B,dh,dw,32]
+ *   dc3_wgrad  dweight [32,32,2,2], dbias [32] from a2 and g3
+ * Weight gradients go through `workspace` (dd_dec_bf16_wgrad_workspace_bytes(layer 3 or 4, ...) bytes) and a fixed-order reduction:
+ * deterministic.  bf16 buffers 16-byte aligned. */
+int dd_dec_bf16_split64(const float* h, uint16_t* x_lo, uint16_t* x_hi, int32_t batch, int32_t dh, int32_t dw, void* stream);
+int dd_dec_bf16_merge64(const uint16_t* g_lo, const uint16_t* g_hi, float* gh, int32_t batch, int32_t dh, int32_t dw, void* stream);
+int dd_dec_bf16_dc1_fwd(const uint16_t* x_lo, const uint16_t* x_hi, const float* w1, const float* b1, uint16_t* a1, uint32_t* relu_bits,
+                        int32_t batch, int32_t dh, int32_t dw, void* stream);
+int64_t dd_dec_bf16_wgrad_workspace_bytes(int32_t layer, int32_t batch, int32_t dh, int32_t dw);
+int dd_dec_bf16_dc34_fwd(const uint16_t* a2, const float* w3, const float* b3, const float* w4, const float* b4, uint16_t* a3,
+                         float* y, int32_t batch, int32_t dh, int32_t dw, void* stream);
+int dd_dec_bf16_dc4_bwd(const float* gy, const uint16_t* a3, const float* w4, uint16_t* g3, float* dweight, float* dbias,
+                        int32_t batch, int32_t dh, int32_t dw, void* workspace, int64_t workspace_bytes, void* stream);
+int dd_dec_bf16_dc3_dgrad(const uint16_t* g3, const float* w3, const uint32_t* relu_bits, uint16_t* g2, int32_t batch, int32_t dh,
+                          int32_t dw, void* stream);
+int dd_dec_bf16_dc3_wgrad(const uint16_t* a2, const uint16_t* g3, float* dweight, float* dbias, int32_t batch, int32_t dh, int32_t dw,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
