@@ -159,6 +159,12 @@ SIGNATURES = {
     "dd_linear_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
     "dd_threat_score_workspace_bytes": (_i64, []),
     "dd_threat_score": (_i32, [_p, _p, _p, _i64, _i32, _p, _p]),
+    "dd_label_components_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dd_label_components": (_i32, [_p, _f32, _p, _i32, _i32, _i32, _p]),
+    "dd_component_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dd_component_boxes": (_i32, [_p, _f32, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_box_iou_ats_workspace_bytes": (_i64, [_p, _p, _i32]),
+    "dd_box_iou_ats": (_i32, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     "dd_conv_wino_packed_floats": (_i64, [_p]),
     "dd_conv_wino_pack": (_i32, [_p, _p, _p, _i32, _p]),
     "dd_conv_wino_fwd_relu_bits": (_i32, [_p, _p, _p, _p, _p, _p, _p]),

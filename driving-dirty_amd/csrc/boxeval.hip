@@ -1,0 +1,537 @@
+// Box-level validation on the device: predicted occupancy map -> connected components -> axis-aligned boxes -> pairwise IoU ->
+// average threat score (reference src/utils/helper.py:33-83, compute_ats_bounding_boxes / compute_iou).  The inverse direction of
+// raster.hip.  None of this touches the matrix cores: the labelling is bound by latency (pointer chasing), the rest by HBM.
+//
+// a. dd_label_components: 4-connected components of `map > threshold`, as a union-find over pixels.  The output buffer IS the parent
+//    array while the kernels run: labels[p] = parent(p) + 1 for a foreground pixel, 0 for background (p = row * W + col inside its
+//    sample; nothing ever points across samples).  INVARIANT, kept by every write below: parent(p) <= p and parent(p) is a pixel
+//    of p's component.  So every parent chain strictly decreases until it reaches a root (parent(r) == r), a tree's root is its
+//    smallest pixel, and once all neighbouring pairs are united the root is the component's FIRST PIXEL IN RASTER ORDER -- the
+//    canonical label, independent of scheduling.
+//      1. tile_label_kernel: one workgroup per 32x32 tile, union-find in LDS over the tile's pixels (left and upper neighbour of each
+//         pixel), then every pixel is written with its tile root (local raster order == global raster order inside a tile).
+//      2. border_merge_kernel: one thread per pixel on a tile's left column / top row unites it with its neighbour across the border,
+//         with vector atomicMin on the global array.
+//      3. flatten_kernel: labels[p] = root(p) + 1.
+//    LOOP BOUNDS.  find(): the index strictly decreases, so at most `n` steps (n = pixels in the tile / in the sample); the loops are
+//    written `for (it < n)` so that they end even if the invariant were broken.  unite(a, b): every round that does not return
+//    replaces (a, b) by two roots that are both smaller than the old max(a, b) (see the function), so at most `n` rounds; written the
+//    same way.  No kernel waits for another workgroup: an atomicMin that loses a race returns the winner's value and the loop goes on
+//    from there with a strictly smaller pair.  Stale (cached) reads of the parent array are harmless: an old parent is still an
+//    ancestor in the same tree with a smaller index.
+// b. dd_component_boxes: a. into the workspace, then per component pixel count and extents by integer atomics at the root's slot (one
+//    set of atomics per horizontal run inside a 64-pixel segment, found with a ballot -- no loop), then a row-count / row-scan /
+//    in-row-scan compaction that orders the survivors by label.  Integer atomics only, so the result is deterministic.
+// c. dd_box_iou_ats: one thread per box pair, fp64, Green's theorem over the boundary of the intersection (fully unrolled: no
+//    indexed local array, no scratch), then one workgroup per sample for max over set 1, the five thresholds and the weighted mean.
+#include "dd_common.h"
+
+// the IoU's sign tests rely on x*y - z*w being exactly zero for equal products and exactly negated when the operands swap: no FMA
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kTile = 32;                 // tile side of the LDS phase
+constexpr int kTilePix = kTile * kTile;
+constexpr int kThreads = 256;
+constexpr int kMaxSide = 8192;            // H, W
+constexpr int kMaxBatch = 65535;          // gridDim.z
+constexpr int kMaxSet = 4096;             // boxes per sample and set in dd_box_iou_ats
+
+// ------------------------------------------------------------------------------------------------ a. labelling
+__device__ __forceinline__ int lds_parent(const int* par, int x) { return __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// root of x in the tile's forest.  Bound: par[x] < x for every non-root, so x strictly decreases: at most kTilePix steps.
+__device__ __forceinline__ int lds_find(const int* par, int x) {
+  for (int it = 0; it < kTilePix; ++it) {
+    const int p = lds_parent(par, x);
+    if (p == x) break;
+    x = p;
+  }
+  return x;
+}
+
+// Unite the trees of a and b.  Each round: a, b := their roots; equal -> done; otherwise hang the larger root (call it a) under the
+// smaller with atomicMin.  If the old value was a itself the link is made.  If not, another thread hung a under `old` < a in the
+// meantime; par[a] is now min(old, b), and uniting old with b restores the connection whichever of the two won.  The new pair
+// (old, b) has both members < a = the old maximum, so the maximum strictly decreases: at most kTilePix rounds.
+__device__ __forceinline__ void lds_unite(int* par, int a, int b) {
+  for (int it = 0; it < kTilePix; ++it) {
+    a = lds_find(par, a);
+    b = lds_find(par, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(par + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void tile_label_kernel(const float* __restrict__ maps, float threshold, int* __restrict__ labels,
+                                                              int H, int W) {
+  __shared__ int par[kTilePix];
+  const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const long base = (long)blockIdx.z * H * W;
+  unsigned fg = 0;                                                    // bit k: pixel threadIdx.x + 256 k of the tile is foreground
+#pragma unroll
+  for (int k = 0; k < kTilePix / kThreads; ++k) {
+    const int i = threadIdx.x + kThreads * k;
+    const int y = y0 + i / kTile, x = x0 + i % kTile;
+    const bool f = y < H && x < W && maps[base + (long)y * W + x] > threshold;      // bounds first: ragged tiles read nothing outside
+    fg |= (unsigned)f << k;
+    par[i] = f ? i : -1;
+  }
+  __syncthreads();
+  // background entries stay -1 and are never the target of an atomic; foreground entries stay >= 0
+#pragma unroll
+  for (int k = 0; k < kTilePix / kThreads; ++k) {
+    const int i = threadIdx.x + kThreads * k;
+    if (!((fg >> k) & 1u)) continue;
+    if (i % kTile > 0 && lds_parent(par, i - 1) >= 0) lds_unite(par, i, i - 1);
+    if (i >= kTile && lds_parent(par, i - kTile) >= 0) lds_unite(par, i, i - kTile);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kTilePix / kThreads; ++k) {
+    const int i = threadIdx.x + kThreads * k;
+    const int y = y0 + i / kTile, x = x0 + i % kTile;
+    if (y >= H || x >= W) continue;
+    int v = 0;
+    if ((fg >> k) & 1u) {
+      const int r = lds_find(par, i);                                 // the tile root: smallest local index == smallest global index
+      v = (y0 + r / kTile) * W + x0 + r % kTile + 1;
+    }
+    labels[base + (long)y * W + x] = v;
+  }
+}
+
+__device__ __forceinline__ int g_parent(const int* lab, int x) { return __hip_atomic_load(lab + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1; }
+
+// root of x in the sample's forest (lab = the sample's labels, n = H * W).  x strictly decreases: at most n steps.  `halve`
+// also hangs x under its grandparent (atomicMin: the entry only ever decreases and stays inside the component -- the invariant).
+template <bool kHalve>
+__device__ __forceinline__ int g_find(int* lab, int x, int n) {
+  for (int it = 0; it < n; ++it) {
+    const int p = g_parent(lab, x);
+    if (p == x) break;
+    if (kHalve) {
+      const int gp = g_parent(lab, p);
+      if (gp != p) atomicMin(lab + x, gp + 1);
+    }
+    x = p;
+  }
+  return x;
+}
+
+// lds_unite on the global array; the same argument bounds it by n rounds.
+__device__ __forceinline__ void g_unite(int* lab, int a, int b, int n) {
+  for (int it = 0; it < n; ++it) {
+    a = g_find<true>(lab, a, n);
+    b = g_find<true>(lab, b, n);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(lab + a, b + 1) - 1;
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// items of one sample: nv vertical borders (columns kTile, 2 kTile, ...) of H pixels each, then nh horizontal borders of W pixels
+__global__ __launch_bounds__(kThreads) void border_merge_kernel(int* __restrict__ labels, int H, int W, int nv, int nh) {
+  int* lab = labels + (long)blockIdx.y * H * W;
+  const int n = H * W;
+  int idx = blockIdx.x * kThreads + threadIdx.x;
+  int p, q;
+  if (idx < nv * H) {
+    const int x = (idx / H + 1) * kTile, y = idx % H;                 // x <= nv * kTile <= W - 1
+    p = y * W + x;
+    q = p - 1;
+  } else {
+    idx -= nv * H;
+    if (idx >= nh * W) return;
+    const int y = (idx / W + 1) * kTile, x = idx % W;                 // y <= nh * kTile <= H - 1
+    p = y * W + x;
+    q = p - W;
+  }
+  if (g_parent(lab, p) >= 0 && g_parent(lab, q) >= 0) g_unite(lab, p, q, n);
+}
+
+struct Stats {        // per component, at its root pixel's slot; all maxima, so zero initialises them
+  int count, w1_minus_c0, c1, r1;
+};
+
+// labels[p] = root + 1.  In place: a thread that walks through p meanwhile sees the old parent or the root, both ancestors.
+__global__ __launch_bounds__(kThreads) void flatten_kernel(int* __restrict__ labels, Stats* __restrict__ stats, int n) {
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= n) return;
+  int* lab = labels + (long)blockIdx.y * n;
+  if (g_parent(lab, p) < 0) return;
+  const int r = g_find<false>(lab, p, n);
+  __hip_atomic_store(lab + p, r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (stats && r == p) stats[(long)blockIdx.y * n + p] = Stats{0, 0, 0, 0};
+}
+
+int label_launch(const float* maps, float threshold, int* labels, Stats* stats, int batch, int H, int W, hipStream_t st) {
+  const int tx = (W + kTile - 1) / kTile, ty = (H + kTile - 1) / kTile;
+  hipLaunchKernelGGL(tile_label_kernel, dim3(tx, ty, batch), dim3(kThreads), 0, st, maps, threshold, labels, H, W);
+  DD_LAUNCH_CHECK("label_components tiles");
+  const int nv = (W - 1) / kTile, nh = (H - 1) / kTile;
+  const long items = (long)nv * H + (long)nh * W;
+  if (items > 0) {
+    hipLaunchKernelGGL(border_merge_kernel, dim3((unsigned)((items + kThreads - 1) / kThreads), batch), dim3(kThreads), 0, st, labels, H, W,
+                       nv, nh);
+    DD_LAUNCH_CHECK("label_components borders");
+  }
+  const int n = H * W;
+  hipLaunchKernelGGL(flatten_kernel, dim3((n + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, labels, stats, n);
+  DD_LAUNCH_CHECK("label_components flatten");
+  return 0;
+}
+
+bool shape_ok(int batch, int H, int W) { return batch >= 1 && batch <= kMaxBatch && H >= 1 && W >= 1 && H <= kMaxSide && W <= kMaxSide; }
+
+// ------------------------------------------------------------------------------------------------ b. component boxes
+// One wave per 64-pixel segment of a row.  Horizontally adjacent foreground pixels share their label, so a run of set bits in the
+// ballot is one component: its first lane adds the run to the root's slot.
+__global__ __launch_bounds__(kThreads) void run_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int H, int W) {
+  const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
+  const long base = (long)blockIdx.z * H * W;
+  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  const unsigned long long mask = __ballot(v != 0);
+  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+  const unsigned long long inv = ~(mask >> lane);                     // lowest zero bit = end of the run; none: the run fills the segment
+  const int len = inv ? __ffsll((long long)inv) - 1 : 64;
+  Stats* s = stats + base + (v - 1);
+  atomicAdd(&s->count, len);
+  atomicMax(&s->w1_minus_c0, W - 1 - x);
+  atomicMax(&s->c1, x + len - 1);
+  atomicMax(&s->r1, y);
+}
+
+// exclusive prefix sum of v over the workgroup's 256 threads; total = the sum.  wsum: 4 ints of LDS.
+__device__ __forceinline__ int block_scan(int v, int* wsum, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d);
+    if (lane >= d) inc += o;
+  }
+  __syncthreads();                                                    // wsum may still be read from the previous call
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  int off = 0;
+  total = 0;
+#pragma unroll
+  for (int k = 0; k < kThreads / 64; ++k) {
+    const int t = wsum[k];
+    if (k < w) off += t;
+    total += t;
+  }
+  return off + inc - v;
+}
+
+__device__ __forceinline__ bool survivor(const int* lab, const Stats* st, int p, int min_pixels) {
+  return lab[p] == p + 1 && st[p].count >= min_pixels;
+}
+
+__global__ __launch_bounds__(kThreads) void row_count_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, int* __restrict__ rowcnt,
+                                                             int H, int W, int min_pixels) {
+  __shared__ int wsum[kThreads / 64];
+  const int y = blockIdx.x, s = blockIdx.y;
+  const long base = (long)s * H * W;
+  int c = 0;
+  for (int x = threadIdx.x; x < W; x += kThreads) c += survivor(labels + base, stats + base, y * W + x, min_pixels);
+  int total;
+  block_scan(c, wsum, total);
+  if (threadIdx.x == 0) rowcnt[s * H + y] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void row_scan_kernel(const int* __restrict__ rowcnt, int* __restrict__ rowbase, int* __restrict__ counts, int H) {
+  __shared__ int wsum[kThreads / 64];
+  const int s = blockIdx.x;
+  int carry = 0;
+  for (int y0 = 0; y0 < H; y0 += kThreads) {                          // uniform trip count: the scan's barriers are reached by all
+    const int y = y0 + threadIdx.x;
+    const int v = y < H ? rowcnt[s * H + y] : 0;
+    int total;
+    const int ex = block_scan(v, wsum, total);
+    if (y < H) rowbase[s * H + y] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) counts[s] = carry;                            // uncapped
+}
+
+__global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, const int* __restrict__ rowcnt,
+                                                              const int* __restrict__ rowbase, float* __restrict__ boxes, int H, int W,
+                                                              int min_pixels, int max_boxes) {
+  __shared__ int wsum[kThreads / 64];
+  const int y = blockIdx.x, s = blockIdx.y;
+  if (rowcnt[s * H + y] == 0) return;                                 // uniform
+  const long base = (long)s * H * W;
+  int carry = rowbase[s * H + y];
+  for (int x0 = 0; x0 < W; x0 += kThreads) {
+    const int x = x0 + threadIdx.x;
+    const bool f = x < W && survivor(labels + base, stats + base, y * W + x, min_pixels);
+    int total;
+    const int slot = carry + block_scan(f, wsum, total);
+    carry += total;
+    if (f && slot < max_boxes) {                                      // the only store: slot in [0, max_boxes)
+      const Stats st = stats[base + y * W + x];
+      const int c0 = W - 1 - st.w1_minus_c0, c1 = st.c1, r0 = y, r1 = st.r1;      // the root is the first pixel in raster order: its row is r0
+      const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;        // exact: multiples of 0.5 far below 2^23
+      const float xmin = ((float)c0 - hw) / 10.f, xmax = ((float)(c1 + 1) - hw) / 10.f;
+      const float ymin = (hh - (float)(r1 + 1)) / 10.f, ymax = (hh - (float)r0) / 10.f;
+      float* o = boxes + ((long)s * max_boxes + slot) * 8;
+      o[0] = xmax; o[1] = xmax; o[2] = xmin; o[3] = xmin;
+      o[4] = ymax; o[5] = ymin; o[6] = ymax; o[7] = ymin;
+    }
+  }
+}
+
+long align16(long v) { return (v + 15) & ~15L; }
+
+// ------------------------------------------------------------------------------------------------ c. IoU and ATS
+__device__ __forceinline__ double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
+
+__device__ __forceinline__ double coord(const void* p, int dtype, long i) { return dtype ? (double)((const float*)p)[i] : ((const double*)p)[i]; }
+
+// sum of cross(p(t0), p(t1)) over the parts of P's four edges that lie inside the convex counter-clockwise quadrilateral Q.  Each
+// edge is clipped to Q's four half-planes as a parameter interval [t0, t1].  An edge PARALLEL to one of Q's (n1 == 0 exactly) is
+// classified from one number that both passes compute from the same operands, s = cross(dB, a - b) with A the first polygon: same
+// direction -> the edge belongs to the first pass when s >= 0 and to the second when s < 0 (a shared boundary piece counts once);
+// opposite direction -> interiors lie on opposite sides of a common line when s == 0, and neither pass takes it.
+template <bool kFirst>
+__device__ __forceinline__ double clipped_boundary(const double (&px)[4], const double (&py)[4], const double (&qx)[4], const double (&qy)[4]) {
+  double acc = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const double ax = px[i], ay = py[i], dx = px[(i + 1) & 3] - ax, dy = py[(i + 1) & 3] - ay;
+    double t0 = 0.0, t1 = 1.0;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double ex = qx[(k + 1) & 3] - qx[k], ey = qy[(k + 1) & 3] - qy[k];
+      const double n0 = cross2(ex, ey, ax - qx[k], ay - qy[k]);       // > 0: the edge's start is inside half-plane k
+      const double n1 = cross2(ex, ey, dx, dy);
+      if (n1 > 0.0) t0 = fmax(t0, -n0 / n1);
+      else if (n1 < 0.0) t1 = fmin(t1, -n0 / n1);
+      else {
+        const double s = kFirst ? n0 : cross2(dx, dy, qx[k] - ax, qy[k] - ay);
+        const bool same = ex * dx + ey * dy > 0.0;
+        ok = ok && (kFirst ? (same ? s >= 0.0 : s > 0.0) : (same ? s < 0.0 : s > 0.0));
+      }
+    }
+    if (ok && t1 > t0) acc += cross2(ax + t0 * dx, ay + t0 * dy, ax + t1 * dx, ay + t1 * dy);
+  }
+  return acc;
+}
+
+// ring 0,1,3,2 of box bi, translated by (-cx,-cy), made counter-clockwise; returns twice its area (>= 0)
+__device__ __forceinline__ double load_ring(const void* boxes, int dtype, long bi, double cx, double cy, double (&x)[4], double (&y)[4]) {
+  const long o = bi * 8;
+  x[0] = coord(boxes, dtype, o + 0) - cx; y[0] = coord(boxes, dtype, o + 4) - cy;
+  x[1] = coord(boxes, dtype, o + 1) - cx; y[1] = coord(boxes, dtype, o + 5) - cy;
+  x[2] = coord(boxes, dtype, o + 3) - cx; y[2] = coord(boxes, dtype, o + 7) - cy;
+  x[3] = coord(boxes, dtype, o + 2) - cx; y[3] = coord(boxes, dtype, o + 6) - cy;
+  double a2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a2 += cross2(x[i], y[i], x[(i + 1) & 3], y[(i + 1) & 3]);
+  if (a2 < 0.0) {
+    double t = x[1]; x[1] = x[3]; x[3] = t;
+    t = y[1]; y[1] = y[3]; y[3] = t;
+    a2 = -a2;
+  }
+  return a2;
+}
+
+struct SetOffsets {       // by value in the kernel arguments, 64 samples per launch
+  int first1[65], first2[65];
+  long mfirst[65];        // sample s's IoU matrix [n1,n2] starts at iou[mfirst[s]]
+};
+
+__global__ __launch_bounds__(kThreads) void pair_iou_kernel(const void* __restrict__ boxes1, int dtype1, const void* __restrict__ boxes2, int dtype2,
+                                                            const SetOffsets offs, float* __restrict__ iou) {
+  const int s = blockIdx.y;
+  const int n1 = offs.first1[s + 1] - offs.first1[s], n2 = offs.first2[s + 1] - offs.first2[s];
+  const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= (long)n1 * n2) return;
+  const int i = (int)(idx / n2), j = (int)(idx % n2);
+  const long bi = offs.first1[s] + i, bj = offs.first2[s] + j;
+  // translate both to A's centroid: the products below are then of box-sized numbers, not of +-40 m coordinates
+  double cx = 0.0, cy = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cx += coord(boxes1, dtype1, bi * 8 + k);
+    cy += coord(boxes1, dtype1, bi * 8 + 4 + k);
+  }
+  cx *= 0.25;
+  cy *= 0.25;
+  double ax[4], ay[4], bx[4], by[4];
+  const double area_a = 0.5 * load_ring(boxes1, dtype1, bi, cx, cy, ax, ay);
+  const double area_b = 0.5 * load_ring(boxes2, dtype2, bj, cx, cy, bx, by);
+  double inter = 0.5 * (clipped_boundary<true>(ax, ay, bx, by) + clipped_boundary<false>(bx, by, ax, ay));
+  inter = fmin(fmax(inter, 0.0), fmin(area_a, area_b));
+  const double uni = area_a + area_b - inter;
+  iou[offs.mfirst[s] + idx] = uni > 0.0 ? (float)(inter / uni) : 0.f;
+}
+
+// helper.py:59-70 for one sample: iou_max over set 1 for each box of set 2, tp per threshold, ts = tp / (n1 + n2 - tp) weighted by
+// 1 / threshold.  Integer counts, one fp64 evaluation by one thread: deterministic.  An empty set on either side scores 0.
+__global__ __launch_bounds__(kThreads) void ats_kernel(const float* __restrict__ iou, const SetOffsets offs, float* __restrict__ ats) {
+  __shared__ int tp[5];
+  const int s = blockIdx.x;
+  const int n1 = offs.first1[s + 1] - offs.first1[s], n2 = offs.first2[s + 1] - offs.first2[s];
+  if (n1 == 0 || n2 == 0) {                                           // uniform
+    if (threadIdx.x == 0) ats[s] = 0.f;
+    return;
+  }
+  if (threadIdx.x < 5) tp[threadIdx.x] = 0;
+  __syncthreads();
+  const float* m = iou + offs.mfirst[s];
+  const double thr[5] = {0.5, 0.6, 0.7, 0.8, 0.9};
+  for (int j = threadIdx.x; j < n2; j += kThreads) {
+    float best = 0.f;
+    for (int i = 0; i < n1; ++i) best = fmaxf(best, m[(long)i * n2 + j]);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if ((double)best > thr[k]) atomicAdd(&tp[k], 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = 0.0, weight = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      total += (1.0 / thr[k]) * ((double)tp[k] / (double)(n1 + n2 - tp[k]));      // tp <= n2 and n1 >= 1: the denominator is positive
+      weight += 1.0 / thr[k];
+    }
+    ats[s] = (float)(total / weight);
+  }
+}
+
+int check_offsets(const int32_t* off, int batch, const char* what) {
+  DD_REQUIRE(off[0] >= 0, DD_ERR_BAD_ARG, "box_iou_ats: %s offsets must be non-negative", what);
+  for (int s = 0; s < batch; ++s) {
+    DD_REQUIRE(off[s + 1] >= off[s], DD_ERR_BAD_ARG, "box_iou_ats: %s offsets must be non-decreasing", what);
+    DD_REQUIRE(off[s + 1] - off[s] <= kMaxSet, DD_ERR_UNSUPPORTED, "box_iou_ats: at most %d boxes per sample and set (%s has %d)", kMaxSet,
+               what, off[s + 1] - off[s]);
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t dd_label_components_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+  if (!shape_ok(batch, height, width)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "label_components: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", kMaxBatch, kMaxSide, batch,
+            height, width);
+    return -1;
+  }
+  return 0;      // the labels buffer itself is the parent array
+}
+
+int dd_label_components(const float* maps, float threshold, int32_t* labels, int32_t batch, int32_t height, int32_t width, void* stream) {
+  DD_REQUIRE(maps && labels, DD_ERR_BAD_ARG, "label_components: null pointer");
+  DD_REQUIRE(shape_ok(batch, height, width), DD_ERR_UNSUPPORTED, "label_components: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)",
+             kMaxBatch, kMaxSide, batch, height, width);
+  return label_launch(maps, threshold, labels, nullptr, batch, height, width, (hipStream_t)stream);
+}
+
+int64_t dd_component_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+  if (!shape_ok(batch, height, width)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "component_boxes: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", kMaxBatch, kMaxSide, batch,
+            height, width);
+    return -1;
+  }
+  const long n = (long)batch * height * width;
+  return align16(n * (long)sizeof(int)) + n * (long)sizeof(Stats) + 2 * align16((long)batch * height * (long)sizeof(int));
+}
+
+int dd_component_boxes(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch,
+                       int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(maps && boxes && counts && workspace, DD_ERR_BAD_ARG, "component_boxes: null pointer");
+  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "component_boxes: min_pixels and max_boxes must be positive");
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "component_boxes: workspace must be 16-byte aligned");
+  const int64_t need = dd_component_boxes_workspace_bytes(batch, height, width);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "component_boxes: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)need);
+  const long n = (long)batch * height * width;
+  char* ws = (char*)workspace;
+  int* labels = (int*)ws;
+  Stats* stats = (Stats*)(ws + align16(n * (long)sizeof(int)));
+  int* rowcnt = (int*)((char*)stats + n * (long)sizeof(Stats));
+  int* rowbase = (int*)((char*)rowcnt + align16((long)batch * height * (long)sizeof(int)));
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = label_launch(maps, threshold, labels, stats, batch, height, width, st);      // zeroes the roots' slots
+  if (rc) return rc;
+  hipLaunchKernelGGL(run_stats_kernel, dim3((width + 63) / 64, (height + 3) / 4, batch), dim3(64, 4), 0, st, labels, stats, height, width);
+  DD_LAUNCH_CHECK("component_boxes stats");
+  hipLaunchKernelGGL(row_count_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, height, width, min_pixels);
+  DD_LAUNCH_CHECK("component_boxes row counts");
+  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, rowcnt, rowbase, counts, height);
+  DD_LAUNCH_CHECK("component_boxes row scan");
+  hipLaunchKernelGGL(emit_boxes_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, rowbase, boxes, height, width,
+                     min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("component_boxes emit");
+  return 0;
+}
+
+int64_t dd_box_iou_ats_workspace_bytes(const int32_t* offsets1, const int32_t* offsets2, int32_t batch) {
+  if (!offsets1 || !offsets2 || batch < 1) {
+    dd_fail(DD_ERR_BAD_ARG, "box_iou_ats: bad argument");
+    return -1;
+  }
+  if (check_offsets(offsets1, batch, "set 1") || check_offsets(offsets2, batch, "set 2")) return -1;
+  long pairs = 0;
+  for (int s = 0; s < batch; ++s) pairs += (long)(offsets1[s + 1] - offsets1[s]) * (offsets2[s + 1] - offsets2[s]);
+  return align16(pairs * (long)sizeof(float)) + 16;      // never zero: callers allocate it unconditionally
+}
+
+int dd_box_iou_ats(const void* boxes1, int32_t dtype1, const int32_t* offsets1, const void* boxes2, int32_t dtype2, const int32_t* offsets2,
+                   float* iou, float* ats, int32_t batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(offsets1 && offsets2 && ats && batch >= 1, DD_ERR_BAD_ARG, "box_iou_ats: bad argument");
+  DD_REQUIRE((dtype1 == 0 || dtype1 == 1) && (dtype2 == 0 || dtype2 == 1), DD_ERR_UNSUPPORTED, "box_iou_ats: dtype must be 0 (f64) or 1 (f32)");
+  int rc = check_offsets(offsets1, batch, "set 1");
+  if (rc) return rc;
+  rc = check_offsets(offsets2, batch, "set 2");
+  if (rc) return rc;
+  DD_REQUIRE(boxes1 || offsets1[batch] == offsets1[0], DD_ERR_BAD_ARG, "box_iou_ats: null boxes1");
+  DD_REQUIRE(boxes2 || offsets2[batch] == offsets2[0], DD_ERR_BAD_ARG, "box_iou_ats: null boxes2");
+  if (!iou) {
+    const int64_t need = dd_box_iou_ats_workspace_bytes(offsets1, offsets2, batch);
+    DD_REQUIRE(workspace && workspace_bytes >= need, DD_ERR_WORKSPACE, "box_iou_ats: workspace of %lld bytes, %lld needed (or pass iou)",
+               (long long)workspace_bytes, (long long)need);
+    iou = (float*)workspace;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  long mbase = 0;
+  for (int s0 = 0; s0 < batch; s0 += 64) {
+    const int ns = min(64, batch - s0);
+    SetOffsets offs;
+    long most = 0;
+    for (int i = 0; i <= 64; ++i) {
+      const int s = s0 + min(i, ns);
+      offs.first1[i] = offsets1[s];
+      offs.first2[i] = offsets2[s];
+      offs.mfirst[i] = mbase;
+      if (i < ns) {
+        const long pairs = (long)(offsets1[s + 1] - offsets1[s]) * (offsets2[s + 1] - offsets2[s]);
+        most = pairs > most ? pairs : most;
+        mbase += pairs;
+      }
+    }
+    if (most > 0) {
+      hipLaunchKernelGGL(pair_iou_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), ns), dim3(kThreads), 0, st, boxes1, dtype1, boxes2,
+                         dtype2, offs, iou);
+      DD_LAUNCH_CHECK("box_iou_ats pairs");
+    }
+    hipLaunchKernelGGL(ats_kernel, dim3(ns), dim3(kThreads), 0, st, (const float*)iou, offs, ats + s0);
+    DD_LAUNCH_CHECK("box_iou_ats reduce");
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@ from torch import nn
 from . import ops
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
-from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, per_sample_inputs
+from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, boxes_from_map, per_sample_inputs
 
 
 class JointRoadMapBBox(LightningModule):
@@ -46,6 +46,11 @@ class JointRoadMapBBox(LightningModule):
         z = self.ae.encoder._tail(pooled, (None, None))
         logits = ops.linear(z, self.fc1.weight, self.fc1.bias).reshape(-1, 800, 800)
         return logits, boxes
+
+    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256):
+        """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4]."""
+        with torch.no_grad():
+            return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes)
 
     def training_step(self, batch, batch_idx):
         sample, target, road_image = batch

@@ -190,6 +190,94 @@ def threat_score(a, b, round_b=False):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ box-level validation
+def _maps(maps, who):
+    if not isinstance(maps, torch.Tensor) or maps.dim() != 3:
+        raise _lib.HotpathError(f"{who}: expected fp32 maps [B,H,W], got {tuple(getattr(maps, 'shape', ()))}")
+    _dev(maps, "maps")
+    b, h, w = maps.shape
+    if b == 0 or _lib.lib().dd_label_components_workspace_bytes(b, h, w) < 0:
+        raise _lib.HotpathError(f"{who}: unsupported shape {tuple(maps.shape)}: {_lib.lib().dd_last_error().decode()}")
+    return b, h, w
+
+
+def label_components(maps, threshold=0.5):
+    """fp32 maps [B,H,W] -> int32 labels [B,H,W] of the 4-connected components of ``maps > threshold``: 0 for background, else
+    1 + the raster-order index (inside its sample) of the component's first pixel.  Canonical and deterministic."""
+    b, h, w = _maps(maps, "label_components")
+    labels = torch.empty((b, h, w), device=maps.device, dtype=torch.int32)
+    check(_lib.lib().dd_label_components(_p(maps), float(threshold), _p(labels), b, h, w, _stream()), "dd_label_components")
+    return labels
+
+
+def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256):
+    """fp32 maps [B,H,W] -> (boxes fp32 [B,max_boxes,2,4], counts int32 [B]): the axis-aligned extents of the components of
+    ``maps > threshold`` with at least ``min_pixels`` pixels, in the data set's box format (metres, ego at the centre: the inverse of
+    ``boxes_to_binary_map``'s pixel mapping), ordered by component label.  ``counts`` is the UNCAPPED number of such components:
+    ``counts[i] > max_boxes`` means sample i overflowed and only its first ``max_boxes`` boxes are present.  Unused rows are zero."""
+    b, h, w = _maps(maps, "component_boxes")
+    if int(min_pixels) < 1 or int(max_boxes) < 1:
+        raise _lib.HotpathError("component_boxes: min_pixels and max_boxes must be positive")
+    boxes = torch.zeros((b, int(max_boxes), 2, 4), device=maps.device, dtype=torch.float32)
+    counts = torch.empty((b,), device=maps.device, dtype=torch.int32)
+    nbytes = _lib.lib().dd_component_boxes_workspace_bytes(b, h, w)
+    ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
+    check(_lib.lib().dd_component_boxes(_p(maps), float(threshold), int(min_pixels), int(max_boxes), _p(boxes), _p(counts), b, h, w,
+                                        _p(ws), nbytes, _stream()), "dd_component_boxes")
+    return boxes, counts
+
+
+def _box_list(box_sets, who, device):
+    """Per-sample [n,2,4] tensors (all f64 or all f32) -> (flat device tensor [sum n, 8], dtype code, ctypes offsets)."""
+    import ctypes
+    dtypes = {t.dtype for t in box_sets}
+    if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float64, torch.float32):
+        raise _lib.HotpathError(f"{who}: boxes must all be float64 or all float32")
+    for t in box_sets:
+        if t.dim() != 3 or tuple(t.shape[1:]) != (2, 4):
+            raise _lib.HotpathError(f"{who}: expected [n,2,4] boxes, got {tuple(t.shape)}")
+    counts = [int(t.shape[0]) for t in box_sets]
+    offsets = (ctypes.c_int32 * (len(box_sets) + 1))(0, *[sum(counts[:i + 1]) for i in range(len(box_sets))])
+    flat = torch.cat([t.reshape(-1, 8) for t in box_sets], dim=0).to(device).contiguous()
+    return flat, 0 if flat.dtype == torch.float64 else 1, offsets
+
+
+def _iou_ats(box_sets1, box_sets2, want_iou, who):
+    b = len(box_sets1)
+    if b == 0 or len(box_sets2) != b:
+        raise _lib.HotpathError(f"{who}: needs two lists of the same non-zero length, got {b} and {len(box_sets2)}")
+    device = next((t.device for t in list(box_sets1) + list(box_sets2) if t.is_cuda), None)
+    if device is None:
+        raise _lib.HotpathError(f"{who}: no box tensor is on a GPU (there is no CPU fallback)")
+    flat1, dt1, off1 = _box_list(box_sets1, who, device)
+    flat2, dt2, off2 = _box_list(box_sets2, who, device)
+    nbytes = _lib.lib().dd_box_iou_ats_workspace_bytes(off1, off2, b)
+    if nbytes < 0:
+        raise _lib.HotpathError(f"{who}: {_lib.lib().dd_last_error().decode()}")
+    ats = torch.empty((b,), device=device, dtype=torch.float32)
+    pairs = sum(int(s.shape[0]) * int(t.shape[0]) for s, t in zip(box_sets1, box_sets2))
+    iou = torch.empty((max(pairs, 1),), device=device, dtype=torch.float32) if want_iou else None
+    ws = None if want_iou else torch.empty(nbytes, device=device, dtype=torch.uint8)
+    check(_lib.lib().dd_box_iou_ats(_p(flat1) if flat1.numel() else None, dt1, off1, _p(flat2) if flat2.numel() else None, dt2, off2,
+                                    _p(iou), _p(ats), b, _p(ws), 0 if want_iou else nbytes, _stream()), "dd_box_iou_ats")
+    return iou, ats
+
+
+def box_iou(boxes1, boxes2):
+    """[n1,2,4], [n2,2,4] corner tensors of one sample -> fp32 IoU matrix [n1,n2] (compute_iou, helper.py:79-83, for every pair).
+    Each box must be a convex quadrilateral of positive area with outline 0,1,3,2 (either orientation), as the data set's are."""
+    iou, _ = _iou_ats([boxes1], [boxes2], True, "box_iou")
+    n1, n2 = int(boxes1.shape[0]), int(boxes2.shape[0])
+    return iou[:n1 * n2].reshape(n1, n2)
+
+
+def ats_bounding_boxes(box_sets1, box_sets2):
+    """Two lists of B per-sample [n,2,4] corner tensors (like ``boxes_to_binary_map``'s) -> fp32 [B]: compute_ats_bounding_boxes
+    (helper.py:33-72) of each sample, ``iou_max`` taken over set 1 for each box of set 2.  DEPARTS from the reference in one point:
+    a sample where either set is empty scores 0 (the reference raises on an empty set)."""
+    return _iou_ats(box_sets1, box_sets2, False, "ats_bounding_boxes")[1]
+
+
 def nchw_to_nhwc(x, c_store):
     b, c, h, w = x.shape
     _dev(x, "x")

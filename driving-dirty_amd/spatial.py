@@ -4,6 +4,7 @@ LightningModule (reference spatial_bb/spatial_w_rm.py, registry name ``spatial_r
 parameter names, construction order (default init parity) and ``forward`` signatures; the modules only hold
 parameters, the arithmetic is ``heads.SpatialMapFn`` / ``heads.MergeFn``.
 """
+import warnings
 from argparse import ArgumentParser
 
 import torch
@@ -128,6 +129,23 @@ def bb_coord_to_map(target, device=None, rasterizer=None):
     return ops.boxes_to_binary_map([t["bounding_box"] for t in target], device)
 
 
+def compute_ats_bounding_boxes(boxes1, boxes2):
+    """helper.py:33-72 for one sample, on the device: [n1,2,4] and [n2,2,4] corner tensors -> 0-dim average threat score
+    (``iou_max`` over ``boxes1`` for each box of ``boxes2``).  An empty set scores 0 where the reference raises."""
+    return ops.ats_bounding_boxes([boxes1], [boxes2])[0]
+
+
+def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256):
+    """[b,H,W] occupancy maps -> tuple of b [n_i,2,4] box tensors (``ops.component_boxes`` cut to each sample's count)."""
+    boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes)
+    counts = counts.tolist()
+    over = [i for i, c in enumerate(counts) if c > max_boxes]
+    if over:
+        warnings.warn(f"boxes_from_map: samples {over} have more than max_boxes={max_boxes} components "
+                      f"({[counts[i] for i in over]}); only the first {max_boxes} are returned")
+    return tuple(boxes[i, :min(c, max_boxes)] for i, c in enumerate(counts))
+
+
 class BBSpatialRoadMap(LightningModule):
     """spatial_w_rm.py:25-167.  ``bb_coord_to_map`` (the per-sample PIL polygon loop of src/utils/bb_to_img.py) runs
     as one launch of the HIP rasteriser over the batch's ``'bounding_box'`` tensors; batches may instead carry a
@@ -200,13 +218,33 @@ class BBSpatialRoadMap(LightningModule):
         train_loss, _, _ = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
+    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256):
+        """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
+        [n_i,2,4] in the data set's format.  A sample with more than ``max_boxes`` components is cut there, with a warning."""
+        with torch.no_grad():
+            return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes)
+
     def validation_step(self, batch, batch_idx):
-        val_loss, _, _ = self._run_step(batch, batch_idx, step_name="valid")
-        return {"val_loss": val_loss}
+        val_loss, target_bb_img, pred_bb_img = self._run_step(batch, batch_idx, step_name="valid")
+        out = {"val_loss": val_loss}
+        if hparam(self.hparams, "box_metrics", False):
+            # the task's own unit: boxes extracted from the predicted map against the targets' boxes, and the map-level threat score
+            with torch.no_grad():
+                missing = [i for i, t in enumerate(batch[1]) if "bounding_box" not in t]
+                if missing:
+                    raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
+                pred = pred_bb_img.detach().reshape(-1, 800, 800).contiguous()
+                out["val_ats"] = ops.ats_bounding_boxes(boxes_from_map(pred), [t["bounding_box"] for t in batch[1]]).mean()
+                out["val_ts"] = ops.threat_score(target_bb_img.contiguous(), pred_bb_img.detach().contiguous(), round_b=True)
+        return out
 
     def validation_epoch_end(self, outputs):
         avg_val_loss = torch.stack([x["val_loss"] for x in outputs]).mean()
-        return {"val_loss": avg_val_loss, "log": {"avg_val_loss": avg_val_loss}}
+        logs = {"avg_val_loss": avg_val_loss}
+        for k in ("val_ats", "val_ts"):          # present only under hparams.box_metrics
+            if outputs and all(k in x for x in outputs):
+                logs["avg_" + k] = torch.stack([x[k] for x in outputs]).mean()
+        return {"val_loss": avg_val_loss, "log": logs}
 
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=self.hparams.learning_rate)
@@ -218,6 +256,9 @@ class BBSpatialRoadMap(LightningModule):
         p.add_argument("--unfreeze_epoch_no", type=int, default=0)
         p.add_argument("--batch_size", type=int, default=16)
         p.add_argument("--mse_loss", action="store_true")
+        p.add_argument("--box_metrics", action="store_true",
+                       help="validation also extracts boxes from the predicted map and reports val_ats (average threat score against the "
+                            "targets' boxes) and val_ts (map-level threat score)")
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)

@@ -566,6 +566,40 @@ int dd_column_sum(const float* dy, float* dbias, int32_t m, int32_t n, void* str
 int64_t dd_threat_score_workspace_bytes(void);
 int dd_threat_score(const float* a, const float* b, float* out, int64_t n, int32_t round_b, void* workspace, void* stream);
 
+/* ---- box-level validation: map -> components -> boxes -> IoU -> average threat score ---------
+ * The inverse direction of dd_boxes_to_binary_map, and compute_ats_bounding_boxes / compute_iou (src/utils/helper.py:33-83).
+ *
+ * 4-connected components of `maps > threshold` (maps fp32 [batch,height,width]).  labels int32 [batch,height,width]: 0 for
+ * background, otherwise 1 + the raster-order index (row * width + col, inside the sample) of the component's first pixel --
+ * canonical, independent of scheduling and of the other samples in the batch.  The labels buffer is the only storage the kernels
+ * use; the query returns 0 for a supported shape (batch <= 65535, height and width <= 8192) and -1 otherwise. */
+int64_t dd_label_components_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int dd_label_components(const float* maps, float threshold, int32_t* labels, int32_t batch, int32_t height, int32_t width, void* stream);
+
+/* Axis-aligned extents of those components with at least min_pixels pixels, ordered by label, as boxes in the data set's format
+ * (metres, ego at the centre; inverse of bb_to_img.py:14-20): pixel (r,c) covers x in [(c - W/2)/10, (c + 1 - W/2)/10] and y in
+ * [(H/2 - 1 - r)/10, (H/2 - r)/10]; boxes fp32 [batch,max_boxes,2,4] with corner columns 0 = (x_max,y_max), 1 = (x_max,y_min),
+ * 2 = (x_min,y_max), 3 = (x_min,y_min), each coordinate one fp32 division of an exact multiple of 0.5 by 10.  counts int32 [batch]
+ * = the UNCAPPED number of survivors: only the first min(counts[s], max_boxes) boxes of sample s are written, the rest of `boxes`
+ * is left as it was.  workspace: 16-byte aligned, dd_component_boxes_workspace_bytes (20 bytes per pixel; -1 = unsupported shape). */
+int64_t dd_component_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int dd_component_boxes(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch,
+                       int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Pairwise IoU and the average threat score of two box lists per sample.  boxes1 / boxes2 = the samples' [n,2,4] corner tensors
+ * concatenated on the DEVICE (dtype 0 = f64, 1 = f32), offsets1 / offsets2 = HOST arrays of batch+1 box indices, the convention of
+ * dd_boxes_to_binary_map; at most 4096 boxes per sample and set (more: DD_ERR_UNSUPPORTED).
+ * IoU = area(A n B) / area(A u B) of the quadrilaterals whose outline is the corner ring 0,1,3,2, in either orientation, computed
+ * in fp64.  PRECONDITION: both are convex with positive area -- then the outline is the convex hull the reference takes
+ * (helper.py:80-81); for anything else the result is finite but not the hull's IoU.
+ * iou (optional, may be NULL) receives the per-sample matrices [n1_s,n2_s] row-major one after the other; when it is NULL they are
+ * kept in `workspace` (dd_box_iou_ats_workspace_bytes; -1 = bad or unsupported offsets).  ats fp32 [batch] is helper.py:59-70:
+ * iou_max over set 1 for each box of set 2, and for t in 0.5..0.9: tp = #(iou_max > t), ts = tp / (n1 + n2 - tp), weighted by 1/t.
+ * Unlike the reference, which raises on an empty set, a sample with an empty set on either side scores 0. */
+int64_t dd_box_iou_ats_workspace_bytes(const int32_t* offsets1, const int32_t* offsets2, int32_t batch);
+int dd_box_iou_ats(const void* boxes1, int32_t dtype1, const int32_t* offsets1, const void* boxes2, int32_t dtype2, const int32_t* offsets2,
+                   float* iou, float* ats, int32_t batch, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- optimizer -----------------------------------------------------------------------------
  * torch.optim.Adam step (autoencoder.py:119-120, roadmap_bce_v2.py:154-157; no weight decay,
  * no amsgrad) over one flat fp32 buffer: p, g, m, v of n elements; step >= 1.  m and v are computed exactly as torch does

@@ -1,0 +1,92 @@
+"""Time the box-level validation ops on the GPU against the CPU reference of tests/_box_eval_ref.py, on the same inputs.
+
+    python tools/bench_box_eval.py [--batch 32] [--boxes 60] [--reps 20] [--out profiles/box_eval_timing.json]
+
+``component_boxes`` on [batch,800,800] rasterised targets and ``ats_bounding_boxes`` on `batch` samples of about boxes x boxes pairs:
+HIP events around `reps` calls after a warm-up (allocation of the workspace included: it is what a validation step pays).  The CPU
+side is what a user without these ops would run: scipy labelling + the Python IoU loop, once, on the cores this process may use."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import _box_eval_ref as ref  # noqa: E402
+from driving_dirty_amd import ops, synth  # noqa: E402
+
+
+def timed(fn, reps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    times.sort()
+    return {"median_ms": times[len(times) // 2], "min_ms": times[0], "max_ms": times[-1], "reps": reps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--boxes", type=int, default=60)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    # the CPU workers are forked BEFORE this process touches the GPU, so none of them holds the device open
+    import multiprocessing
+    workers = min(16, len(os.sched_getaffinity(0)))
+    pool = multiprocessing.get_context("fork").Pool(workers)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_box_eval: needs a GPU (a CPU run says nothing about these kernels)")
+    dev = torch.device("cuda:0")
+    targets = [synth.car_boxes(args.boxes, seed=100 + i) for i in range(args.batch)]
+    maps = ops.boxes_to_binary_map(targets, dev)
+
+    gpu_boxes = timed(lambda: ops.component_boxes(maps, 0.5, 1, 256), args.reps)
+    boxes, counts = ops.component_boxes(maps, 0.5, 1, 256)
+    counts = counts.tolist()
+    preds = [boxes[i, :min(c, 256)] for i, c in enumerate(counts)]
+    gpu_ats = timed(lambda: ops.ats_bounding_boxes(preds, targets), args.reps)
+    gpu_labels = timed(lambda: ops.label_components(maps, 0.5), args.reps)
+    got = ops.ats_bounding_boxes(preds, targets).cpu().numpy()
+
+    masks = (maps > 0.5).cpu().numpy()
+    preds_np, targets_np = [p.cpu().numpy() for p in preds], [t.numpy() for t in targets]
+    with pool:
+        t0 = time.perf_counter()
+        cpu_boxes = pool.map(ref.component_boxes, masks)
+        t1 = time.perf_counter()
+        cpu_ats = pool.starmap(ref.ats, zip(preds_np, targets_np))
+        t2 = time.perf_counter()
+    assert [n for _, n in cpu_boxes] == counts
+    assert float(np.abs(np.array(cpu_ats) - got).max()) <= 1e-6
+    result = {
+        "device": torch.cuda.get_device_name(0), "batch": args.batch, "boxes_per_sample": args.boxes,
+        "components_per_sample_mean": float(np.mean(counts)),
+        "gpu_label_components_ms": gpu_labels, "gpu_component_boxes_ms": gpu_boxes, "gpu_ats_bounding_boxes_ms": gpu_ats,
+        "cpu_workers": workers, "cpu_component_boxes_ms": (t1 - t0) * 1e3, "cpu_ats_bounding_boxes_ms": (t2 - t1) * 1e3,
+        "ats_mean": float(got.mean()),
+    }
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
