@@ -163,6 +163,8 @@ SIGNATURES = {
     "dd_label_components": (_i32, [_p, _f32, _p, _i32, _i32, _i32, _p]),
     "dd_component_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dd_component_boxes": (_i32, [_p, _f32, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_component_obb_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dd_component_obb": (_i32, [_p, _f32, _i32, _i32, _f32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "dd_box_iou_ats_workspace_bytes": (_i64, [_p, _p, _i32]),
     "dd_box_iou_ats": (_i32, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     "dd_conv_wino_packed_floats": (_i64, [_p]),
@@ -214,7 +216,7 @@ SIGNATURES = {
     "dd_adam_step_multi": (_i32, [C.POINTER(AdamTensor), _i32, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
 }
 
-ABI_VERSION = 3      # include/dd_hotpath.h: DD_ABI_VERSION
+ABI_VERSION = 4      # include/dd_hotpath.h: DD_ABI_VERSION
 _lib = None
 
 

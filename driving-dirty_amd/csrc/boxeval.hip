@@ -22,6 +22,15 @@
 // b. dd_component_boxes: a. into the workspace, then per component pixel count and extents by integer atomics at the root's slot (one
 //    set of atomics per horizontal run inside a 64-pixel segment, found with a ballot -- no loop), then a row-count / row-scan /
 //    in-row-scan compaction that orders the survivors by label.  Integer atomics only, so the result is deterministic.
+// b'. dd_component_obb: the same components, the same survivors in the same order, but each fitted with an ORIENTED box: the principal
+//    axis of its pixel cloud from exact integer second moments, then the extents of the pixel centres along and across that axis.
+//    After b.'s labelling, count and ordering launches: slot (the emit structure) gives every survivor its output slot and a zeroed
+//    record there; moment (the run structure) adds each run's closed-form sums to the record with 64-bit integer atomics; extent (the
+//    run structure again, a SEPARATE launch, so every moment is final) projects the two end pixels of each run -- u and v are monotone
+//    along a run -- and folds them in with 64-bit integer max on an order-preserving encoding of the fp64 value; emit writes the
+//    corners.  Integer add and integer max only: bit-identical from launch to launch.  Every thread that needs the heading evaluates
+//    the one function heading() on the same integers, so all of them agree bit for bit.  No loop in any of the four kernels except the
+//    slot kernel's walk along its row (W / 256 rounds, as in emit_boxes_kernel).
 // c. dd_box_iou_ats: one thread per box pair, fp64, Green's theorem over the boundary of the intersection (fully unrolled: no
 //    indexed local array, no scratch), then one workgroup per sample for max over set 1, the five thresholds and the weighted mean.
 #include "dd_common.h"
@@ -37,6 +46,8 @@ constexpr int kThreads = 256;
 constexpr int kMaxSide = 8192;            // H, W
 constexpr int kMaxBatch = 65535;          // gridDim.z
 constexpr int kMaxSet = 4096;             // boxes per sample and set in dd_box_iou_ats
+constexpr int kObbMaxSide = 1024;         // H, W in dd_component_obb: N <= 2^20 and Sxx <= N * 1023^2 < 2^40, so N * Sxx < 2^60 fits int64
+constexpr int kObbMaxBoxes = kObbMaxSide * kObbMaxSide;      // no sample has more components than pixels
 
 // ------------------------------------------------------------------------------------------------ a. labelling
 __device__ __forceinline__ int lds_parent(const int* par, int x) { return __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -291,6 +302,139 @@ __global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restr
 
 long align16(long v) { return (v + 15) & ~15L; }
 
+// ------------------------------------------------------------------------------------------------ b'. oriented boxes
+struct Obb {          // per survivor, at its output slot; zero initialises all of it (the four extents are maxima of codes that are never 0)
+  long long n, sx, sy, sxx, sxy, syy;
+  unsigned long long u1, neg_u0, v1, neg_v0;      // code(max u), code(max -u), code(max v), code(max -v)
+};
+
+// fp64 -> uint64, order-preserving (a < b  <=>  code(a) < code(b), -0 below +0); code(-inf) = 2^52 - 1 > 0 is the smallest code
+__device__ __forceinline__ unsigned long long code(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+
+__device__ __forceinline__ double decode(unsigned long long e) {
+  return __longlong_as_double((long long)((e >> 63) ? e & 0x7fffffffffffffffull : ~e));
+}
+
+// the major axis of the pixel cloud: theta = atan2(2 mxy, mxx - myy) / 2 in (-pi/2, pi/2], from N^2 times the central second moments,
+// which are exact in int64 for sides up to kObbMaxSide.  A cloud without a direction (mxy == 0, mxx == myy) gives atan2(0, 0) = 0.
+__device__ __forceinline__ void heading(const Obb& m, double& c, double& s) {
+  const long long mxx = m.n * m.sxx - m.sx * m.sx, myy = m.n * m.syy - m.sy * m.sy, mxy = m.n * m.sxy - m.sx * m.sy;
+  const double theta = 0.5 * atan2(2.0 * (double)mxy, (double)(mxx - myy));
+  c = cos(theta);
+  s = sin(theta);
+}
+
+// The slot of every survivor, in label order (emit_boxes_kernel's walk).  The extents of b. are not used on this path: the survivor's
+// c1 field is overwritten with its slot (uncapped), and the record of a slot below max_boxes is zeroed except for the pixel count.
+__global__ __launch_bounds__(kThreads) void obb_slot_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, const int* __restrict__ rowcnt,
+                                                            const int* __restrict__ rowbase, Obb* __restrict__ recs, int H, int W, int min_pixels,
+                                                            int max_boxes) {
+  __shared__ int wsum[kThreads / 64];
+  const int y = blockIdx.x, s = blockIdx.y;
+  if (rowcnt[s * H + y] == 0) return;                                 // uniform
+  const long base = (long)s * H * W;
+  int carry = rowbase[s * H + y];
+  for (int x0 = 0; x0 < W; x0 += kThreads) {                          // ceil(W / 256) rounds, uniform: the scan's barriers are reached by all
+    const int x = x0 + threadIdx.x;
+    const bool f = x < W && survivor(labels + base, stats + base, y * W + x, min_pixels);
+    int total;
+    const int slot = carry + block_scan(f, wsum, total);
+    carry += total;
+    if (f) {
+      Stats* st = stats + base + y * W + x;
+      st->c1 = slot;
+      if (slot < max_boxes) recs[(long)s * max_boxes + slot] = Obb{st->count, 0, 0, 0, 0, 0, 0ull, 0ull, 0ull, 0ull};      // slot in [0, max_boxes)
+    }
+  }
+}
+
+// the record of the component with label v, or null when it is no survivor or lies past the cap
+__device__ __forceinline__ Obb* obb_record(const Stats* __restrict__ stats, Obb* __restrict__ recs, long base, int sample, int v, int min_pixels,
+                                           int max_boxes) {
+  const Stats st = stats[base + (v - 1)];
+  if (st.count < min_pixels || st.c1 >= max_boxes) return nullptr;   // c1 = the slot, >= 0, written by obb_slot_kernel for every survivor
+  return recs + (long)sample * max_boxes + st.c1;
+}
+
+// run_stats_kernel's structure.  The run [x, x + len) of row y adds sum 1, X, Y, X^2, X Y, Y^2 in closed form (len <= 64: no overflow).
+__global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
+  const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
+  const long base = (long)blockIdx.z * H * W;
+  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  const unsigned long long mask = __ballot(v != 0);
+  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+  const unsigned long long inv = ~(mask >> lane);
+  const long long len = inv ? __ffsll((long long)inv) - 1 : 64;
+  Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
+  if (!r) return;
+  const long long tri = len * (len - 1) / 2, sx = len * x + tri;
+  const long long sxx = len * x * x + 2 * x * tri + (len - 1) * len * (2 * len - 1) / 6;
+  atomicAdd((unsigned long long*)&r->sx, (unsigned long long)sx);
+  atomicAdd((unsigned long long*)&r->sy, (unsigned long long)(len * y));
+  atomicAdd((unsigned long long*)&r->sxx, (unsigned long long)sxx);
+  atomicAdd((unsigned long long*)&r->sxy, (unsigned long long)(sx * y));
+  atomicAdd((unsigned long long*)&r->syy, (unsigned long long)(len * y * y));
+}
+
+// After the moment launch.  u = (X + .5) c + (Y + .5) s and v = -(X + .5) s + (Y + .5) c are monotone in X along a row (a rounded product
+// and a rounded sum are monotone in their operand), so the run's extremes are at its two end pixels.
+__global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
+  const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
+  const long base = (long)blockIdx.z * H * W;
+  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  const unsigned long long mask = __ballot(v != 0);
+  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+  const unsigned long long inv = ~(mask >> lane);
+  const int len = inv ? __ffsll((long long)inv) - 1 : 64;
+  Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
+  if (!r) return;
+  double c, s;
+  heading(*r, c, s);
+  const double xa = (double)x + 0.5, xb = (double)(x + len - 1) + 0.5, yc = (double)y + 0.5;
+  const double ua = xa * c + yc * s, ub = xb * c + yc * s, va = -xa * s + yc * c, vb = -xb * s + yc * c;
+  atomicMax(&r->u1, code(fmax(ua, ub)));
+  atomicMax(&r->neg_u0, code(-fmin(ua, ub)));
+  atomicMax(&r->v1, code(fmax(va, vb)));
+  atomicMax(&r->neg_v0, code(-fmin(va, vb)));
+}
+
+// one thread per stored box: extents moved outwards by pad (|c| + |s|), the ring (u1,v1), (u1,v0), (u0,v0), (u0,v1) rotated back to
+// pixel coordinates and mapped to metres in fp64, ONE rounding to fp32.  The ring goes to columns 0, 1, 3, 2.
+__global__ __launch_bounds__(kThreads) void obb_emit_kernel(const Obb* __restrict__ recs, const int* __restrict__ counts, float pad_px,
+                                                            float* __restrict__ boxes, long long* __restrict__ moments, int H, int W, int max_boxes) {
+  const int slot = blockIdx.x * kThreads + threadIdx.x, smp = blockIdx.y;
+  if (slot >= max_boxes || slot >= counts[smp]) return;               // the only stores: slot in [0, max_boxes)
+  const long i = (long)smp * max_boxes + slot;
+  const Obb m = recs[i];
+  double c, s;
+  heading(m, c, s);
+  const double pad = (double)pad_px * (fabs(c) + fabs(s));
+  const double u0 = -decode(m.neg_u0) - pad, u1 = decode(m.u1) + pad, v0 = -decode(m.neg_v0) - pad, v1 = decode(m.v1) + pad;
+  const double hw = 0.5 * (double)W, hh = 0.5 * (double)H;
+  const double ru[4] = {u1, u1, u0, u0}, rv[4] = {v1, v0, v0, v1};
+  const int col[4] = {0, 1, 3, 2};
+  float* o = boxes + i * 8;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double X = ru[k] * c - rv[k] * s, Y = ru[k] * s + rv[k] * c;
+    o[col[k]] = (float)((X - hw) / 10.0);
+    o[4 + col[k]] = (float)((hh - Y) / 10.0);
+  }
+  if (moments) {
+    long long* q = moments + i * 6;
+    q[0] = m.n; q[1] = m.sx; q[2] = m.sy; q[3] = m.sxx; q[4] = m.sxy; q[5] = m.syy;
+  }
+}
+
+bool obb_shape_ok(int batch, int H, int W, int max_boxes) {
+  return batch >= 1 && batch <= kMaxBatch && H >= 1 && W >= 1 && H <= kObbMaxSide && W <= kObbMaxSide && max_boxes >= 1 && max_boxes <= kObbMaxBoxes;
+}
+
 // ------------------------------------------------------------------------------------------------ c. IoU and ATS
 __device__ __forceinline__ double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
 
@@ -476,6 +620,55 @@ int dd_component_boxes(const float* maps, float threshold, int32_t min_pixels, i
   hipLaunchKernelGGL(emit_boxes_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, rowbase, boxes, height, width,
                      min_pixels, max_boxes);
   DD_LAUNCH_CHECK("component_boxes emit");
+  return 0;
+}
+
+int64_t dd_component_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes) {
+  if (!obb_shape_ok(batch, height, width, max_boxes)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "component_obb: batch in [1,%d], height and width in [1,%d] (the second moments are exact in 64-bit integers up to "
+            "there), max_boxes in [1,%d] (got %d x %d x %d, max_boxes %d)", kMaxBatch, kObbMaxSide, kObbMaxBoxes, batch, height, width, max_boxes);
+    return -1;
+  }
+  return dd_component_boxes_workspace_bytes(batch, height, width) + (long)batch * max_boxes * (long)sizeof(Obb);
+}
+
+int dd_component_obb(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts,
+                     int64_t* moments, int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(maps && boxes && counts && workspace, DD_ERR_BAD_ARG, "component_obb: null pointer");
+  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "component_obb: min_pixels and max_boxes must be positive");
+  DD_REQUIRE(pad_px >= 0.f && pad_px <= (float)kObbMaxSide, DD_ERR_BAD_ARG, "component_obb: pad_px must lie in [0,%d]", kObbMaxSide);
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "component_obb: workspace must be 16-byte aligned");
+  const int64_t need = dd_component_obb_workspace_bytes(batch, height, width, max_boxes);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "component_obb: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)need);
+  const long n = (long)batch * height * width;
+  char* ws = (char*)workspace;
+  int* labels = (int*)ws;
+  Stats* stats = (Stats*)(ws + align16(n * (long)sizeof(int)));
+  int* rowcnt = (int*)((char*)stats + n * (long)sizeof(Stats));
+  int* rowbase = (int*)((char*)rowcnt + align16((long)batch * height * (long)sizeof(int)));
+  Obb* recs = (Obb*)((char*)rowbase + align16((long)batch * height * (long)sizeof(int)));
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = label_launch(maps, threshold, labels, stats, batch, height, width, st);
+  if (rc) return rc;
+  const dim3 runs((width + 63) / 64, (height + 3) / 4, batch);
+  hipLaunchKernelGGL(run_stats_kernel, runs, dim3(64, 4), 0, st, labels, stats, height, width);
+  DD_LAUNCH_CHECK("component_obb stats");
+  hipLaunchKernelGGL(row_count_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, height, width, min_pixels);
+  DD_LAUNCH_CHECK("component_obb row counts");
+  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, rowcnt, rowbase, counts, height);
+  DD_LAUNCH_CHECK("component_obb row scan");
+  hipLaunchKernelGGL(obb_slot_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, rowbase, recs, height, width, min_pixels,
+                     max_boxes);
+  DD_LAUNCH_CHECK("component_obb slots");
+  hipLaunchKernelGGL(obb_moment_kernel, runs, dim3(64, 4), 0, st, labels, stats, recs, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("component_obb moments");
+  hipLaunchKernelGGL(obb_extent_kernel, runs, dim3(64, 4), 0, st, labels, stats, recs, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("component_obb extents");
+  hipLaunchKernelGGL(obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, recs, counts, pad_px, boxes,
+                     (long long*)moments, height, width, max_boxes);
+  DD_LAUNCH_CHECK("component_obb emit");
   return 0;
 }
 

@@ -210,16 +210,36 @@ def label_components(maps, threshold=0.5):
     return labels
 
 
-def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256):
-    """fp32 maps [B,H,W] -> (boxes fp32 [B,max_boxes,2,4], counts int32 [B]): the axis-aligned extents of the components of
-    ``maps > threshold`` with at least ``min_pixels`` pixels, in the data set's box format (metres, ego at the centre: the inverse of
+def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False):
+    """fp32 maps [B,H,W] -> (boxes fp32 [B,max_boxes,2,4], counts int32 [B]): one box for each component of ``maps > threshold`` with
+    at least ``min_pixels`` pixels, in the data set's box format (metres, ego at the centre: the inverse of
     ``boxes_to_binary_map``'s pixel mapping), ordered by component label.  ``counts`` is the UNCAPPED number of such components:
-    ``counts[i] > max_boxes`` means sample i overflowed and only its first ``max_boxes`` boxes are present.  Unused rows are zero."""
+    ``counts[i] > max_boxes`` means sample i overflowed and only its first ``max_boxes`` boxes are present.  Unused rows are zero.
+
+    ``fit="extent"``: the axis-aligned pixel extent.  ``fit="oriented"``: the rectangle along the component's principal axis (exact
+    integer second moments -> heading -> extents of the pixel centres along and across it, moved outwards by ``pad_px`` pixels:
+    0.5 = the support of the pixel squares, 0 = the hull of the centres; include/dd_hotpath.h states the fit).  Same components, same
+    order, same counts; sides up to 1024.  A principal-axis fit, not a minimum-area rectangle (for a filled rectangle the two agree);
+    which end of the box is its front is arbitrary.  ``want_moments`` (oriented only) also returns int64 [B,max_boxes,6]:
+    N, Sx, Sy, Sxx, Sxy, Syy of each stored box."""
+    if fit not in ("extent", "oriented"):
+        raise ValueError(f"component_boxes: fit must be 'extent' or 'oriented', got {fit!r}")
+    if want_moments and fit != "oriented":
+        raise ValueError("component_boxes: want_moments needs fit='oriented' (the extent fit forms no moments)")
     b, h, w = _maps(maps, "component_boxes")
     if int(min_pixels) < 1 or int(max_boxes) < 1:
         raise _lib.HotpathError("component_boxes: min_pixels and max_boxes must be positive")
     boxes = torch.zeros((b, int(max_boxes), 2, 4), device=maps.device, dtype=torch.float32)
     counts = torch.empty((b,), device=maps.device, dtype=torch.int32)
+    if fit == "oriented":
+        nbytes = _lib.lib().dd_component_obb_workspace_bytes(b, h, w, int(max_boxes))
+        if nbytes < 0:
+            raise _lib.HotpathError(f"component_boxes: unsupported shape {tuple(maps.shape)}: {_lib.lib().dd_last_error().decode()}")
+        moments = torch.zeros((b, int(max_boxes), 6), device=maps.device, dtype=torch.int64) if want_moments else None
+        ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
+        check(_lib.lib().dd_component_obb(_p(maps), float(threshold), int(min_pixels), int(max_boxes), float(pad_px), _p(boxes), _p(counts),
+                                          _p(moments), b, h, w, _p(ws), nbytes, _stream()), "dd_component_obb")
+        return (boxes, counts, moments) if want_moments else (boxes, counts)
     nbytes = _lib.lib().dd_component_boxes_workspace_bytes(b, h, w)
     ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
     check(_lib.lib().dd_component_boxes(_p(maps), float(threshold), int(min_pixels), int(max_boxes), _p(boxes), _p(counts), b, h, w,

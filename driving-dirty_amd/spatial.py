@@ -135,9 +135,10 @@ def compute_ats_bounding_boxes(boxes1, boxes2):
     return ops.ats_bounding_boxes([boxes1], [boxes2])[0]
 
 
-def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256):
-    """[b,H,W] occupancy maps -> tuple of b [n_i,2,4] box tensors (``ops.component_boxes`` cut to each sample's count)."""
-    boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes)
+def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5):
+    """[b,H,W] occupancy maps -> tuple of b [n_i,2,4] box tensors (``ops.component_boxes`` cut to each sample's count).
+    ``fit="oriented"`` fits each component along its principal axis instead of taking its axis-aligned extent."""
+    boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes, fit=fit, pad_px=pad_px)
     counts = counts.tolist()
     over = [i for i, c in enumerate(counts) if c > max_boxes]
     if over:
@@ -218,11 +219,12 @@ class BBSpatialRoadMap(LightningModule):
         train_loss, _, _ = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
-    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256):
+    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5):
         """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
-        [n_i,2,4] in the data set's format.  A sample with more than ``max_boxes`` components is cut there, with a warning."""
+        [n_i,2,4] in the data set's format.  A sample with more than ``max_boxes`` components is cut there, with a warning.
+        ``fit="oriented"``: rotated rectangles along each component's principal axis (which end is the front is arbitrary)."""
         with torch.no_grad():
-            return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes)
+            return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px)
 
     def validation_step(self, batch, batch_idx):
         val_loss, target_bb_img, pred_bb_img = self._run_step(batch, batch_idx, step_name="valid")
@@ -234,7 +236,8 @@ class BBSpatialRoadMap(LightningModule):
                 if missing:
                     raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
                 pred = pred_bb_img.detach().reshape(-1, 800, 800).contiguous()
-                out["val_ats"] = ops.ats_bounding_boxes(boxes_from_map(pred), [t["bounding_box"] for t in batch[1]]).mean()
+                fitted = boxes_from_map(pred, fit=hparam(self.hparams, "box_fit", "extent"), pad_px=hparam(self.hparams, "box_pad_px", 0.5))
+                out["val_ats"] = ops.ats_bounding_boxes(fitted, [t["bounding_box"] for t in batch[1]]).mean()
                 out["val_ts"] = ops.threat_score(target_bb_img.contiguous(), pred_bb_img.detach().contiguous(), round_b=True)
         return out
 
@@ -259,6 +262,11 @@ class BBSpatialRoadMap(LightningModule):
         p.add_argument("--box_metrics", action="store_true",
                        help="validation also extracts boxes from the predicted map and reports val_ats (average threat score against the "
                             "targets' boxes) and val_ts (map-level threat score)")
+        p.add_argument("--box_fit", type=str, default="extent", choices=("extent", "oriented"),
+                       help="how box_metrics fits a box to a component of the predicted map: its axis-aligned extent, or the rectangle "
+                            "along its principal axis (the data set's boxes are rotated)")
+        p.add_argument("--box_pad_px", type=float, default=0.5,
+                       help="oriented fit: pixels added on each side of the pixel centres' extents (0.5 = the pixel squares, 0 = the centres)")
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)

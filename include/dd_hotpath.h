@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DD_ABI_VERSION 3
+#define DD_ABI_VERSION 4
 
 enum {
   DD_OK = 0,
@@ -585,6 +585,28 @@ int dd_label_components(const float* maps, float threshold, int32_t* labels, int
 int64_t dd_component_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width);
 int dd_component_boxes(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch,
                        int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The same components, survivors, order and counts as dd_component_boxes, each fitted with an ORIENTED box (a car that is turned by
+ * 20-70 degrees has an IoU of only 0.3-0.5 with its own axis-aligned extent).  Per component, with pixel = (column X, row Y):
+ *   1. N, Sx, Sy, Sxx, Sxy, Syy = sums of 1, X, Y, X*X, X*Y, Y*Y over its pixels, exact 64-bit integers;
+ *   2. mxx = N*Sxx - Sx*Sx, myy = N*Syy - Sy*Sy, mxy = N*Sxy - Sx*Sy (exact), theta = 0.5 * atan2(2.0*mxy, (double)(mxx - myy)) in
+ *      fp64: the major axis of the pixel cloud, in image coordinates, in (-pi/2, pi/2]; a cloud without a direction (single pixel,
+ *      square, disc) gives theta = 0, the axis-aligned box;
+ *   3. with c = cos(theta), s = sin(theta) and pixel centres (X+0.5, Y+0.5): u = (X+0.5)*c + (Y+0.5)*s, v = -(X+0.5)*s + (Y+0.5)*c;
+ *      u0,u1,v0,v1 = min / max over the component, each moved outwards by pad_px * (|c| + |s|).  pad_px = 0.5 is the support of the
+ *      pixel squares (at theta = 0 the box dd_component_boxes gives), pad_px = 0 the hull of the centres, the closer inverse of an
+ *      inclusive rasteriser;
+ *   4. the ring (u1,v1), (u1,v0), (u0,v0), (u0,v1) rotated back, X = u*c - v*s, Y = u*s + v*c, then x = (X - W/2)/10,
+ *      y = (H/2 - Y)/10, all fp64, ONE rounding to fp32; the ring is stored in corner columns 0, 1, 3, 2, so those are the outline as
+ *      in the data set.  Which end is the front cannot be known from a blob: the +u end is columns 0 and 1, and that is arbitrary.
+ * A principal-axis fit, not a minimum-area rectangle; for a filled rectangle the two agree.  Integer atomics only: bit-identical from
+ * launch to launch.  moments (optional, may be NULL) int64 [batch,max_boxes,6] receives N, Sx, Sy, Sxx, Sxy, Syy of each stored box.
+ * boxes, counts, min_pixels, max_boxes: as dd_component_boxes (counts uncapped; nothing is written past min(counts[s], max_boxes)).
+ * pad_px in [0,1024].  height and width <= 1024, so that N*Sxx < 2^60 stays inside int64; max_boxes <= 1048576.  workspace: 16-byte
+ * aligned, dd_component_obb_workspace_bytes = dd_component_boxes_workspace_bytes + 80 bytes per box slot (-1 = unsupported shape). */
+int64_t dd_component_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes);
+int dd_component_obb(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts,
+                     int64_t* moments, int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Pairwise IoU and the average threat score of two box lists per sample.  boxes1 / boxes2 = the samples' [n,2,4] corner tensors
  * concatenated on the DEVICE (dtype 0 = f64, 1 = f32), offsets1 / offsets2 = HOST arrays of batch+1 box indices, the convention of

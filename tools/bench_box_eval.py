@@ -1,10 +1,13 @@
 """Time the box-level validation ops on the GPU against the CPU reference of tests/_box_eval_ref.py, on the same inputs.
 
     python tools/bench_box_eval.py [--batch 32] [--boxes 60] [--reps 20] [--out profiles/box_eval_timing.json]
+    python tools/bench_box_eval.py --fit oriented --out profiles/box_fit_timing.json
 
 ``component_boxes`` on [batch,800,800] rasterised targets and ``ats_bounding_boxes`` on `batch` samples of about boxes x boxes pairs:
 HIP events around `reps` calls after a warm-up (allocation of the workspace included: it is what a validation step pays).  The CPU
-side is what a user without these ops would run: scipy labelling + the Python IoU loop, once, on the cores this process may use."""
+side is what a user without these ops would run: scipy labelling + the Python IoU loop, once, on the cores this process may use.
+``--fit oriented`` instead times ``component_boxes(fit="oriented")`` beside the extent fit, on the same maps in the same run (no CPU
+side: the question there is what the second pass over the labels and the 64-bit atomics cost)."""
 import argparse
 import json
 import os
@@ -38,13 +41,49 @@ def timed(fn, reps, warmup=3):
     return {"median_ms": times[len(times) // 2], "min_ms": times[0], "max_ms": times[-1], "reps": reps}
 
 
+def report(result, out):
+    print(json.dumps(result))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+def bench_fit(args):
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_box_eval: needs a GPU (a CPU run says nothing about these kernels)")
+    dev = torch.device("cuda:0")
+    targets = [synth.car_boxes(args.boxes, seed=100 + i) for i in range(args.batch)]
+    maps = ops.boxes_to_binary_map(targets, dev)
+    extent = timed(lambda: ops.component_boxes(maps, 0.5, 1, 256), args.reps)
+    oriented = timed(lambda: ops.component_boxes(maps, 0.5, 1, 256, fit="oriented"), args.reps)
+    moments = timed(lambda: ops.component_boxes(maps, 0.5, 1, 256, fit="oriented", want_moments=True), args.reps)
+    extent_again = timed(lambda: ops.component_boxes(maps, 0.5, 1, 256), args.reps)      # brackets the oriented runs: drift shows here
+    _, counts = ops.component_boxes(maps, 0.5, 1, 256)
+    boxes, counts2 = ops.component_boxes(maps, 0.5, 1, 256, fit="oriented")
+    assert torch.equal(counts, counts2)
+    counts = counts.tolist()
+    ats = {}
+    for name, bx in (("extent", ops.component_boxes(maps, 0.5, 1, 256)[0]), ("oriented", boxes),
+                     ("oriented_pad0", ops.component_boxes(maps, 0.5, 1, 256, fit="oriented", pad_px=0.0)[0])):
+        ats[name] = float(ops.ats_bounding_boxes([bx[i, :min(c, 256)] for i, c in enumerate(counts)], targets).mean())
+    report({"device": torch.cuda.get_device_name(0), "batch": args.batch, "boxes_per_sample": args.boxes,
+            "components_per_sample_mean": float(np.mean(counts)),
+            "gpu_component_boxes_extent_ms": extent, "gpu_component_boxes_oriented_ms": oriented,
+            "gpu_component_boxes_oriented_with_moments_ms": moments, "gpu_component_boxes_extent_again_ms": extent_again,
+            "oriented_over_extent": oriented["median_ms"] / extent["median_ms"], "ats_mean_of_the_rasterised_targets": ats}, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--boxes", type=int, default=60)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
+    ap.add_argument("--fit", default="extent", choices=("extent", "oriented"), help="oriented: time the oriented fit beside the extent fit")
     args = ap.parse_args()
+    if args.fit == "oriented":
+        return bench_fit(args)
     # the CPU workers are forked BEFORE this process touches the GPU, so none of them holds the device open
     import multiprocessing
     workers = min(16, len(os.sched_getaffinity(0)))
@@ -80,12 +119,7 @@ def main():
         "cpu_workers": workers, "cpu_component_boxes_ms": (t1 - t0) * 1e3, "cpu_ats_bounding_boxes_ms": (t2 - t1) * 1e3,
         "ats_mean": float(got.mean()),
     }
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(json.dumps(result, indent=1) + "\n")
+    report(result, args.out)
 
 
 if __name__ == "__main__":
