@@ -438,10 +438,19 @@ bool obb_shape_ok(int batch, int H, int W, int max_boxes) {
 // ------------------------------------------------------------------------------------------------ c. IoU and ATS
 __device__ __forceinline__ double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
 
+// the sine of the angle between the edges e and d is at most 1e-12: cross(e, d)^2 <= 1e-24 |e|^2 |d|^2.  Every product and sum is
+// rounded on its own (no fused multiply-add, whichever way the surrounding code is contracted), so the answer does not depend on
+// which of the two edges is called e: cross(d, e) is exactly -cross(e, d), and the right-hand side is a commutative product
+__device__ __forceinline__ bool nearly_parallel(double ex, double ey, double dx, double dy) {
+#pragma clang fp contract(off)
+  const double c = ex * dy - ey * dx;
+  return c * c <= 1e-24 * ((ex * ex + ey * ey) * (dx * dx + dy * dy));
+}
+
 __device__ __forceinline__ double coord(const void* p, int dtype, long i) { return dtype ? (double)((const float*)p)[i] : ((const double*)p)[i]; }
 
 // sum of cross(p(t0), p(t1)) over the parts of P's four edges that lie inside the convex counter-clockwise quadrilateral Q.  Each
-// edge is clipped to Q's four half-planes as a parameter interval [t0, t1].  An edge PARALLEL to one of Q's (n1 == 0 exactly) is
+// edge is clipped to Q's four half-planes as a parameter interval [t0, t1].  An edge PARALLEL to one of Q's (to a sine of 1e-12) is
 // classified from one number that both passes compute from the same operands, s = cross(dB, a - b) with A the first polygon: same
 // direction -> the edge belongs to the first pass when s >= 0 and to the second when s < 0 (a shared boundary piece counts once);
 // opposite direction -> interiors lie on opposite sides of a common line when s == 0, and neither pass takes it.
@@ -458,8 +467,13 @@ __device__ __forceinline__ double clipped_boundary(const double (&px)[4], const 
       const double ex = qx[(k + 1) & 3] - qx[k], ey = qy[(k + 1) & 3] - qy[k];
       const double n0 = cross2(ex, ey, ax - qx[k], ay - qy[k]);       // > 0: the edge's start is inside half-plane k
       const double n1 = cross2(ex, ey, dx, dy);
-      if (n1 > 0.0) t0 = fmax(t0, -n0 / n1);
-      else if (n1 < 0.0) t1 = fmin(t1, -n0 / n1);
+      // parallel (nearly_parallel: the two passes see the same pair of edges with e and d exchanged, and agree on it bit for bit).
+      // A copy of a box shifted along its own heading has edges on a common line whose directions differ by the rounding of the
+      // corners (sine ~1e-14): -n0 / n1 is then a ratio of two rounding errors, and the shared boundary piece was counted zero,
+      // one or two times by chance (IoU 1/9 came out up to 0.03 off)
+      const bool par = nearly_parallel(ex, ey, dx, dy);
+      if (!par && n1 > 0.0) t0 = fmax(t0, -n0 / n1);
+      else if (!par && n1 < 0.0) t1 = fmin(t1, -n0 / n1);
       else {
         const double s = kFirst ? n0 : cross2(dx, dy, qx[k] - ax, qy[k] - ay);
         const bool same = ex * dx + ey * dy > 0.0;

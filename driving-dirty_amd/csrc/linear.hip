@@ -378,6 +378,7 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const float* __restrict
 }
 
 int pick_mt(int M) { return M <= 32 ? 1 : (M <= 64 ? 2 : 0); }   // 64 KB of static LDS caps the batch tile at 64 rows
+constexpr int MCHUNK = 64;      // more rows than that: the forward and the data gradient run once per 64 rows (rows are independent)
 
 int pick_split(int blocks_other, int ntiles) {
   if (ntiles <= 8) return 1;      // a handful of tiles: one block walks them faster than a second launch can add the splits up
@@ -388,7 +389,6 @@ int pick_split(int blocks_other, int ntiles) {
 
 int check_linear(const char* who, int M, int N, int K) {
   DD_REQUIRE(M > 0 && N > 0 && K > 0, DD_ERR_BAD_ARG, "%s: non-positive size", who);
-  DD_REQUIRE(pick_mt(M) != 0, DD_ERR_UNSUPPORTED, "%s: batch rows M = %d > 64", who, M);
   DD_REQUIRE(K % 4 == 0 && N % 4 == 0, DD_ERR_UNSUPPORTED, "%s: N = %d and K = %d must be multiples of 4", who, N, K);
   return 0;
 }
@@ -400,8 +400,10 @@ extern "C" {
 int64_t dd_linear_workspace_bytes(int32_t m, int32_t n, int32_t k) {
   // worst case of the forward (split-K partials [512][M][N]) and dgrad (split-N partials [512][M][K]) passes,
   // only when that pass actually splits; never more than 512 slabs of the SMALLER output
-  const int64_t fwd = ((n + 127) / 128 >= 2 * DD_NUM_CU) ? 0 : (int64_t)512 * m * n * 4;
-  const int64_t dgr = ((k + 127) / 128 >= 2 * DD_NUM_CU) ? 0 : (int64_t)512 * m * k * 4;
+  // (more than 64 rows run 64 at a time and share it)
+  const int64_t mc = m < MCHUNK ? m : MCHUNK;
+  const int64_t fwd = ((n + 127) / 128 >= 2 * DD_NUM_CU) ? 0 : (int64_t)512 * mc * n * 4;
+  const int64_t dgr = ((k + 127) / 128 >= 2 * DD_NUM_CU) ? 0 : (int64_t)512 * mc * k * 4;
   return (fwd > dgr ? fwd : dgr) + 16;
 }
 
@@ -416,17 +418,22 @@ int dd_linear_fwd(const float* x, const float* w, const float* bias, float* y, i
   const int nsplit = (ntiles + tps - 1) / tps;
   float* part = (float*)workspace;
   if (nsplit > 1)
-    DD_REQUIRE(workspace && workspace_bytes >= (int64_t)nsplit * m * n * 4, DD_ERR_WORKSPACE, "linear_fwd: workspace too small");
+    DD_REQUIRE(workspace && workspace_bytes >= (int64_t)nsplit * min(m, MCHUNK) * n * 4, DD_ERR_WORKSPACE, "linear_fwd: workspace too small");
   const dim3 grid(nblk, nsplit);
-  switch (pick_mt(m)) {
-    case 1: hipLaunchKernelGGL(linear_fwd_kernel<1>, grid, dim3(256), 0, st, x, w, bias, y, part, m, n, k, tps); break;
-    default: hipLaunchKernelGGL(linear_fwd_kernel<2>, grid, dim3(256), 0, st, x, w, bias, y, part, m, n, k, tps); break;
-  }
-  DD_LAUNCH_CHECK("linear_fwd");
-  if (nsplit > 1) {
-    const long elems = (long)m * n;
-    launch_splits_reduce(part, bias, y, elems, nsplit, n, st);
-    DD_LAUNCH_CHECK("linear_fwd reduce");
+  for (int m0 = 0; m0 < m; m0 += MCHUNK) {      // the chunks share the partials' workspace: they run in stream order
+    const int mc = min(MCHUNK, m - m0);
+    const float* xc = x + (long)m0 * k;
+    float* yc = y + (long)m0 * n;
+    switch (pick_mt(mc)) {
+      case 1: hipLaunchKernelGGL(linear_fwd_kernel<1>, grid, dim3(256), 0, st, xc, w, bias, yc, part, mc, n, k, tps); break;
+      default: hipLaunchKernelGGL(linear_fwd_kernel<2>, grid, dim3(256), 0, st, xc, w, bias, yc, part, mc, n, k, tps); break;
+    }
+    DD_LAUNCH_CHECK("linear_fwd");
+    if (nsplit > 1) {
+      const long elems = (long)mc * n;
+      launch_splits_reduce(part, bias, yc, elems, nsplit, n, st);
+      DD_LAUNCH_CHECK("linear_fwd reduce");
+    }
   }
   return 0;
 }
@@ -442,17 +449,22 @@ int dd_linear_dgrad(const float* dy, const float* w, float* dx, int32_t m, int32
   const int nsplit = (ntiles + tps - 1) / tps;
   float* part = (float*)workspace;
   if (nsplit > 1)
-    DD_REQUIRE(workspace && workspace_bytes >= (int64_t)nsplit * m * k * 4, DD_ERR_WORKSPACE, "linear_dgrad: workspace too small");
+    DD_REQUIRE(workspace && workspace_bytes >= (int64_t)nsplit * min(m, MCHUNK) * k * 4, DD_ERR_WORKSPACE, "linear_dgrad: workspace too small");
   const dim3 grid(kblk, nsplit);
-  switch (pick_mt(m)) {
-    case 1: hipLaunchKernelGGL(linear_dgrad_kernel<1>, grid, dim3(256), 0, st, dy, w, dx, part, m, n, k, tps); break;
-    default: hipLaunchKernelGGL(linear_dgrad_kernel<2>, grid, dim3(256), 0, st, dy, w, dx, part, m, n, k, tps); break;
-  }
-  DD_LAUNCH_CHECK("linear_dgrad");
-  if (nsplit > 1) {
-    const long elems = (long)m * k;
-    launch_splits_reduce(part, nullptr, dx, elems, nsplit, k, st);
-    DD_LAUNCH_CHECK("linear_dgrad reduce");
+  for (int m0 = 0; m0 < m; m0 += MCHUNK) {
+    const int mc = min(MCHUNK, m - m0);
+    const float* dyc = dy + (long)m0 * n;
+    float* dxc = dx + (long)m0 * k;
+    switch (pick_mt(mc)) {
+      case 1: hipLaunchKernelGGL(linear_dgrad_kernel<1>, grid, dim3(256), 0, st, dyc, w, dxc, part, mc, n, k, tps); break;
+      default: hipLaunchKernelGGL(linear_dgrad_kernel<2>, grid, dim3(256), 0, st, dyc, w, dxc, part, mc, n, k, tps); break;
+    }
+    DD_LAUNCH_CHECK("linear_dgrad");
+    if (nsplit > 1) {
+      const long elems = (long)mc * k;
+      launch_splits_reduce(part, nullptr, dxc, elems, nsplit, k, st);
+      DD_LAUNCH_CHECK("linear_dgrad reduce");
+    }
   }
   return 0;
 }

@@ -54,7 +54,7 @@ class JointRoadMapBBox(LightningModule):
 
     def training_step(self, batch, batch_idx):
         sample, target, road_image = batch
-        if per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image) and len(road_image) <= 64:
+        if per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image) and len(road_image) <= ops.PTR_TABLE_MAX:
             # roadmap_bce_v2.py:87 / spatial_w_rm.py:100-105 without the stacks: views and masks are read where the collate left them
             dev = sample[0].device
             b = len(sample)

@@ -1146,6 +1146,26 @@ class EncoderTail(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------ losses
+PTR_TABLE_MAX = 64        # samples per pointer table of dd_bce_logits_u8_ptrs (the table travels in the kernel arguments)
+
+
+def _check_masks(target, n):
+    """The collate's tuple of per-sample masks for ``n`` logits -> elements per sample; raises on anything the byte kernels cannot read."""
+    b = len(target)
+    per = n // max(b, 1)
+    for t in target:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.bool, torch.uint8) and t.numel() == per):
+            raise _lib.HotpathError("bce: per-sample masks must be contiguous bool / uint8 GPU tensors of logits.numel() / batch elements")
+    if b * per != n:
+        raise _lib.HotpathError(f"bce: {b} masks of {per} elements for {n} logits")
+    return per
+
+
+def _stack_masks(target, shape):
+    """One byte copy of the per-sample masks into a tensor of the logits' shape, for dd_bce_logits_u8."""
+    return torch.stack(tuple(t.reshape(-1) for t in target), dim=0).reshape(shape)
+
+
 def _loss_ws(n, device):
     return torch.empty(_lib.lib().dd_loss_workspace_bytes(n), device=device, dtype=torch.uint8)
 
@@ -1179,6 +1199,9 @@ class BceWithLogits(torch.autograd.Function):
         n = logits.numel()
         loss = torch.empty((), device=logits.device, dtype=torch.float32)
         dz = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
+        if isinstance(target, (tuple, list)):               # the collate's tuple of per-sample masks: stacked (any batch size)
+            _check_masks(target, n)
+            target = _stack_masks(target, logits.shape)
         if target.dtype in (torch.bool, torch.uint8):      # the dataset's bool road masks, read as bytes
             if not target.is_cuda or not target.is_contiguous() or target.shape != logits.shape:
                 raise _lib.HotpathError(f"bce: target must be a contiguous GPU tensor of shape {tuple(logits.shape)}")
@@ -1212,10 +1235,12 @@ class BceWithLogitsProbs(torch.autograd.Function):
         probs = torch.empty_like(logits)
         dz = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
         if isinstance(target, (tuple, list)):
-            b, per = len(target), n // max(len(target), 1)
-            for t in target:
-                if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.bool, torch.uint8) and t.numel() == per):
-                    raise _lib.HotpathError("bce: per-sample masks must be contiguous bool / uint8 GPU tensors of logits.numel() / batch elements")
+            b, per = len(target), _check_masks(target, n)
+            if b > PTR_TABLE_MAX:
+                # past the pointer table's size the masks are stacked after all and take dd_bce_logits_u8: the same arithmetic in
+                # the same order over the same grid, so the same bits as the table kernel would give
+                target = _stack_masks(target, logits.shape)
+        if isinstance(target, (tuple, list)):
             table = (C.c_void_p * b)(*[t.data_ptr() for t in target])
             check(_lib.lib().dd_bce_logits_u8_ptrs(_p(logits), table, b, per, _p(loss), _p(dz), _p(probs), 1.0,
                                                    _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits_u8_ptrs")

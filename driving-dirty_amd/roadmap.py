@@ -64,7 +64,7 @@ class RoadMapBCE(LightningModule):
         sample, target, road_image = batch
         logging = self.logger is not None and batch_idx % self.hparams.output_img_freq == 0
         per_sample = tuple(road_image)
-        if (step_name == "train" and not logging and 0 < len(per_sample) <= 64 and
+        if (step_name == "train" and not logging and 0 < len(per_sample) <= ops.PTR_TABLE_MAX and
                 all(t.is_cuda and t.is_contiguous() and t.dtype in (torch.bool, torch.uint8) and t.numel() % 4 == 0 for t in per_sample)):
             # the training step only needs the masks inside the loss: the kernel reads them where the collate left them
             # (a pointer table) instead of torch.stack-ing them first (roadmap_bce_v2.py:87)

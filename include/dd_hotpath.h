@@ -286,7 +286,8 @@ int dd_bce_logits_u8(const float* logits, const unsigned char* target, float* lo
                      int64_t n, float grad_scale, void* workspace, void* stream);
 /* The same with the masks as the collate hands them over -- a tuple of per-sample bool tensors (helper.py:22-23), which the
  * reference stacks first (roadmap_bce_v2.py:87): target_ptrs is a HOST array of `batch` (<= 64) device pointers to
- * per_sample bytes each (per_sample % 4 == 0); logits / dlogits / probs are [batch * per_sample]. */
+ * per_sample bytes each (per_sample % 4 == 0); logits / dlogits / probs are [batch * per_sample].  More than 64 samples are
+ * refused: the caller stacks the masks and calls dd_bce_logits_u8, which gives the same bits (ops.BceWithLogitsProbs does). */
 int dd_bce_logits_u8_ptrs(const float* logits, const unsigned char* const* target_ptrs, int32_t batch, int64_t per_sample,
                           float* loss_out, float* dlogits, float* probs, float grad_scale, void* workspace, void* stream);
 /* x[0..n) *= *scalar (a DEVICE float), skipped entirely on the device when *scalar == 1: the upstream gradient of the scalar
@@ -544,7 +545,7 @@ int dd_bce_probs(const float* probs, const float* target, float* loss_out, float
 
 /* ---- skinny GEMMs of the dense head (K7): nn.Linear with the weight kept as [out=N, in=K] ------------
  * Replace F.linear / its autograd for DenseBlock.fc1 (components.py:105), Encoder.fc_z_out (components.py:51)
- * and the roadmap head (roadmap_bce_v2.py:75).  M = batch rows (<= 64), N and K multiples of 4.
+ * and the roadmap head (roadmap_bce_v2.py:75).  M = batch rows (fwd / dgrad run 64 rows per launch, any M), N and K multiples of 4.
  *   fwd   y[M,N]  = x[M,K] w[N,K]^T + bias[N]     (bias may be NULL)
  *   dgrad dx[M,K] = dy[M,N] w[N,K]
  *   wgrad dw[N,K] = dy[M,N]^T x[M,K];  dbias[N] = sum_m dy[m,:]   (dbias may be NULL)

@@ -8,6 +8,7 @@
 
 Also the seeded generators the GPU tests draw their boxes from.  Nothing here imports the package under test.
 """
+import functools
 import math
 
 import numpy as np
@@ -242,3 +243,43 @@ def ats_pair(rng, n_targets, n_exact, n_mid, n_off, n_stray):
         preds.append(rotated_rect(x, y, l, w, a))
     preds = np.array(preds).reshape(-1, 2, 4)
     return preds[rng.permutation(len(preds))], targets
+
+
+def ats_batch():
+    """130 (set 1, set 2, IoU matrix) samples from ats_pair for tests/test_gpu_batch_boundaries.py, under the rule of
+    tests/test_gpu_box_eval.py: a pair with an IoU within 1e-3 of a threshold is discarded and drawn again.
+    -> (cases, number generated)."""
+    rng = np.random.default_rng(6465)
+    cases, generated = [], 0
+    while len(cases) < 130:
+        generated += 1
+        s1, s2 = ats_pair(rng, int(rng.integers(1, 14)), int(rng.integers(0, 5)), int(rng.integers(0, 3)), int(rng.integers(0, 3)),
+                          int(rng.integers(0, 4)))
+        m = iou_matrix(s1, s2)
+        if threshold_margin(m) < 1e-3:
+            continue
+        cases.append((s1, s2, m))
+    return cases, generated
+
+
+EMPTY = np.zeros((0, 2, 4))
+
+
+@functools.lru_cache(maxsize=None)
+def ats_arrangements():
+    """Two placements of empty sets over the same 130 samples.  "edges": an empty side at samples 0, 63, 64 and 129.  "middle": every
+    sample of the second table (64-127) has an empty side, so that launch has no pair and the third must still start at the right
+    place of the flat IoU buffer."""
+    cases, generated = ats_batch()
+    out = {}
+    for name in ("edges", "middle"):
+        sets1, sets2 = [c[0] for c in cases], [c[1] for c in cases]
+        holes = {0: 1, 63: 2, 64: 1, 129: 2} if name == "edges" else {i: 1 + i % 2 for i in range(64, 128)}
+        for i, side in holes.items():
+            if side == 1:
+                sets1[i] = EMPTY
+            else:
+                sets2[i] = EMPTY
+        mats = [np.zeros((len(a), len(b))) if i in holes else cases[i][2] for i, (a, b) in enumerate(zip(sets1, sets2))]
+        out[name] = (sets1, sets2, mats)
+    return out, cases, generated

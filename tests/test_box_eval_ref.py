@@ -149,3 +149,19 @@ def test_box_metrics_flag_is_off_unless_asked_for():
                                                       {"val_loss": torch.tensor(3.0), "val_ats": torch.tensor(0.0), "val_ts": torch.tensor(0.4)}])
     assert set(full["log"]) == {"avg_val_loss", "avg_val_ats", "avg_val_ts"}
     assert float(full["log"]["avg_val_ats"]) == 0.25 and float(full["log"]["avg_val_ts"]) == pytest.approx(0.3)
+
+
+def test_ats_generator_of_the_130_sample_batches():
+    """The generator of tests/test_gpu_batch_boundaries.py alone (ref.ats_arrangements): at most 1 pair in 20 discarded, no kept IoU
+    within 1e-3 of a threshold, and the empty sets where the two arrangements say (samples 0, 63, 64, 129; every sample of 64-127)."""
+    arrangements, cases, generated = ref.ats_arrangements()
+    assert len(cases) == 130 and (generated - len(cases)) * 20 <= generated, f"{generated - len(cases)} of {generated} pairs discarded"
+    for _, _, m in cases:
+        assert ref.threshold_margin(m) >= 1e-3
+    assert len({(len(a), len(b)) for a, b, _ in cases}) > 20 and sum(m.size for _, _, m in cases) > 1000
+    s1, s2, mats = arrangements["edges"]
+    assert [i for i in range(130) if not mats[i].size] == [0, 63, 64, 129]
+    assert len(s1[0]) == 0 and len(s2[63]) == 0 and len(s1[64]) == 0 and len(s2[129]) == 0
+    s1, s2, mats = arrangements["middle"]
+    assert all(mats[i].size == 0 for i in range(64, 128)) and all(mats[i].size > 0 for i in list(range(64)) + [128, 129])
+    assert any(len(s1[i]) == 0 for i in range(64, 128)) and any(len(s2[i]) == 0 for i in range(64, 128))

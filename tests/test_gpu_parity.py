@@ -295,7 +295,14 @@ def test_dense_block_counts_batches(dev):
 
 @pytest.mark.parametrize("rows,feat,training,drop", [(3, 16, True, 0.0), (32, 128, True, 0.2), (5, 300, False, 0.2),
                                                      # wide layers (>= 65536 features): four / two features per thread (the decoder's DenseBlock)
-                                                     (32, 65540, True, 0.2), (7, 65536, False, 0.2), (32, 70002, True, 0.0)])
+                                                     (32, 65540, True, 0.2), (7, 65536, False, 0.2), (32, 70002, True, 0.0),
+                                                     # 33-64 rows: bn_relu_drop_{fwd,bwd}_kernel<64>; 65 and up: the generic <0>; train and eval, with
+                                                     # and without dropout; a wide layer on each (no multi-feature form past 32 rows)
+                                                     (33, 128, True, 0.2), (33, 300, False, 0.0), (48, 300, True, 0.0), (48, 16, False, 0.2),
+                                                     (64, 128, True, 0.2), (64, 300, False, 0.2), (65, 128, True, 0.2), (65, 300, False, 0.0),
+                                                     (100, 16, True, 0.2), (100, 300, False, 0.2), (130, 128, True, 0.0), (130, 300, True, 0.2),
+                                                     (130, 20, False, 0.2), (64, 65540, True, 0.2), (65, 65540, True, 0.2),
+                                                     (64, 65536, False, 0.2), (65, 65536, False, 0.0)])
 def test_bn_relu_dropout(dev, rows, feat, training, drop):
     from driving_dirty_amd import ops
     from oracle.ae_parts import FcBlock
@@ -326,7 +333,10 @@ def test_bn_relu_dropout(dev, rows, feat, training, drop):
 
 
 @pytest.mark.parametrize("m,n,k", [(3, 16, 704), (3, 8, 16), (32, 128, 128), (32, 64, 128), (5, 20, 8), (2, 1000, 64),
-                                   (32, 128, 18816), (33, 260, 72), (64, 36, 132), (4, 640000, 8)])
+                                   (32, 128, 18816), (33, 260, 72), (64, 36, 132), (4, 640000, 8),
+                                   # both sides of 64 rows: the forward and the data gradient run 64 rows per launch
+                                   (63, 128, 18816), (64, 128, 18816), (65, 128, 18816), (130, 128, 18816),
+                                   (63, 260, 72), (64, 260, 72), (65, 260, 72), (130, 260, 72), (65, 640000, 8)])
 def test_linear_fwd_dgrad_wgrad(dev, m, n, k):
     """Skinny GEMMs (split-K forward, split-N dgrad, register wgrad) vs fp64 torch."""
     from driving_dirty_amd import ops
@@ -354,7 +364,9 @@ def test_linear_refuses_unsupported(dev):
     with pytest.raises(_lib.HotpathError):
         ops.linear(torch.zeros(3, 6, device=dev), torch.zeros(8, 6, device=dev), None)      # K % 4 != 0
     with pytest.raises(_lib.HotpathError):
-        ops.linear(torch.zeros(65, 8, device=dev), torch.zeros(8, 8, device=dev), None)     # M > 64
+        ops.linear(torch.zeros(3, 8, device=dev), torch.zeros(6, 8, device=dev), None)      # N % 4 != 0
+    # more than 64 rows are no longer refused: they run 64 per launch (test_linear_fwd_dgrad_wgrad at 65 and 130 rows)
+    assert tuple(ops.linear(torch.zeros(65, 8, device=dev), torch.zeros(8, 8, device=dev), None).shape) == (65, 8)
 
 
 @pytest.mark.parametrize("n", [7, 4096, 2 * 640000 + 3])
