@@ -27,10 +27,9 @@
 
 namespace {
 
-// D(16x16) += A(16x4) B(4x16), exact fp32.  This file is compiled with -mllvm -amdgpu-mfma-vgpr-form (build.py): the accumulators stay in
+// DD_MFMA16 here: this file is compiled with -mllvm -amdgpu-mfma-vgpr-form (build.py): the accumulators stay in
 // ordinary vector registers -- left to the default the four accumulators go to the accumulation registers and are COPIED to vector
 // registers for the epilogue: 32 registers for 16, and the whole kernel has 72.
-__device__ __forceinline__ void mfma16(f32x4& acc, float a, float b) { acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
 
 struct RankbArgs {
   float* p;
@@ -47,14 +46,6 @@ struct RankbArgs {
   int total;               // ceil(ntile_n / 4) * ntile_k group-tiles
   float b1, b2, omb1, omb2, eps, step_size, inv_bc2, bc2_sqrt, gscale;
 };
-
-__device__ __forceinline__ f32x4 nt_load4(__amdgpu_buffer_rsrc_t r, int off, int soff) {      // streaming: nt
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, 2));
-}
-__device__ __forceinline__ void nt_store4(__amdgpu_buffer_rsrc_t r, int off, int soff, f32x4 v) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, soff, 2);
-}
 
 // ---- the LDS form: the shipped one ------------------------------------------------------------------------------------------------
 // Same tile, same order, same arithmetic; what changes is how often a wave waits for memory.  Beside the conv backward a round trip to
@@ -83,9 +74,9 @@ __device__ __forceinline__ void rankb_epilogue(const RankbArgs& a, int nt, int k
 #pragma unroll
     for (int j = 0; j < RG; ++j) {
       const int so = (i0 + j) * a.K * 4;
-      pa[j] = nt_load4(ps, off, so);
-      ma[j] = nt_load4(ms, off, so);
-      va[j] = nt_load4(vs, off, so);
+      pa[j] = dd_bload4<DD_AUX_NT>(ps, off, so);
+      ma[j] = dd_bload4<DD_AUX_NT>(ms, off, so);
+      va[j] = dd_bload4<DD_AUX_NT>(vs, off, so);
     }
 #pragma unroll
     for (int j = 0; j < RG; ++j) {
@@ -93,13 +84,13 @@ __device__ __forceinline__ void rankb_epilogue(const RankbArgs& a, int nt, int k
       const f32x4 g = {acc0[i], acc1[i], acc2[i], acc3[i]};
 #pragma unroll
       for (int cc = 0; cc < 4; cc += 2) {
-        f32x2a pe = {pa[j][cc], pa[j][cc + 1]}, me = {ma[j][cc], ma[j][cc + 1]}, ve = {va[j][cc], va[j][cc + 1]};
-        adam_elem2(pe, me, ve, f32x2a{g[cc], g[cc + 1]}, a.gscale, a.b1, a.b2, a.omb1, a.omb2, a.eps, a.step_size, a.inv_bc2);
+        f32x2 pe = {pa[j][cc], pa[j][cc + 1]}, me = {ma[j][cc], ma[j][cc + 1]}, ve = {va[j][cc], va[j][cc + 1]};
+        adam_elem2(pe, me, ve, f32x2{g[cc], g[cc + 1]}, a.gscale, a.b1, a.b2, a.omb1, a.omb2, a.eps, a.step_size, a.inv_bc2);
         pa[j][cc] = pe.x; pa[j][cc + 1] = pe.y; ma[j][cc] = me.x; ma[j][cc + 1] = me.y; va[j][cc] = ve.x; va[j][cc + 1] = ve.y;
       }
-      nt_store4(ps, off, so, pa[j]);
-      nt_store4(ms, off, so, ma[j]);
-      nt_store4(vs, off, so, va[j]);
+      dd_bstore<DD_AUX_NT>(ps, off, pa[j], so);
+      dd_bstore<DD_AUX_NT>(ms, off, ma[j], so);
+      dd_bstore<DD_AUX_NT>(vs, off, va[j], so);
     }
   }
 }
@@ -124,14 +115,14 @@ __device__ __forceinline__ void rankb_mfma_chunk(const float* yp, const float* x
   for (int s = 0; s < 2 * pairs; s += 2) {                // pair of LDS reads is issued under the first four MFMAs
     const float av0 = yp[s * 256], av1 = yp[s * 256 + 256];
     const f32x4 bv0 = *(const f32x4*)(xp + s * 4 * XS), bv1 = *(const f32x4*)(xp + (s + 1) * 4 * XS);
-    mfma16(acc0, av0, bv0.x);
-    mfma16(acc1, av0, bv0.y);
-    mfma16(acc2, av0, bv0.z);
-    mfma16(acc3, av0, bv0.w);
-    mfma16(acc0, av1, bv1.x);
-    mfma16(acc1, av1, bv1.y);
-    mfma16(acc2, av1, bv1.z);
-    mfma16(acc3, av1, bv1.w);
+    acc0 = DD_MFMA16(av0, bv0.x, acc0);
+    acc1 = DD_MFMA16(av0, bv0.y, acc1);
+    acc2 = DD_MFMA16(av0, bv0.z, acc2);
+    acc3 = DD_MFMA16(av0, bv0.w, acc3);
+    acc0 = DD_MFMA16(av1, bv1.x, acc0);
+    acc1 = DD_MFMA16(av1, bv1.y, acc1);
+    acc2 = DD_MFMA16(av1, bv1.z, acc2);
+    acc3 = DD_MFMA16(av1, bv1.w, acc3);
   }
 }
 

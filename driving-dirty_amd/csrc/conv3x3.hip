@@ -54,28 +54,6 @@ struct StripCfg {
   static constexpr int WFLOATS = KGROUPS * 64 * 4;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-typedef int i32x4s __attribute__((ext_vector_type(4)));
-// The same descriptor as rsrc() as four words (an inline-asm "s" operand): base, num_records = bytes, raw dword access.
-__device__ __forceinline__ i32x4s rsrc_words(const void* base, int bytes) {
-  const unsigned long a = (unsigned long)base;
-  return i32x4s{(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffff), bytes, 0x00020000};
-}
-__device__ __forceinline__ f32x4 bload4(__amdgpu_buffer_rsrc_t r, int off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 2));
-}
-__device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t r, int off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 2));
-}
-__device__ __forceinline__ float bload1s(__amdgpu_buffer_rsrc_t r, int off, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, soff, 0));
-}
-__device__ __forceinline__ void bstore1(__amdgpu_buffer_rsrc_t r, int off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, 2);
-}
-
 // XOR swizzle of the 16-byte chunk index inside a 128-byte pixel so that the ds_read_b128 of 16
 // consecutive pixels (one lane group) covers all 64 banks: pixels q and q+1 differ in address bit 7,
 // (q>>1)&7 spreads the other 8 pixel pairs over the 8 chunk positions.
@@ -90,14 +68,14 @@ __device__ __forceinline__ void load_row(const float* __restrict__ img, int H, i
                                          f32x4 (&r)[StripCfg<CIN, S>::NLOAD]) {
   using C = StripCfg<CIN, S>;
   const bool rowok = (iy >= 0) && (iy < H);
-  const __amdgpu_buffer_rsrc_t rs = rsrc(img + (long)(rowok ? iy : 0) * W * CIN, rowok ? W * C::PXB : 0);
+  const __amdgpu_buffer_rsrc_t rs = dd_rsrc(img + (long)(rowok ? iy : 0) * W * CIN, rowok ? W * C::PXB : 0);
 #pragma unroll
   for (int i = 0; i < C::NLOAD; ++i) {
     const int c = lane + 64 * i;
     const int q = c / C::CHUNKS, ch = c % C::CHUNKS;
     // a negative pixel index gives a huge unsigned offset: out of range -> zero, like the pixels right of the image
     const int off = (c < C::NCH) ? ((gx0 + q) * C::PXB + ch * 16) : -16;
-    r[i] = bload4(rs, off);
+    r[i] = dd_bload4<DD_AUX_NT>(rs, off);
   }
 }
 
@@ -110,13 +88,13 @@ __device__ __forceinline__ void load_row_img(const float* __restrict__ img, int 
   using C = StripCfg<CIN, S>;
   const bool rowok = (iy >= 0) && (iy < H);
   const int so = rowok ? iy * W * C::PXB : 0;
-  const __amdgpu_buffer_rsrc_t rs = rsrc(img, rowok ? so + W * C::PXB : 0);
+  const __amdgpu_buffer_rsrc_t rs = dd_rsrc(img, rowok ? so + W * C::PXB : 0);
 #pragma unroll
   for (int i = 0; i < C::NLOAD; ++i) {
     const int c = lane + 64 * i;
     const int q = c / C::CHUNKS, ch = c % C::CHUNKS;
     const int off = (c < C::NCH) ? ((gx0 + q) * C::PXB + ch * 16) : -16;
-    r[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, so, 2));
+    r[i] = dd_bload4<DD_AUX_NT>(rs, off, so);
   }
 }
 
@@ -159,13 +137,6 @@ __device__ __forceinline__ void store_row_aff(char* slot, char* spill, int lane,
   }
 }
 
-// The contiguous range of row tiles owned by global wave gw; idx = column * rows + row.
-__device__ __forceinline__ void wave_range(long total, int gw, int nw, long& idx, long& end) {
-  const long per = (total + nw - 1) / nw;
-  idx = (long)gw * per;
-  end = min(idx + per, total);
-}
-
 // ------------------------------------------------------------------------------------------------
 // forward / stride-1 dgrad
 // ------------------------------------------------------------------------------------------------
@@ -201,7 +172,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
   float st_sum = 0.f, st_sq = 0.f;
 
   long idx, end;
-  wave_range((long)B * nstrips * Ho, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * Ho, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / Ho;
     const int y0 = (int)(idx - col * Ho);
@@ -229,14 +200,14 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
       const long orow = ((long)(b * Ho + yy) * Wo) * 32;
       float mreg[16];
       if (EPI == DD_EPI_RELU_MASK || EPI == EPI_RELU_MASK_AFF) {
-        const __amdgpu_buffer_rsrc_t ms = rsrc(msk + orow, Wo * 128);
+        const __amdgpu_buffer_rsrc_t ms = dd_rsrc(msk + orow, Wo * 128);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mreg[r] = bload1(ms, ((x0 + dd_acc_row(r, lane)) * 32 + n) * 4);
+        for (int r = 0; r < 16; ++r) mreg[r] = dd_bload1<DD_AUX_NT>(ms, ((x0 + dd_acc_row(r, lane)) * 32 + n) * 4);
       }
       if (EPI == EPI_RELU_BITS) {   // one uint32 per pixel: 32x fewer mask bytes than the fp32 activation
-        const __amdgpu_buffer_rsrc_t ms = rsrc((const unsigned*)msk + (long)(b * Ho + yy) * Wo, Wo * 4);
+        const __amdgpu_buffer_rsrc_t ms = dd_rsrc((const unsigned*)msk + (long)(b * Ho + yy) * Wo, Wo * 4);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mreg[r] = bload1(ms, (x0 + dd_acc_row(r, lane)) * 4);
+        for (int r = 0; r < 16; ++r) mreg[r] = dd_bload1<DD_AUX_NT>(ms, (x0 + dd_acc_row(r, lane)) * 4);
       }
       // keep the loads ABOVE the MFMA chain: left alone, hipcc sinks them to their first use (the ring store
       // behind the chain) and the wave then eats a full HBM round trip per row
@@ -291,7 +262,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
 
       // epilogue: lane = output channel, register = pixel -> 128 contiguous bytes per pixel per store;
       // pixels right of the image fall outside the row descriptor and are dropped by the hardware
-      const __amdgpu_buffer_rsrc_t ys = rsrc(y + orow, Wo * 128);
+      const __amdgpu_buffer_rsrc_t ys = dd_rsrc(y + orow, Wo * 128);
       unsigned sign_word = 0;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -305,7 +276,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
         if (EPI == DD_EPI_RELU_MASK) v = (mreg[r] > 0.f) ? v : 0.f;
         if (EPI == EPI_RELU_MASK_AFF) v = (mreg[r] * msc + msh > 0.f) ? v : 0.f;
         if (EPI == EPI_RELU_BITS) v = ((__builtin_bit_cast(unsigned, mreg[r]) >> n) & 1u) ? v : 0.f;
-        bstore1(ys, ((x0 + dd_acc_row(r, lane)) * 32 + n) * 4, v);
+        dd_bstore1<DD_AUX_NT>(ys, ((x0 + dd_acc_row(r, lane)) * 32 + n) * 4, v);
         if (EPI == EPI_BIAS_RELU_BITS) {
           // lanes 0-31 hold the 32 channels of pixel i = (r&3)+8(r>>2), lanes 32-63 those of pixel i+4: one ballot =
           // two mask words.  Lane p (< 32) keeps the word of strip pixel p, so the row's 32 words leave as ONE store.
@@ -316,7 +287,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
         }
       }
       if (EPI == EPI_BIAS_RELU_BITS) {
-        const __amdgpu_buffer_rsrc_t bs = rsrc(bits_out + (long)(b * Ho + yy) * Wo, Wo * 4);
+        const __amdgpu_buffer_rsrc_t bs = dd_rsrc(bits_out + (long)(b * Ho + yy) * Wo, Wo * 4);
         __builtin_amdgcn_raw_buffer_store_b32(sign_word, bs, (h == 0) ? (x0 + n) * 4 : -16, 0, 0);
       }
     }
@@ -358,7 +329,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_s2_dgrad(const float* __restric
   const int h = lane >> 5, n = lane & 31;
 
   long idx, end;
-  wave_range((long)B * nstrips * nr, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * nr, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / nr;
     const int r0 = (int)(idx - col * nr);
@@ -392,15 +363,15 @@ __global__ __launch_bounds__(WPB * 64) void conv_s2_dgrad(const float* __restric
     const int obytes = (yi < H) ? W * 128 : 0;                                                  \
     float mreg[16];                                                                             \
     if (MASK == 1 || MASK == 3) {                                                               \
-      const __amdgpu_buffer_rsrc_t ms = rsrc(msk + orow, obytes);                               \
+      const __amdgpu_buffer_rsrc_t ms = dd_rsrc(msk + orow, obytes);                            \
       _Pragma("unroll") for (int rr = 0; rr < 16; ++rr)                                         \
-        mreg[rr] = bload1(ms, ((2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 32 + n) * 4);         \
+        mreg[rr] = dd_bload1<DD_AUX_NT>(ms, ((2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 32 + n) * 4); \
       __builtin_amdgcn_sched_barrier(0);                                                        \
     }                                                                                           \
     if (MASK == 2) {                                                                            \
-      const __amdgpu_buffer_rsrc_t ms = rsrc((const unsigned*)msk + (long)(b * H + min(yi, H - 1)) * W, obytes / 32); \
+      const __amdgpu_buffer_rsrc_t ms = dd_rsrc((const unsigned*)msk + (long)(b * H + min(yi, H - 1)) * W, obytes / 32); \
       _Pragma("unroll") for (int rr = 0; rr < 16; ++rr)                                         \
-        mreg[rr] = bload1(ms, (2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 4);                    \
+        mreg[rr] = dd_bload1<DD_AUX_NT>(ms, (2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 4);      \
       __builtin_amdgcn_sched_barrier(0);                                                        \
     }                                                                                           \
     f32x16 acc;                                                                                 \
@@ -419,13 +390,13 @@ __global__ __launch_bounds__(WPB * 64) void conv_s2_dgrad(const float* __restric
         acc = DD_MFMA(a.w, w.w, acc);                                                           \
       }                                                                                         \
     }                                                                                           \
-    const __amdgpu_buffer_rsrc_t os = rsrc(dx + orow, obytes);                                  \
+    const __amdgpu_buffer_rsrc_t os = dd_rsrc(dx + orow, obytes);                               \
     _Pragma("unroll") for (int rr = 0; rr < 16; ++rr) {                                         \
       float v = acc[rr];                                                                        \
       if (MASK == 1) v = (mreg[rr] > 0.f) ? v : 0.f;                                            \
       if (MASK == 3) v = (mreg[rr] * msc + msh > 0.f) ? v : 0.f;                                \
       if (MASK == 2) v = ((__builtin_bit_cast(unsigned, mreg[rr]) >> n) & 1u) ? v : 0.f;        \
-      bstore1(os, ((2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 32 + n) * 4, v);                  \
+      dd_bstore1<DD_AUX_NT>(os, ((2 * (s0 + dd_acc_row(rr, lane)) + (PX)) * 32 + n) * 4, v);    \
     }                                                                                           \
   }
       DD_TILE(1, 1, 4, {1, 1, 0}, {1, 0, 2}, {0, 1, 6}, {0, 0, 8})   // (ky,kx) = (0,0) (0,2) (2,0) (2,2)
@@ -477,7 +448,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wgrad(const float* __restrict__
   const int dy4 = tap4 / 3, dx4 = tap4 - 3 * dy4;
 
   long idx, end;
-  wave_range((long)B * nstrips * Ho, gw, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * Ho, gw, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / Ho;
     const int y0 = (int)(idx - col * Ho);
@@ -499,9 +470,9 @@ __global__ __launch_bounds__(WPB * 64) void conv_wgrad(const float* __restrict__
     }
     float areg[16];
     {
-      const __amdgpu_buffer_rsrc_t as = rsrc(dyb + (long)y0 * Wo * 32, Wo * 128);
+      const __amdgpu_buffer_rsrc_t as = dd_rsrc(dyb + (long)y0 * Wo * 32, Wo * 128);
 #pragma unroll
-      for (int pp = 0; pp < 16; ++pp) areg[pp] = bload1(as, aoff + pp * 256);
+      for (int pp = 0; pp < 16; ++pp) areg[pp] = dd_bload1<DD_AUX_NT>(as, aoff + pp * 256);
     }
 
     for (int yy = y0; yy < y1; ++yy) {
@@ -511,9 +482,9 @@ __global__ __launch_bounds__(WPB * 64) void conv_wgrad(const float* __restrict__
       float anext[16];
       {
         const bool ok = yy + 1 < Ho;
-        const __amdgpu_buffer_rsrc_t as = rsrc(dyb + (long)(ok ? yy + 1 : 0) * Wo * 32, ok ? Wo * 128 : 0);
+        const __amdgpu_buffer_rsrc_t as = dd_rsrc(dyb + (long)(ok ? yy + 1 : 0) * Wo * 32, ok ? Wo * 128 : 0);
 #pragma unroll
-        for (int pp = 0; pp < 16; ++pp) anext[pp] = bload1(as, aoff + pp * 256);
+        for (int pp = 0; pp < 16; ++pp) anext[pp] = dd_bload1<DD_AUX_NT>(as, aoff + pp * 256);
       }
       __builtin_amdgcn_sched_barrier(0);   // loads stay above the MFMA chains (see conv_strip_fwd)
 
@@ -647,35 +618,32 @@ __global__ void conv_pack_kernel(const float* __restrict__ w, float* __restrict_
 // never goes back to LDS; U (48 KB) sits in LDS next to the eight 3-slot rings (13.5 KB each): 159.7 of 160 KB.
 // Rest of the machinery (ring, prefetch, ranges, buffer addressing) is conv_strip_fwd's.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-#define DD_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 constexpr int WINO_UFLOATS = 3 * 4 * 2 * 2 * 64 * 4;      // [ky][pos][half][chunk][lane][4]
 
 // Packed fp32 add / subtract on 4-channel vectors: the fp32 matrix and vector instructions share the ALUs, so every VALU
 // instruction beside the MFMAs costs matrix time; v_pk_add_f32 does two lanes' worth per issue.  (hipcc selects it for
 // a 2-vector add but splits a subtract into scalars, hence the explicit form with the negate modifiers.)
-typedef float f32x2p __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2p pk_sub2(f32x2p a, f32x2p b) {
-  f32x2p r;
+__device__ __forceinline__ f32x2 pk_sub2(f32x2 a, f32x2 b) {
+  f32x2 r;
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ f32x2p pk_add2(f32x2p a, f32x2p b) {      // always packed (hipcc splits a 2-vector add whose operands are not register pairs yet)
-  f32x2p r;
+__device__ __forceinline__ f32x2 pk_add2(f32x2 a, f32x2 b) {      // always packed (hipcc splits a 2-vector add whose operands are not register pairs yet)
+  f32x2 r;
   asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
 __device__ __forceinline__ f32x4 pk_add4a(f32x4 a, f32x4 b) {
-  const f32x2p lo = pk_add2(f32x2p{a.x, a.y}, f32x2p{b.x, b.y}), hi = pk_add2(f32x2p{a.z, a.w}, f32x2p{b.z, b.w});
+  const f32x2 lo = pk_add2(f32x2{a.x, a.y}, f32x2{b.x, b.y}), hi = pk_add2(f32x2{a.z, a.w}, f32x2{b.z, b.w});
   return f32x4{lo.x, lo.y, hi.x, hi.y};
 }
 __device__ __forceinline__ f32x4 pk_add4(f32x4 a, f32x4 b) {
-  const f32x2p lo = f32x2p{a.x, a.y} + f32x2p{b.x, b.y}, hi = f32x2p{a.z, a.w} + f32x2p{b.z, b.w};
+  const f32x2 lo = f32x2{a.x, a.y} + f32x2{b.x, b.y}, hi = f32x2{a.z, a.w} + f32x2{b.z, b.w};
   return f32x4{lo.x, lo.y, hi.x, hi.y};
 }
 __device__ __forceinline__ f32x4 pk_sub4(f32x4 a, f32x4 b) {
-  f32x2p lo, hi;
-  const f32x2p alo = {a.x, a.y}, ahi = {a.z, a.w}, blo = {b.x, b.y}, bhi = {b.z, b.w};
+  f32x2 lo, hi;
+  const f32x2 alo = {a.x, a.y}, ahi = {a.z, a.w}, blo = {b.x, b.y}, bhi = {b.z, b.w};
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(lo) : "v"(alo), "v"(blo));
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(hi) : "v"(ahi), "v"(bhi));
   return f32x4{lo.x, lo.y, hi.x, hi.y};
@@ -704,7 +672,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_fwd(const float* __restric
   const float bv0 = (EPI == EPI_BIAS_RELU_BITS) ? bias[t16] : 0.f, bv1 = (EPI == EPI_BIAS_RELU_BITS) ? bias[16 + t16] : 0.f;
 
   long idx, end;
-  wave_range((long)B * nstrips * H, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * H, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / H;
     const int y0 = (int)(idx - col * H);
@@ -728,18 +696,18 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_fwd(const float* __restric
       const long opix = (long)(b * H + yy) * W;
       unsigned mw[8];
       if (EPI == EPI_RELU_BITS) {   // sign words of this lane's 8 output pixels: pairs 4q..4q+3 = pixels x0 + 8q .. +7
-        const __amdgpu_buffer_rsrc_t ms = rsrc(bits_in + opix, W * 4);
+        const __amdgpu_buffer_rsrc_t ms = dd_rsrc(bits_in + opix, W * 4);
 #pragma unroll
         for (int i = 0; i < 8; ++i)   // one dword each: every word is range-checked by itself at a ragged row end
           mw[i] = __builtin_amdgcn_raw_buffer_load_b32(ms, (x0 + 8 * q4 + i) * 4, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
 
-      f32x4v acc[4][2];
+      f32x4 acc[4][2];
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) acc[p][hf] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int hf = 0; hf < 2; ++hf) acc[p][hf] = f32x4{0.f, 0.f, 0.f, 0.f};
 
       // 6 groups (tap row ky, channel quad g) of 12 reads (4 input pixels + 8 U vectors) + 32 MFMAs; the reads of the
       // next group are issued before the MFMAs of the current one
@@ -789,7 +757,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_fwd(const float* __restric
       store_row<32, 1, true>(ring + ((yy + 3) % 3) * C::SLOTB, spill, lane, pre);
 
       // output transform + epilogue: lane = channel t16 (+16 per half), register r = pair 4q + r
-      const __amdgpu_buffer_rsrc_t ys = rsrc(y + opix * 32, W * 128);
+      const __amdgpu_buffer_rsrc_t ys = dd_rsrc(y + opix * 32, W * 128);
       unsigned keep[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) keep[i] = 0;
@@ -808,7 +776,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_fwd(const float* __restric
               v = ((mw[2 * r + e] >> (t16 + 16 * hf)) & 1u) ? v : 0.f;
             }
             o[hf] = v;
-            bstore1(ys, (opx * 32 + t16 + 16 * hf) * 4, v);
+            dd_bstore1<DD_AUX_NT>(ys, (opx * 32 + t16 + 16 * hf) * 4, v);
           }
           if (EPI == EPI_BIAS_RELU_BITS) {
             // ballot bit L = (o > 0) of lane L = (channel L&15, pair group L>>4): 16 channel bits of 4 different pixels
@@ -825,7 +793,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_fwd(const float* __restric
         unsigned word = keep[0];
 #pragma unroll
         for (int i = 1; i < 8; ++i) word = (sel == i) ? keep[i] : word;
-        const __amdgpu_buffer_rsrc_t bs = rsrc(bits_out + opix, W * 4);
+        const __amdgpu_buffer_rsrc_t bs = dd_rsrc(bits_out + opix, W * 4);
         __builtin_amdgcn_raw_buffer_store_b32(word, bs, (lane < 32) ? (x0 + P) * 4 : -16, 0, 0);
       }
     }
@@ -874,11 +842,11 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
   __syncthreads();
   char* xring = smem + W2_XBASE + wave * W2_XRINGB;
   char* xspill = xring + 4 * C4::SLOTB;
-  f32x4v wacc[2][2];      // [channel half][column half] of dW1, this wave's share
+  f32x4 wacc[2][2];      // [channel half][column half] of dW1, this wave's share
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-    for (int nh = 0; nh < 2; ++nh) wacc[hf][nh] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int nh = 0; nh < 2; ++nh) wacc[hf][nh] = f32x4{0.f, 0.f, 0.f, 0.f};
   char* ring = smem + WINO2_UFLOATS * 4 + wave * RINGB;
   char* spill = ring + 4 * C::SLOTB;
   const f32x4* ul = (const f32x4*)smem;
@@ -891,11 +859,11 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
     xlane[nh] = (8 * q4 + kx) * 16 + ci * 4;
   }
   const float bv0 = (EPI == EPI_BIAS_RELU_BITS) ? bias[t16] : 0.f, bv1 = (EPI == EPI_BIAS_RELU_BITS) ? bias[16 + t16] : 0.f;
-  const f32x4v bias0 = {bv0, bv0, bv0, bv0}, bias1 = {bv1, bv1, bv1, bv1};
+  const f32x4 bias0 = {bv0, bv0, bv0, bv0}, bias1 = {bv1, bv1, bv1, bv1};
   const int HT = (H + 1) / 2;                         // tile rows
 
   long idx, end;
-  wave_range((long)B * nstrips * HT, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * HT, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / HT;
     const int r0 = (int)(idx - col * HT);
@@ -982,13 +950,13 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
         for (int a = 0; a < 2; ++a) {
           const int oy = 2 * tr + a;
           const int mso = (oy < H) ? oy * W * 4 : 0;
-          const __amdgpu_buffer_rsrc_t ms = rsrc(bits_in + (long)b * H * W, (oy < H) ? mso + W * 4 : 0);
+          const __amdgpu_buffer_rsrc_t ms = dd_rsrc(bits_in + (long)b * H * W, (oy < H) ? mso + W * 4 : 0);
 #pragma unroll
           for (int i = 0; i < 8; ++i) mw[a][i] = __builtin_amdgcn_raw_buffer_load_b32(ms, (x0 + 8 * q4 + i) * 4, mso, 0);
         }
       }
 
-      f32x4v acc[16][2];
+      f32x4 acc[16][2];
 #pragma unroll
       for (int st = 0; st < 8; ++st) {
         const int g = st >> 2, u = st & 3;
@@ -1015,7 +983,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
         // ---- this stage's 32 MFMAs ----
         const f32x4(&vv)[4] = vq[st & 1];
         const f32x4(&uu)[4][2] = uq[st & 1];
-        const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1024,7 +992,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
             for (int hf = 0; hf < 2; ++hf) {
               // the first MFMA of an accumulator takes a literal zero (no register clears) -- or, at position (1,1), the
               // bias: A^T e11 A = all ones, so a constant in M[1][1] reaches all four outputs of the tile once
-              const f32x4v init = (EPI == EPI_BIAS_RELU_BITS && u == 1 && v == 1) ? (hf ? bias1 : bias0) : zero;
+              const f32x4 init = (EPI == EPI_BIAS_RELU_BITS && u == 1 && v == 1) ? (hf ? bias1 : bias0) : zero;
               acc[u * 4 + v][hf] = DD_MFMA16(vv[v][j], uu[v][hf][j], (g == 0 && j == 0) ? init : acc[u * 4 + v][hf]);
             }
         // interleave: one MFMA, then a few of the other instructions, 32 times
@@ -1048,7 +1016,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
       for (int a = 0; a < 2; ++a) {
         const int oy = 2 * tr + a;
         const long opix = (long)(b * H + min(oy, H - 1)) * W;
-        const __amdgpu_buffer_rsrc_t ys = rsrc(y + (W1 ? 0 : opix * 32), (!W1 && oy < H) ? W * 128 : 0);
+        const __amdgpu_buffer_rsrc_t ys = dd_rsrc(y + (W1 ? 0 : opix * 32), (!W1 && oy < H) ? W * 128 : 0);
         const char* xa[2];      // W1: this lane's patch element of output pixel (row a, tile 4q, e = 0): ring slot of image row oy + ky - 1
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh) {
@@ -1075,7 +1043,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
               // and / compare / select of `bit ? v : 0`)
               if (MASKED) v = __builtin_bit_cast(float, __builtin_bit_cast(int, v) & __builtin_amdgcn_sbfe((int)mw[a][2 * r + e], (unsigned)(t16 + 16 * hf), 1u));
               o[hf] = v;
-              if (!W1) bstore1(ys, (opx * 32 + t16 + 16 * hf) * 4, v);
+              if (!W1) dd_bstore1<DD_AUX_NT>(ys, (opx * 32 + t16 + 16 * hf) * 4, v);
             }
             if (W1) {
               const float b0 = *(const float*)(xa[0] + (2 * r + e) * 16), b1 = *(const float*)(xa[1] + (2 * r + e) * 16);
@@ -1096,7 +1064,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_fwd(const float* __restri
           unsigned word = keep[a][0];
 #pragma unroll
           for (int i = 1; i < 8; ++i) word = (sel == i) ? keep[a][i] : word;
-          const __amdgpu_buffer_rsrc_t bs = rsrc(bits_out + opix, (oy < H) ? W * 4 : 0);
+          const __amdgpu_buffer_rsrc_t bs = dd_rsrc(bits_out + opix, (oy < H) ? W * 4 : 0);
           __builtin_amdgcn_raw_buffer_store_b32(word, bs, (lane < 32) ? (x0 + P) * 4 : -16, 0, 0);
         }
       }
@@ -1161,11 +1129,11 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
   __syncthreads();
   char* xring = smem + W2_XBASE + wave * W2_XRINGB;      // W1: 4-row ring of the NHWC4 image, slot of row iy = (iy + 1) & 3
   char* xspill = xring + 4 * C4::SLOTB;
-  f32x4v wacc[2][2];
+  f32x4 wacc[2][2];
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-    for (int nh = 0; nh < 2; ++nh) wacc[hf][nh] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int nh = 0; nh < 2; ++nh) wacc[hf][nh] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int ulane = (int)(unsigned long)(__attribute__((address_space(3))) char*)smem + lane * 16;      // LDS byte address of U[..][lane]
   const int t16 = lane & 15, q4 = lane >> 4;
   int xky[2], xlane[2];
@@ -1176,23 +1144,23 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
     xlane[nh] = (8 * q4 + kx) * 16 + ci * 4;
   }
   const float bv0 = (EPI == EPI_BIAS_RELU_BITS) ? bias[t16] : 0.f, bv1 = (EPI == EPI_BIAS_RELU_BITS) ? bias[16 + t16] : 0.f;
-  const f32x4v bias0 = {bv0, bv0, bv0, bv0}, bias1 = {bv1, bv1, bv1, bv1};
+  const f32x4 bias0 = {bv0, bv0, bv0, bv0}, bias1 = {bv1, bv1, bv1, bv1};
   const int HT = (H + 1) / 2;
 
-  f32x4v accr[2][4][2];      // [position row u & 1][v][channel half]
+  f32x4 accr[2][4][2];      // [position row u & 1][v][channel half]
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int v = 0; v < 4; ++v)
 #pragma unroll
-      for (int hf = 0; hf < 2; ++hf) accr[i][v][hf] = f32x4v{0.f, 0.f, 0.f, 0.f};
-  f32x2p o1[2][2][2];        // [register pair][column e][channel half]: output row 2tr+1 on its way (z1 - z2 - z3)
+      for (int hf = 0; hf < 2; ++hf) accr[i][v][hf] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x2 o1[2][2][2];        // [register pair][column e][channel half]: output row 2tr+1 on its way (z1 - z2 - z3)
 #pragma unroll
-  for (int i = 0; i < 8; ++i) o1[i >> 2][(i >> 1) & 1][i & 1] = f32x2p{0.f, 0.f};
+  for (int i = 0; i < 8; ++i) o1[i >> 2][(i >> 1) & 1][i & 1] = f32x2{0.f, 0.f};
 
   float pfacc = 0.f;
   long idx, end;
-  wave_range((long)B * nstrips * HT, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * HT, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / HT;
     const int r0 = (int)(idx - col * HT);
@@ -1211,8 +1179,8 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
     const unsigned* bib = bits_in + (MASKED ? (long)b * H * W : 0);
     const int pitch = W * 128, pitchb = W * 4;
     constexpr int FAR = 1 << 30;      // beyond any image (the launcher checks H * W * 128 < 2^30), no wrap with a row offset on top
-    const __amdgpu_buffer_rsrc_t xrs = rsrc(xb, H * pitch), bors = rsrc(bob, H * pitchb), birs = rsrc(bib, H * pitchb);
-    const i32x4s yrs = rsrc_words(yb, W1 ? 0 : H * pitch);
+    const __amdgpu_buffer_rsrc_t xrs = dd_rsrc(xb, H * pitch), bors = dd_rsrc(bob, H * pitchb), birs = dd_rsrc(bib, H * pitchb);
+    const i32x4 yrs = dd_rsrc_words(yb, W1 ? 0 : H * pitch);
     const int gx0 = x0 - 1;
     int poff[4];      // byte offset of this lane's patch column c inside an input row (left / right of the image: out of range -> 0)
 #pragma unroll
@@ -1238,7 +1206,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
 #pragma unroll
       for (int g = 0; g < 2; ++g)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) R[g][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, poff[c] + g * 64, so, 0));
+        for (int c = 0; c < 4; ++c) R[g][c] = dd_bload4(xrs, poff[c] + g * 64, so);
     };
     auto xstage = [&](const f32x4 (&L)[2][4], f32x4 (&R)[2][4]) {      // landing registers -> row registers (or in place)
 #pragma unroll
@@ -1281,27 +1249,27 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
 #pragma unroll
       for (int i = 0; i < 8; ++i) m[i] = __builtin_amdgcn_raw_buffer_load_b32(birs, pmk[i], so, 0);
     };
-    auto acc_read2 = [&](float a0, float a1, f32x2p& d) {
+    auto acc_read2 = [&](float a0, float a1, f32x2& d) {
       float lo, hi;
       asm volatile("v_accvgpr_read_b32 %0, %2\n\tv_accvgpr_read_b32 %1, %3" : "=v"(lo), "=v"(hi) : "a"(a0), "a"(a1));
-      d = f32x2p{lo, hi};
+      d = f32x2{lo, hi};
     };
     // x-direction output transform of position row u (accumulators accr[u & 1]) and its term of the two y sums.  The reads are
     // pinned to the stage that calls this (volatile): left to itself the compiler puts each one right behind the MFMA that
     // finishes the accumulator, a stage earlier, and waits there for the result.
-    auto transform_row = [&](int u, f32x2p (&o0)[2][2][2]) {
+    auto transform_row = [&](int u, f32x2 (&o0)[2][2][2]) {
       asm volatile("s_nop 7\n\ts_nop 7");      // the last MFMA of accr[u & 1] is >= 11 wait states away (the compiler cannot count for us)
 #pragma unroll
       for (int rp = 0; rp < 2; ++rp)
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-          const f32x4v(&m)[4][2] = accr[u & 1];
-          f32x2p mm[4];
+          const f32x4(&m)[4][2] = accr[u & 1];
+          f32x2 mm[4];
 #pragma unroll
           for (int v = 0; v < 4; ++v) acc_read2(m[v][hf][2 * rp], m[v][hf][2 * rp + 1], mm[v]);
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
-            const f32x2p z = e == 0 ? pk_add2(pk_add2(mm[0], mm[1]), mm[2]) : pk_sub2(pk_sub2(mm[1], mm[2]), mm[3]);
+            const f32x2 z = e == 0 ? pk_add2(pk_add2(mm[0], mm[1]), mm[2]) : pk_sub2(pk_sub2(mm[1], mm[2]), mm[3]);
             if (u == 0) o0[rp][e][hf] = z;
             if (u == 1) { o0[rp][e][hf] = pk_add2(o0[rp][e][hf], z); o1[rp][e][hf] = z; }
             if (u == 2) { o0[rp][e][hf] = pk_add2(o0[rp][e][hf], z); o1[rp][e][hf] = pk_sub2(o1[rp][e][hf], z); }
@@ -1310,7 +1278,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
         }
     };
     // output row oy leaves: ReLU / mask, store, sign words, the c1 weight gradient's MFMAs
-    auto emit_row = [&](int oy, const f32x2p (&o)[2][2][2], const unsigned (&mw)[8], float (&pend)[16], int& yso) {
+    auto emit_row = [&](int oy, const f32x2 (&o)[2][2][2], const unsigned (&mw)[8], float (&pend)[16], int& yso) {
       yso = oy * pitch;
       const char* xa[2];
 #pragma unroll
@@ -1394,7 +1362,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
     // One tile-row.  A0 .. A3 = the register rows holding input rows 2tr-1 .. 2tr+2; A0 is refilled with row 2tr+3 and A1 with
     // row 2tr+4 (the next tile-row's r = 2, 3).  mp = sign words of the previous tile-row's second output row, mn = this one's.
     auto step = [&](int tr, f32x4 (&A0)[2][4], f32x4 (&A1)[2][4], f32x4 (&A2)[2][4], f32x4 (&A3)[2][4]) {
-      f32x2p o0[2][2][2];
+      f32x2 o0[2][2][2];
       unsigned m0w[8];
       float pend[16];      // the outputs of a row between the vector block that forms them and their stores
       int yso;
@@ -1413,7 +1381,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
           if (pf_rows) {
             pfacc += pfv[0] + pfv[1] + pfv[2] + pfv[3];      // the previous tile-row's (landed long ago; keeps them alive)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) pfv[q] = bload1s(xrs, pfoff + (q & 1) * 64, (2 * (tr + pf_rows) + 3 + (q >> 1)) * pitch);
+            for (int q = 0; q < 4; ++q) pfv[q] = dd_bload1(xrs, pfoff + (q & 1) * 64, (2 * (tr + pf_rows) + 3 + (q >> 1)) * pitch);
           }
           transform_row(0, o0);
           if (W1) {
@@ -1454,7 +1422,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
           for (int v = 0; v < 4; ++v)
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
-              f32x4v& acc = accr[u & 1][v][hf];
+              f32x4& acc = accr[u & 1][v][hf];
               if (g == 0 && j == 0) {
                 // the first MFMA of an accumulator takes a literal zero -- or, at position (1,1), the bias: A^T e11 A = all
                 // ones, so a constant in M[1][1] reaches all four outputs of the tile once
@@ -1483,7 +1451,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2r_fwd(const float* __restr
       if (++tr >= r1) break;
     }
     {      // the column's last output row
-      f32x2p unused[2][2][2];
+      f32x2 unused[2][2][2];
       float pend[16];
       int yso;
       transform_row(3, unused);
@@ -1597,7 +1565,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_wgrad(const float* __restr
   float bsum = 0.f;
 
   long idx, end;
-  wave_range((long)B * nstrips * H, gw, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * H, gw, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / H;
     const int y0 = (int)(idx - col * H);
@@ -1629,17 +1597,17 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_wgrad(const float* __restr
     auto issue_part = [&](int t, Group& f, int part) {       // part 0..7: dy pair s8 = part; parts 8..12: x chunks
       if (part < 8) {
         const bool ok = (t + 1 < y1);                        // dy rows past the range belong to the next wave: read zeros
-        const __amdgpu_buffer_rsrc_t as = rsrc(dyb + (long)(ok ? t + 1 : 0) * W * 32, ok ? W * 128 : 0);
-        f.d0[part] = bload1(as, aoff + part * 512);
-        f.d1[part] = bload1(as, aoff + part * 512 + 128);
+        const __amdgpu_buffer_rsrc_t as = dd_rsrc(dyb + (long)(ok ? t + 1 : 0) * W * 32, ok ? W * 128 : 0);
+        f.d0[part] = dd_bload1<DD_AUX_NT>(as, aoff + part * 512);
+        f.d1[part] = dd_bload1<DD_AUX_NT>(as, aoff + part * 512 + 128);
       } else {
         const int i = part - 8;
         const int iy = t + 2;
         const bool rowok = (iy >= 0) && (iy < H);
-        const __amdgpu_buffer_rsrc_t rs = rsrc(xb + (long)(rowok ? iy : 0) * W * 32, rowok ? W * 128 : 0);
+        const __amdgpu_buffer_rsrc_t rs = dd_rsrc(xb + (long)(rowok ? iy : 0) * W * 32, rowok ? W * 128 : 0);
         const int c = lane + 64 * i;
         const int q = c / C::CHUNKS, ch = c % C::CHUNKS;
-        f.xrow[i] = bload4(rs, (c < C::NCH) ? ((gx0 + q) * C::PXB + ch * 16) : -16);
+        f.xrow[i] = dd_bload4<DD_AUX_NT>(rs, (c < C::NCH) ? ((gx0 + q) * C::PXB + ch * 16) : -16);
       }
     };
     auto step = [&](int yy, const Group& prev, Group& cur, Group& nxt) {
@@ -1693,11 +1661,11 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino_wgrad(const float* __restr
     };
     Group ga, gb, gc;
     {   // dy row y0 (group y0-1's dy half) and group y0, synchronously enough: the loop waits for them where it uses them
-      const __amdgpu_buffer_rsrc_t as = rsrc(dyb + (long)y0 * W * 32, W * 128);
+      const __amdgpu_buffer_rsrc_t as = dd_rsrc(dyb + (long)y0 * W * 32, W * 128);
 #pragma unroll
       for (int s8 = 0; s8 < 8; ++s8) {
-        ga.d0[s8] = bload1(as, aoff + s8 * 512);
-        ga.d1[s8] = bload1(as, aoff + s8 * 512 + 128);
+        ga.d0[s8] = dd_bload1<DD_AUX_NT>(as, aoff + s8 * 512);
+        ga.d1[s8] = dd_bload1<DD_AUX_NT>(as, aoff + s8 * 512 + 128);
       }
 #pragma unroll
       for (int part = 0; part < 13; ++part) issue_part(y0, gb, part);
@@ -1753,7 +1721,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_wgrad(const float* __rest
   float bsum = 0.f;
 
   long idx, end;
-  wave_range((long)B * nstrips * HT, gw, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * HT, gw, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / HT;
     const int r0 = (int)(idx - col * HT);
@@ -1778,7 +1746,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_wgrad(const float* __rest
     auto row_loadq = [&](int iy, int q, f32x4& d) {      // chunk group q of input row iy
       const bool ok = (iy >= 0) && (iy < H);
       const int so = ok ? iy * pitch : 0;
-      d = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc(xb, ok ? so + pitch : 0), roff[q], so, 2));
+      d = dd_bload4<DD_AUX_NT>(dd_rsrc(xb, ok ? so + pitch : 0), roff[q], so);
     };
 
 #pragma unroll
@@ -1790,22 +1758,22 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_wgrad(const float* __rest
       store_row<32, 1, false>(ring + ((iy + 1) & 3) * C::SLOTB, spill, lane, t);
     }
     // dy rows 2tr, 2tr+1 of the strip: g[a][e][s]
-    auto load_dy1 = [&](int tr, int s8, f32x2p (&g)[2][8]) {      // g[e][s] = (row 2tr, row 2tr+1) of the tile's column e: tile s8's four
+    auto load_dy1 = [&](int tr, int s8, f32x2 (&g)[2][8]) {      // g[e][s] = (row 2tr, row 2tr+1) of the tile's column e: tile s8's four
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
         const int oy = 2 * tr + a;
         const bool ok = (tr < r1) && (oy < H);       // rows past the range belong to the next wave: read zeros
         const int so = ok ? oy * pitch : 0;
-        const __amdgpu_buffer_rsrc_t as = rsrc(dyb, ok ? so + pitch : 0);
-        g[0][s8][a] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(as, aoff + s8 * 512, so, 2));
-        g[1][s8][a] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(as, aoff + s8 * 512 + 128, so, 2));
+        const __amdgpu_buffer_rsrc_t as = dd_rsrc(dyb, ok ? so + pitch : 0);
+        g[0][s8][a] = dd_bload1<DD_AUX_NT>(as, aoff + s8 * 512, so);
+        g[1][s8][a] = dd_bload1<DD_AUX_NT>(as, aoff + s8 * 512 + 128, so);
       }
     };
-    f32x2p ga[2][8], gb[2][8];      // dy of the current / next tile-row, alternating (no register moves)
+    f32x2 ga[2][8], gb[2][8];      // dy of the current / next tile-row, alternating (no register moves)
 #pragma unroll
     for (int s8 = 0; s8 < 8; ++s8) load_dy1(r0, s8, ga);
 
-    auto step = [&](int tr, const f32x2p (&gc)[2][8], f32x2p (&gn)[2][8]) {
+    auto step = [&](int tr, const f32x2 (&gc)[2][8], f32x2 (&gn)[2][8]) {
       f32x4 pre[2][C::NLOAD];
 
       const char* rb[4];
@@ -1823,15 +1791,15 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_wgrad(const float* __rest
       auto tf = [&](int s8, const float (&d)[4][4], float (&av)[16], float (&bv)[16]) {
         // packed fp32 throughout (the vector ALUs are the matrix ALUs: every instruction here is matrix time lost).
         // x stage on register pairs (c0,c1) / (c2,c3) with a broadcast operand, y stage pairwise over c.
-        f32x2p wl[4], wh[4];
+        f32x2 wl[4], wh[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const f32x2p lo = {d[r][0], d[r][1]}, hi = {d[r][2], d[r][3]};
+          const f32x2 lo = {d[r][0], d[r][1]}, hi = {d[r][2], d[r][3]};
           asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(wl[r]) : "v"(lo), "v"(hi));                // d0 - d2, d1 + d2
           asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(wh[r]) : "v"(hi), "v"(lo));  // d2 - d1, d3 - d1
         }
-        const f32x2p bl[4] = {pk_sub2(wl[0], wl[2]), wl[1] + wl[2], pk_sub2(wl[2], wl[1]), pk_sub2(wl[3], wl[1])};
-        const f32x2p bh[4] = {pk_sub2(wh[0], wh[2]), wh[1] + wh[2], pk_sub2(wh[2], wh[1]), pk_sub2(wh[3], wh[1])};
+        const f32x2 bl[4] = {pk_sub2(wl[0], wl[2]), wl[1] + wl[2], pk_sub2(wl[2], wl[1]), pk_sub2(wl[3], wl[1])};
+        const f32x2 bh[4] = {pk_sub2(wh[0], wh[2]), wh[1] + wh[2], pk_sub2(wh[2], wh[1]), pk_sub2(wh[3], wh[1])};
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           bv[u * 4 + 0] = bl[u].x;
@@ -1841,11 +1809,11 @@ __global__ __launch_bounds__(WPB * 64) void conv_wino2_wgrad(const float* __rest
         }
         // dy tile (pairs over the tile's two rows), WITHOUT the halves of G = [[1,0],[.5,.5],[.5,-.5],[0,1]]: position
         // (u,v) carries the factor (1,2,2,1)[u] * (1,2,2,1)[v], taken out again (exactly) in conv_wino2_wgrad_reduce_b.
-        const f32x2p g0 = gc[0][s8], g1 = gc[1][s8];
-        const f32x2p gr[4] = {g0, g0 + g1, pk_sub2(g0, g1), g1};
+        const f32x2 g0 = gc[0][s8], g1 = gc[1][s8];
+        const f32x2 gr[4] = {g0, g0 + g1, pk_sub2(g0, g1), g1};
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          f32x2p sd;      // (row0 + row1, row0 - row1)
+          f32x2 sd;      // (row0 + row1, row0 - row1)
           asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(sd) : "v"(gr[v]));
           av[0 * 4 + v] = gr[v].x;
           av[1 * 4 + v] = sd.x;
@@ -2147,17 +2115,6 @@ __global__ void relu_bwd_kernel(const f32x4* __restrict__ dy, const f32x4* __res
   }
 }
 
-template <typename K>
-int allow_lds(K kernel, size_t bytes) {
-  static thread_local const void* done[48];
-  static thread_local int ndone = 0;
-  for (int i = 0; i < ndone; ++i)
-    if (done[i] == (const void*)kernel) return 0;
-  if (ndone < 48) done[ndone++] = (const void*)kernel;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return e == hipSuccess ? 0 : dd_fail(DD_ERR_LAUNCH, "hipFuncSetAttribute(%zu bytes LDS): %s", bytes, hipGetErrorString(e));
-}
-
 int check_desc(const dd_conv_desc* d) {
   DD_REQUIRE(d != nullptr, DD_ERR_BAD_ARG, "conv: NULL descriptor");
   DD_REQUIRE(d->batch > 0 && d->height > 0 && d->width > 0, DD_ERR_BAD_ARG, "conv: non-positive size");
@@ -2190,10 +2147,28 @@ int launch_fwd(const float* x, const float* wp, const float* bias, const float* 
   const int per_cu = (int)max((size_t)1, min((size_t)2, (size_t)(160 * 1024) / lds));
   const int grid = resident_grid(d, (long)d->batch * nstrips * Ho, WPB, per_cu);
   auto k = conv_strip_fwd<CIN, S, EPI, WPB, AFF>;
-  if (int rc = allow_lds(k, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)k, lds)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, x, wp, bias, msk, y, bits_out, d->batch, d->height, d->width,
                      Ho, Wo, nstrips, aff, stats);
   DD_LAUNCH_CHECK("conv_strip_fwd");
+  return 0;
+}
+
+// Data gradient of the stride-2 layer; MASK: 0 none, 1 fp32 ReLU source, 2 ReLU bits, 3 pre-BatchNorm tensor + affine.
+template <int MASK>
+int launch_s2_dgrad(const float* dy, const float* packed_dgrad, const float* relu_src, float* dx, const dd_conv_desc* d, hipStream_t st,
+                    const float* aff) {
+  using C = StripCfg<32, 1>;
+  constexpr int WPB = 8;
+  const int H = d->height, W = d->width, Ho = dd_conv_out(H, 2), Wo = dd_conv_out(W, 2);
+  const int ns = (W + 1) / 2, nr = (H + 1) / 2;
+  const int nstrips = (ns + 31) / 32;
+  const size_t lds = C::WFLOATS * 4 + (size_t)WPB * C::WAVEB;
+  const int grid = resident_grid(d, (long)d->batch * nstrips * nr, WPB, 1);
+  auto k = conv_s2_dgrad<WPB, MASK>;
+  if (int rc = dd_allow_lds((const void*)k, lds)) return rc;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, dy, packed_dgrad, relu_src, dx, d->batch, H, W, Ho, Wo, nstrips, aff);
+  DD_LAUNCH_CHECK("conv_s2_dgrad");
   return 0;
 }
 
@@ -2215,7 +2190,7 @@ int launch_wino2(const float* x, const float* up, const float* bias, const unsig
                      (EPI == EPI_RELU_BITS_W1 ? (size_t)WPB * (4 * C4::SLOTB + C4::SPILLB) + 128 : 0);
   const int grid = resident_grid(d, (long)d->batch * nstrips * ((d->height + 1) / 2), WPB, 1);
   if (nw_out) *nw_out = grid * WPB;
-  if (int rc = ring ? allow_lds(conv_wino2_fwd<EPI, WPB>, lds) : allow_lds(conv_wino2r_fwd<EPI, WPB>, lds)) return rc;
+  if (int rc = dd_allow_lds(ring ? (const void*)conv_wino2_fwd<EPI, WPB> : (const void*)conv_wino2r_fwd<EPI, WPB>, lds)) return rc;
   // rows of the next tile-row are pulled into L2 a tile-row ahead (in the step: forward 1.195 -> 1.163 ms against no prefetch)
   constexpr int pf_rows = 1;
   auto kring = conv_wino2_fwd<EPI, WPB>;
@@ -2235,7 +2210,7 @@ int launch_wino(const float* x, const float* up, const float* bias, const unsign
   const size_t lds = (size_t)WINO_UFLOATS * 4 + (size_t)WPB * C::WAVEB;
   const int grid = resident_grid(d, (long)d->batch * nstrips * d->height, WPB, 1);
   auto k = conv_wino_fwd<EPI, WPB>;
-  if (int rc = allow_lds(k, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)k, lds)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, x, up, bias, bits_in, y, bits_out, d->batch, d->height, d->width, nstrips);
   DD_LAUNCH_CHECK("conv_wino_fwd");
   return 0;
@@ -2327,36 +2302,12 @@ static int conv_dgrad_impl(const float* dy, const float* packed_dgrad, const flo
     return mask_mode ? launch_fwd<32, 1, DD_EPI_RELU_MASK, 8>(dy, packed_dgrad, nullptr, relu_src, dx, d, st)
                      : launch_fwd<32, 1, DD_EPI_NONE, 8>(dy, packed_dgrad, nullptr, nullptr, dx, d, st);
   }
-  using C = StripCfg<32, 1>;
-  constexpr int WPB = 8;
-  const int H = d->height, W = d->width, Ho = dd_conv_out(H, 2), Wo = dd_conv_out(W, 2);
-  const int ns = (W + 1) / 2, nr = (H + 1) / 2;
-  const int nstrips = (ns + 31) / 32;
-  const size_t lds = C::WFLOATS * 4 + (size_t)WPB * C::WAVEB;
-  const int grid = resident_grid(d, (long)d->batch * nstrips * nr, WPB, 1);
-  if (mask_mode == 3) {
-    auto k = conv_s2_dgrad<WPB, 3>;
-    if (int rc = allow_lds(k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, dy, packed_dgrad, relu_src, dx, d->batch, H, W, Ho, Wo,
-                       nstrips, aff);
-  } else if (mask_mode == 2) {
-    auto k = conv_s2_dgrad<WPB, 2>;
-    if (int rc = allow_lds(k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, dy, packed_dgrad, relu_src, dx, d->batch, H, W, Ho, Wo,
-                       nstrips, aff);
-  } else if (mask_mode == 1) {
-    auto k = conv_s2_dgrad<WPB, 1>;
-    if (int rc = allow_lds(k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, dy, packed_dgrad, relu_src, dx, d->batch, H, W, Ho, Wo,
-                       nstrips, aff);
-  } else {
-    auto k = conv_s2_dgrad<WPB, 0>;
-    if (int rc = allow_lds(k, lds)) return rc;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, dy, packed_dgrad, relu_src, dx, d->batch, H, W, Ho, Wo,
-                       nstrips, aff);
+  switch (mask_mode) {
+    case 3: return launch_s2_dgrad<3>(dy, packed_dgrad, relu_src, dx, d, st, aff);
+    case 2: return launch_s2_dgrad<2>(dy, packed_dgrad, relu_src, dx, d, st, aff);
+    case 1: return launch_s2_dgrad<1>(dy, packed_dgrad, relu_src, dx, d, st, aff);
+    default: return launch_s2_dgrad<0>(dy, packed_dgrad, relu_src, dx, d, st, aff);
   }
-  DD_LAUNCH_CHECK("conv_s2_dgrad");
-  return 0;
 }
 
 int64_t dd_conv_wgrad_workspace_bytes(const dd_conv_desc* d) {
@@ -2419,7 +2370,7 @@ static int conv_wgrad_impl(const float* x, const float* aff, const float* dy, fl
   {                                                                                                                 \
     auto k = conv_wgrad<CIN, SS, WPB, AFF>;                                                                         \
     const size_t lds = (size_t)WPB * StripCfg<CIN, SS>::WAVEB;                                                      \
-    if (int rc = allow_lds(k, lds)) return rc;                                                                      \
+    if (int rc = dd_allow_lds((const void*)k, lds)) return rc;                                                      \
     hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, x, dy, part, bpart, d->batch, H, W, Ho, Wo, nstrips, \
                        aff);                                                                                        \
   }
@@ -2577,7 +2528,7 @@ int dd_conv_wino2_wgrad_partials(const float* x, const float* dy, void* workspac
   float* bpart = part + (size_t)grid * 16 * 1024;
   auto k = conv_wino2_wgrad<WPB>;
   const size_t lds = max((size_t)WPB * (4 * StripCfg<32, 1>::SLOTB + StripCfg<32, 1>::SPILLB), (size_t)2 * W2W_STAGE4 * 16);
-  if (int rc = allow_lds(k, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)k, lds)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, (hipStream_t)stream, x, dy, part, bpart, d->batch, d->height, d->width, nstrips);
   DD_LAUNCH_CHECK("conv_wino2_wgrad");
   return 0;
@@ -2625,7 +2576,7 @@ int dd_conv_wino_wgrad(const float* x, const float* dy, float* dw_oihw, float* d
   float* bpart = part + (size_t)nw * 12 * 1024;
   auto k = conv_wino_wgrad<WPB>;
   const size_t lds = (size_t)WPB * StripCfg<32, 1>::WAVEB;
-  if (int rc = allow_lds(k, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)k, lds)) return rc;
   hipLaunchKernelGGL(k, dim3(grid), dim3(WPB * 64), lds, st, x, dy, part, bpart, d->batch, d->height, d->width, nstrips);
   DD_LAUNCH_CHECK("conv_wino_wgrad");
   hipLaunchKernelGGL(conv_wino_wgrad_reduce, dim3(49), dim3(1024), 0, st, part, bpart, dw_oihw, dbias, nw);

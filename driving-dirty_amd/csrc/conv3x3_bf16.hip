@@ -21,40 +21,13 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-
-#define BF_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {   // round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
 // Output streams carry the non-temporal hint (aux bit 1), as in conv3x3.hip; input streams carry it in the weight-gradient kernels only.
 // A/B/A/B on one box, bs 16, 512 x 3672 (tools/ab_libs.sh over tools/bench_bf16.py): stores -- c1 forward 0.69 -> 0.59 ms, c2 forward
 // 0.99 -> 0.87, c2 data gradient 0.89 -> 0.86; loads on top of that -- c3 / c1 / c2 weight gradient 0.43 -> 0.39, 0.44 -> 0.40, 0.79 -> 0.78,
 // but c1 forward 0.45 -> 0.51 (its 8-byte pixels are re-read by the neighbouring strips), the others unchanged.  Not on the pool forward's
 // stores: its 32-byte pieces want to be merged in the L2 first (0.21 -> 0.41 ms with the hint).
-constexpr int BF_NT = 2;
-template <int AUX = 0>
-__device__ __forceinline__ u32x4 bload4(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AUX); }
-template <int AUX = 0>
-__device__ __forceinline__ u32x2 bload2(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX); }
-__device__ __forceinline__ unsigned bload1(__amdgpu_buffer_rsrc_t r, int off) { return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0); }
+constexpr int BF_NT = DD_AUX_NT;
 constexpr int BF_ST = BF_NT;
-__device__ __forceinline__ void bstore2(__amdgpu_buffer_rsrc_t r, int off, u32x2 v) { __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, BF_ST); }
-__device__ __forceinline__ void bstore1(__amdgpu_buffer_rsrc_t r, int off, unsigned v) { __builtin_amdgcn_raw_buffer_store_b32(v, r, off, 0, BF_ST); }
 
 // LDS geometry of one wave.  CIN == 32: 64-byte pixels in 16-byte chunks of 8 channels; CIN == 4 (3 real channels):
 // 8-byte pixels, one "chunk" per pixel.
@@ -87,14 +60,14 @@ __device__ __forceinline__ void load_row(const unsigned short* __restrict__ img,
                                          typename RowRegs<CIN>::T (&r)[BCfg<CIN, S>::NLOAD]) {
   using C = BCfg<CIN, S>;
   const bool rowok = (iy >= 0) && (iy < H);
-  const __amdgpu_buffer_rsrc_t rs = rsrc(img + (long)(rowok ? iy : 0) * W * CIN, rowok ? W * C::PXB : 0);
+  const __amdgpu_buffer_rsrc_t rs = dd_rsrc(img + (long)(rowok ? iy : 0) * W * CIN, rowok ? W * C::PXB : 0);
 #pragma unroll
   for (int i = 0; i < C::NLOAD; ++i) {
     const int c = lane + 64 * i;
     const int q = c / C::CHUNKS, ch = c % C::CHUNKS;
     const int off = (c < C::NCH) ? ((gx0 + q) * C::PXB + ch * C::CHB) : -16;      // negative pixel -> huge offset -> zeros
-    if constexpr (CIN == 32) r[i] = bload4<AUX>(rs, off);
-    else r[i] = bload2<AUX>(rs, off);
+    if constexpr (CIN == 32) r[i] = dd_bload<u32x4, AUX>(rs, off);
+    else r[i] = dd_bload<u32x2, AUX>(rs, off);
   }
 }
 
@@ -111,14 +84,6 @@ __device__ __forceinline__ void store_row(char* slot, char* spill, int lane, con
   }
 }
 
-__device__ __forceinline__ void wave_range(long total, int gw, int nw, long& idx, long& end) {
-  const long per = (total + nw - 1) / nw;
-  idx = (long)gw * per;
-  end = min(idx + per, total);
-}
-
-__device__ __forceinline__ int chan_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // accumulator row -> channel
-
 // Output staging.  The accumulator holds 16 channels of ONE pixel per lane; written straight to HBM that is 8-byte
 // pieces scattered at a 64-byte pitch (4 partial requests per pixel -- measured: the store path, not HBM, then bounds
 // the kernel).  Instead the tile goes through a per-wave LDS image (64-byte pixels, 16-byte chunks XOR-swizzled so
@@ -131,8 +96,8 @@ __device__ __forceinline__ void stage_pixel16(char* tile, int pix, int h, const 
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     u32x2 w;
-    w.x = pack_bf16(v[4 * g], v[4 * g + 1]);
-    w.y = pack_bf16(v[4 * g + 2], v[4 * g + 3]);
+    w.x = dd_pack_bf16(v[4 * g], v[4 * g + 1]);
+    w.y = dd_pack_bf16(v[4 * g + 2], v[4 * g + 3]);
     *(u32x2*)(tile + pix * 64 + ((g ^ sw) << 4) + h * 8) = w;
   }
 }
@@ -145,7 +110,7 @@ __device__ __forceinline__ void flush_tile(const char* tile, __amdgpu_buffer_rsr
     const int c = 64 * k + lane;
     const int pix = c >> 2, q = c & 3;
     const u32x4 v = *(const u32x4*)(tile + pix * 64 + ((q ^ stage_swz(pix)) << 4));
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, base_off + c * 16, 0, BF_ST);
+    dd_bstore<BF_ST>(rs, base_off + c * 16, v);
   }
 }
 
@@ -193,7 +158,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
   for (int i = 0; i < C::NW; ++i) wreg[i] = wp[i * 64 + lane];
 
   long idx, end;
-  wave_range((long)B * nstrips * Ho, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * Ho, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / Ho;
     const int y0 = (int)(idx - col * Ho);
@@ -213,8 +178,8 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
       for (int s2 = 0; s2 < S; ++s2) load_row<CIN, S>(xb, H, W, S * t + 2 + s2, gx0, lane, f.rows[s2]);
       if (EPI == 1) {
         const bool ok = t < y1;
-        const __amdgpu_buffer_rsrc_t ms = rsrc(bits_in + (long)(b * Ho + (ok ? t : 0)) * Wo, ok ? Wo * 4 : 0);
-        f.mword = bload1(ms, (x0 + n) * 4);
+        const __amdgpu_buffer_rsrc_t ms = dd_rsrc(bits_in + (long)(b * Ho + (ok ? t : 0)) * Wo, ok ? Wo * 4 : 0);
+        f.mword = dd_bload<unsigned>(ms, (x0 + n) * 4);
       }
     };
     // one output row: compute from the ring, retire `cur` (rows for the next output row), write row t
@@ -251,8 +216,8 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
         for (int tap = 0; tap < 9; ++tap) {
           if (tap + 3 < 9) rd(tap + 3);
           __builtin_amdgcn_sched_barrier(0);
-          acc = BF_MFMA(wreg[tap * 2], op[tap][0], acc);
-          acc = BF_MFMA(wreg[tap * 2 + 1], op[tap][1], acc);
+          acc = DD_MFMA_BF16(wreg[tap * 2], op[tap][0], acc);
+          acc = DD_MFMA_BF16(wreg[tap * 2 + 1], op[tap][1], acc);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {   // k16 step = the 4 channels of pixels n + 2h, n + 2h + 1 (dx = 2h, 2h+1; dx = 3 has zero weights)
@@ -266,7 +231,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
           op[dy] = __builtin_bit_cast(bf16x8, v);
         }
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy) acc = BF_MFMA(wreg[dy], op[dy], acc);
+        for (int dy = 0; dy < 3; ++dy) acc = DD_MFMA_BF16(wreg[dy], op[dy], acc);
       }
 
       // retire the rows output row t+1 needs into the ring slots row t no longer uses
@@ -282,16 +247,16 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
       const bool live = t < y1;                 // the second half of the last pair may be a dummy row: stores dropped
 #endif
       const long opix = (long)(b * Ho + (live ? t : 0)) * Wo;
-      const __amdgpu_buffer_rsrc_t ys = rsrc(y + opix * 32, live ? Wo * 64 : 0);
+      const __amdgpu_buffer_rsrc_t ys = dd_rsrc(y + opix * 32, live ? Wo * 64 : 0);
       float v[16];
       unsigned mine = 0;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (EPI == 0) {
           v[r] = fmaxf(acc[r], 0.f);
-          mine |= (v[r] > 0.f ? 1u : 0u) << chan_of(r, h);
+          mine |= (v[r] > 0.f ? 1u : 0u) << dd_acc_row_half(r, h);
         } else {
-          v[r] = ((cur.mword >> chan_of(r, h)) & 1u) ? acc[r] : 0.f;
+          v[r] = ((cur.mword >> dd_acc_row_half(r, h)) & 1u) ? acc[r] : 0.f;
         }
       }
       stage_pixel16(tile, n, h, v);
@@ -303,8 +268,8 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
 #else
         const bool want = live && bits_out != nullptr;
 #endif
-        const __amdgpu_buffer_rsrc_t bs = rsrc(want ? bits_out + opix : (unsigned*)y, want ? Wo * 4 : 0);
-        bstore1(bs, (h == 0) ? (x0 + n) * 4 : -16, word);
+        const __amdgpu_buffer_rsrc_t bs = dd_rsrc(want ? bits_out + opix : (unsigned*)y, want ? Wo * 4 : 0);
+        dd_bstore<BF_ST>(bs, (h == 0) ? (x0 + n) * 4 : -16, word);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -322,11 +287,11 @@ __global__ __launch_bounds__(WPB * 64) void bf_strip_fwd(const unsigned short* _
     asm volatile("" ::: "memory");            // keep the loads in front of the mirror stores at IR level too
     __builtin_amdgcn_sched_barrier(0);
     {   // mirror the loop body's stores so that the loop header sees the same queue from both predecessors
-      const __amdgpu_buffer_rsrc_t none = rsrc(y, 0);
+      const __amdgpu_buffer_rsrc_t none = dd_rsrc(y, 0);
       const u32x4 z = {0u, 0u, 0u, 0u};
-      __builtin_amdgcn_raw_buffer_store_b128(z, none, lane * 16, 0, BF_ST);          // distinct offsets: two stores, not one
-      __builtin_amdgcn_raw_buffer_store_b128(z, none, 1024 + lane * 16, 0, BF_ST);
-      if (EPI == 0) bstore1(none, lane * 4, 0u);
+      dd_bstore<BF_ST>(none, lane * 16, z);          // distinct offsets: two stores, not one
+      dd_bstore<BF_ST>(none, 1024 + lane * 16, z);
+      if (EPI == 0) dd_bstore<BF_ST>(none, lane * 4, 0u);
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
@@ -363,7 +328,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_s2_dgrad(const unsigned short* __
   for (int i = 0; i < 18; ++i) wreg[i] = wp[i * 64 + lane];
 
   long idx, end;
-  wave_range((long)B * nstrips * nr, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * nr, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / nr;
     const int r0 = (int)(idx - col * nr);
@@ -387,9 +352,9 @@ __global__ __launch_bounds__(WPB * 64) void bf_s2_dgrad(const unsigned short* __
 #pragma unroll
       for (int py = 0; py < 2; ++py) {
         const int yi = 2 * r + py;
-        const __amdgpu_buffer_rsrc_t ms = rsrc(bits_in + (long)(b * H + min(yi, H - 1)) * W, (yi < H) ? W * 4 : 0);
-        mw[py][0] = bload1(ms, (2 * (s0 + n)) * 4);
-        mw[py][1] = bload1(ms, (2 * (s0 + n) + 1) * 4);
+        const __amdgpu_buffer_rsrc_t ms = dd_rsrc(bits_in + (long)(b * H + min(yi, H - 1)) * W, (yi < H) ? W * 4 : 0);
+        mw[py][0] = dd_bload<unsigned>(ms, (2 * (s0 + n)) * 4);
+        mw[py][1] = dd_bload<unsigned>(ms, (2 * (s0 + n) + 1) * 4);
       }
       __builtin_amdgcn_sched_barrier(0);
 
@@ -407,18 +372,18 @@ __global__ __launch_bounds__(WPB * 64) void bf_s2_dgrad(const unsigned short* __
       const int sw = swz(q);                                                                           \
       _Pragma("unroll") for (int m = 0; m < 2; ++m) {                                                  \
         const bf16x8 px = __builtin_bit_cast(bf16x8, *(const u32x4*)(pa + (((2 * m + h) ^ sw) << 4))); \
-        acc = BF_MFMA(wreg[taps[t][2] * 2 + m], px, acc);                                              \
+        acc = DD_MFMA_BF16(wreg[taps[t][2] * 2 + m], px, acc);                                         \
       }                                                                                                \
     }                                                                                                  \
     float v[16];                                                                                       \
     _Pragma("unroll") for (int rr = 0; rr < 16; ++rr)                                                  \
-      v[rr] = ((mw[PY][PX] >> chan_of(rr, h)) & 1u) ? acc[rr] : 0.f;                                   \
+      v[rr] = ((mw[PY][PX] >> dd_acc_row_half(rr, h)) & 1u) ? acc[rr] : 0.f;                           \
     stage_pixel16(tile, 2 * n + (PX), h, v);                                                           \
   }
 #define BF_FLUSH(PY)                                                                                   \
   {                                                                                                    \
     const int yi = 2 * r + (PY);                                                                       \
-    const __amdgpu_buffer_rsrc_t os = rsrc(dx + ((long)(b * H + min(yi, H - 1)) * W) * 32, (yi < H) ? W * 64 : 0); \
+    const __amdgpu_buffer_rsrc_t os = dd_rsrc(dx + ((long)(b * H + min(yi, H - 1)) * W) * 32, (yi < H) ? W * 64 : 0); \
     flush_tile<64>(tile, os, 2 * s0 * 64, lane);                                                       \
   }
       BF_TILE(1, 1, 4, {1, 1, 0}, {1, 0, 2}, {0, 1, 6}, {0, 0, 8})
@@ -438,13 +403,6 @@ __global__ __launch_bounds__(WPB * 64) void bf_s2_dgrad(const unsigned short* __
 // weight / bias gradient: D[ci][co] += sum over pixels of x[pixel + tap][ci] * dy[pixel][co], one accumulator per
 // tap; both operands come out of row-major LDS images through the transpose read.
 // ------------------------------------------------------------------------------------------------
-// transpose read: per 16-lane group a block of 4 rows x 16 consecutive bf16; lane 4q+p of the group supplies the
-// address of row q, elements 4p..4p+3; lane e receives element e of the four rows.
-__device__ __forceinline__ s16x4 tr_read(const char* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)p); }
-__device__ __forceinline__ bf16x8 join(s16x4 a, s16x4 b) {
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 template <int CIN, int S>
 struct WCfg {
   using C = BCfg<CIN, S>;
@@ -485,7 +443,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
   float bsum = 0.f;
 
   long idx, end;
-  wave_range((long)B * nstrips * Ho, gw, gridDim.x * WPB, idx, end);
+  dd_range((long)B * nstrips * Ho, gw, gridDim.x * WPB, idx, end);
   while (idx < end) {
     const long col = idx / Ho;
     const int y0 = (int)(idx - col * Ho);
@@ -506,9 +464,9 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
     }
     u32x4 dcur[2];
     {
-      const __amdgpu_buffer_rsrc_t ds = rsrc(dyb + (long)y0 * Wo * 32, Wo * 64);
-      dcur[0] = bload4<BF_NT>(ds, doff);
-      dcur[1] = bload4<BF_NT>(ds, doff + 1024);
+      const __amdgpu_buffer_rsrc_t ds = dd_rsrc(dyb + (long)y0 * Wo * 32, Wo * 64);
+      dcur[0] = dd_bload<u32x4, BF_NT>(ds, doff);
+      dcur[1] = dd_bload<u32x4, BF_NT>(ds, doff + 1024);
     }
 
     for (int yy = y0; yy < y1; ++yy) {
@@ -518,9 +476,9 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
       u32x4 dnext[2];
       {
         const bool ok = yy + 1 < Ho;
-        const __amdgpu_buffer_rsrc_t ds = rsrc(dyb + (long)(ok ? yy + 1 : 0) * Wo * 32, ok ? Wo * 64 : 0);
-        dnext[0] = bload4<BF_NT>(ds, doff);
-        dnext[1] = bload4<BF_NT>(ds, doff + 1024);
+        const __amdgpu_buffer_rsrc_t ds = dd_rsrc(dyb + (long)(ok ? yy + 1 : 0) * Wo * 32, ok ? Wo * 64 : 0);
+        dnext[0] = dd_bload<u32x4, BF_NT>(ds, doff);
+        dnext[1] = dd_bload<u32x4, BF_NT>(ds, doff + 1024);
       }
       __builtin_amdgcn_sched_barrier(0);
 
@@ -530,10 +488,10 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
       bf16x8 bm[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
-        const s16x4 lo = tr_read(dys + dy_lane + (16 * m) * 64), hi = tr_read(dys + dy_lane + (16 * m + 4) * 64);
-        bm[m] = join(lo, hi);
+        const s16x4 lo = dd_tr_read(dys + dy_lane + (16 * m) * 64), hi = dd_tr_read(dys + dy_lane + (16 * m + 4) * 64);
+        bm[m] = dd_join(lo, hi);
         const u32x4 raw = __builtin_bit_cast(u32x4, bm[m]);    // bias gradient: this lane's 8 pixels of channel lane&31
-        bsum += (bf_lo(raw.x) + bf_hi(raw.x)) + (bf_lo(raw.y) + bf_hi(raw.y)) + (bf_lo(raw.z) + bf_hi(raw.z)) + (bf_lo(raw.w) + bf_hi(raw.w));
+        bsum += (dd_bf16_lo(raw.x) + dd_bf16_hi(raw.x)) + (dd_bf16_lo(raw.y) + dd_bf16_hi(raw.y)) + (dd_bf16_lo(raw.z) + dd_bf16_hi(raw.z)) + (dd_bf16_lo(raw.w) + dd_bf16_hi(raw.w));
       }
 
       if constexpr (CIN == 32) {
@@ -546,8 +504,8 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
         auto rd = [&](int it) {
           const int tap = it >> 1, m = it & 1;
           const char* pa = rowb[tap / 3] + (S * 16 * m + tap % 3) * 64;
-          lo[it % (AH + 1)] = tr_read(pa);
-          hi[it % (AH + 1)] = tr_read(pa + S * 4 * 64);
+          lo[it % (AH + 1)] = dd_tr_read(pa);
+          hi[it % (AH + 1)] = dd_tr_read(pa + S * 4 * 64);
         };
 #pragma unroll
         for (int it = 0; it < AH; ++it) rd(it);
@@ -555,7 +513,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
         for (int it = 0; it < 18; ++it) {
           if (it + AH < 18) rd(it + AH);
           __builtin_amdgcn_sched_barrier(0);
-          acc[it >> 1] = BF_MFMA(join(lo[it % (AH + 1)], hi[it % (AH + 1)]), bm[it & 1], acc[it >> 1]);
+          acc[it >> 1] = DD_MFMA_BF16(dd_join(lo[it % (AH + 1)], hi[it % (AH + 1)]), bm[it & 1], acc[it >> 1]);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -565,8 +523,8 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
         const char* rk2 = ring + ((yy + 2) % 3) * C::SLOTB + x_lane;
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-          acc[0] = BF_MFMA(join(tr_read(rk0 + (16 * m) * 8), tr_read(rk0 + (16 * m + 4) * 8)), bm[m], acc[0]);
-          acc[1] = BF_MFMA(join(tr_read(rk2 + (16 * m) * 8), tr_read(rk2 + (16 * m + 4) * 8)), bm[m], acc[1]);
+          acc[0] = DD_MFMA_BF16(dd_join(dd_tr_read(rk0 + (16 * m) * 8), dd_tr_read(rk0 + (16 * m + 4) * 8)), bm[m], acc[0]);
+          acc[1] = DD_MFMA_BF16(dd_join(dd_tr_read(rk2 + (16 * m) * 8), dd_tr_read(rk2 + (16 * m + 4) * 8)), bm[m], acc[1]);
         }
       }
 
@@ -588,7 +546,7 @@ __global__ __launch_bounds__(WPB * 64) void bf_wgrad(const unsigned short* __res
 }
 
 // Second stage (deterministic): per (accumulator, register) row of 64 lanes, sum the waves' partials in a fixed order
-// and scatter to OIHW.  D[i][j]: lane = j = co, register r -> i = chan_of(r, lane>>5).
+// and scatter to OIHW.  D[i][j]: lane = j = co, register r -> i = dd_acc_row(r, lane).
 template <int CIN>
 __global__ __launch_bounds__(1024) void bf_wgrad_reduce(const float* __restrict__ part, const float* __restrict__ bpart,
                                                         float* __restrict__ dw, float* __restrict__ db, int nw) {
@@ -617,7 +575,7 @@ __global__ __launch_bounds__(1024) void bf_wgrad_reduce(const float* __restrict_
   for (int i = 0; i < G; ++i) s += red[i][l];
   if (row < NT * 16) {
     const int t = row >> 4, r = row & 15;
-    const int i = chan_of(r, l >> 5), co = l & 31;
+    const int i = dd_acc_row_half(r, l >> 5), co = l & 31;
     if (CIN == 32) {
       dw[((long)co * 32 + i) * 9 + t] = s;
     } else {
@@ -655,7 +613,7 @@ __global__ void bf_pack_kernel(const float* __restrict__ w, unsigned short* __re
     const int co = lane & 31, kx = 2 * (lane >> 5) + (j >> 2), c = j & 3;
     v = (kx < 3 && c < 3) ? w[((long)co * 3 + c) * 9 + ky * 3 + kx] : 0.f;
   }
-  p[idx] = (unsigned short)(pack_bf16(v, 0.f) & 0xffffu);
+  p[idx] = (unsigned short)(dd_pack_bf16(v, 0.f) & 0xffffu);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -685,8 +643,8 @@ __global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restri
     const int slot = xw / W, xx = xw - slot * W;
     const float* src = views + (((long)b * 6 + kViewOrderBf[slot]) * 3) * plane + (long)yy * W + xx;
     u32x2 o;
-    o.x = pack_bf16(src[0], src[plane]);
-    o.y = pack_bf16(src[2 * plane], 0.f);
+    o.x = dd_pack_bf16(src[0], src[plane]);
+    o.y = dd_pack_bf16(src[2 * plane], 0.f);
     if (slot == mask_slot) {
       bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
       o.x = 0u; o.y = 0u;
@@ -710,8 +668,8 @@ __global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePt
     const int slot = xw / W, xx = xw - slot * W;
     const float* src = samples.p[b] + ((long)kViewOrderBf[slot] * 3) * plane + (long)yy * W + xx;
     u32x2 o;
-    o.x = pack_bf16(src[0], src[plane]);
-    o.y = pack_bf16(src[2 * plane], 0.f);
+    o.x = dd_pack_bf16(src[0], src[plane]);
+    o.y = dd_pack_bf16(src[2 * plane], 0.f);
     if (slot == mask_slot) {
       bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
       o.x = 0u; o.y = 0u;
@@ -737,8 +695,8 @@ __global__ __launch_bounds__(256) void stitch6_bf16_u8_ptrs_kernel(const BfSampl
     const unsigned char* src = samples.p[b] + (((long)kViewOrderBf[slot] * H + yy) * W + xx) * 3;
     const float c0 = (float)src[0] / 255.0f, c1 = (float)src[1] / 255.0f, c2 = (float)src[2] / 255.0f;
     u32x2 o;
-    o.x = pack_bf16(c0, c1);
-    o.y = pack_bf16(c2, 0.f);
+    o.x = dd_pack_bf16(c0, c1);
+    o.y = dd_pack_bf16(c2, 0.f);
     if (slot == mask_slot) {
       bf_stitch_target(target, b, yy, xx, H, W, c0, c1, c2);
       o.x = 0u; o.y = 0u;
@@ -762,7 +720,7 @@ __global__ __launch_bounds__(256) void pool4_bf16_fwd(const u32x2* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const u32x2 v = __builtin_nontemporal_load(src + (long)k * groups);
-      const float f[4] = {bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y)};
+      const float f[4] = {dd_bf16_lo(v.x), dd_bf16_hi(v.x), dd_bf16_lo(v.y), dd_bf16_hi(v.y)};
 #pragma unroll
       for (int c = 0; c < 4; ++c) m[c] = (k == 0) ? f[c] : fmaxf(m[c], f[c]);
     }
@@ -788,7 +746,7 @@ __global__ __launch_bounds__(256) void pool4_bf16_bwd(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const u32x2 v = __builtin_nontemporal_load(feat + base + (long)k * groups);
-      f[k][0] = bf_lo(v.x); f[k][1] = bf_hi(v.x); f[k][2] = bf_lo(v.y); f[k][3] = bf_hi(v.y);
+      f[k][0] = dd_bf16_lo(v.x); f[k][1] = dd_bf16_hi(v.x); f[k][2] = dd_bf16_lo(v.y); f[k][3] = dd_bf16_hi(v.y);
     }
     const float* gp = dpooled + b * (quads * C) + qd;
     float d[4][4];
@@ -807,8 +765,8 @@ __global__ __launch_bounds__(256) void pool4_bf16_bwd(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       u32x2 o;
-      o.x = pack_bf16(d[k][0], d[k][1]);
-      o.y = pack_bf16(d[k][2], d[k][3]);
+      o.x = dd_pack_bf16(d[k][0], d[k][1]);
+      o.y = dd_pack_bf16(d[k][2], d[k][3]);
       __builtin_nontemporal_store(o, dfeat + base + (long)k * groups);
     }
   }
@@ -840,7 +798,7 @@ __global__ __launch_bounds__(256) void pool4_bf16_fwd_tile(const u32x4* __restri
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned w = v[k][j >> 1];
-        f[k] = (j & 1) ? bf_hi(w) : bf_lo(w);
+        f[k] = (j & 1) ? dd_bf16_hi(w) : dd_bf16_lo(w);
       }
       float m = f[0];
       unsigned am = 0;
@@ -895,7 +853,7 @@ __global__ __launch_bounds__(256) void pool4_bf16_bwd_tile(const float* __restri
       d[j] = ((c4 & 4u) && (c4 & 3u) == (unsigned)pos) ? g[8 * c8 + j][qd] : 0.f;
     }
     u32x4 o;
-    o.x = pack_bf16(d[0], d[1]); o.y = pack_bf16(d[2], d[3]); o.z = pack_bf16(d[4], d[5]); o.w = pack_bf16(d[6], d[7]);
+    o.x = dd_pack_bf16(d[0], d[1]); o.y = dd_pack_bf16(d[2], d[3]); o.z = dd_pack_bf16(d[4], d[5]); o.w = dd_pack_bf16(d[6], d[7]);
     __builtin_nontemporal_store(o, out + i);
   }
 }
@@ -904,26 +862,19 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const f32x4* __restric
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const f32x4 v = src[i];
     u32x2 o;
-    o.x = pack_bf16(v.x, v.y);
-    o.y = pack_bf16(v.z, v.w);
+    o.x = dd_pack_bf16(v.x, v.y);
+    o.y = dd_pack_bf16(v.z, v.w);
     dst[i] = o;
   }
 }
 __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const u32x2* __restrict__ src, f32x4* __restrict__ dst, long n4) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const u32x2 v = src[i];
-    dst[i] = f32x4{bf_lo(v.x), bf_hi(v.x), bf_lo(v.y), bf_hi(v.y)};
+    dst[i] = f32x4{dd_bf16_lo(v.x), dd_bf16_hi(v.x), dd_bf16_lo(v.y), dd_bf16_hi(v.y)};
   }
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-template <typename K>
-int allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return 0;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return e == hipSuccess ? 0 : dd_fail(DD_ERR_LAUNCH, "hipFuncSetAttribute(%zu bytes LDS): %s", bytes, hipGetErrorString(e));
-}
-
 // resident grid: as many workgroups as fit on the CUs this library may use (occupancy from the runtime, cached per kernel)
 template <typename K>
 int resident_blocks(K kernel, int threads, size_t lds, int* out) {
@@ -974,7 +925,7 @@ int launch_strip(const unsigned short* x, const unsigned short* wp, const float*
                  unsigned* bits_out, const Geo& g, hipStream_t st) {
   auto kern = bf_strip_fwd<CIN, S, EPI, kWPB>;
   const size_t lds = 128 + (size_t)kWPB * (BCfg<CIN, S>::WAVEB + 2048);
-  if (int rc = allow_lds(kern, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)kern, lds)) return rc;
   int grid = 0;
   if (int rc = resident_blocks(kern, kWPB * 64, lds, &grid)) return rc;
   const long tiles = (long)g.B * g.nstrips * g.Ho;
@@ -989,7 +940,7 @@ template <int CIN, int S>
 int wgrad_grid(const Geo& g, int* grid, size_t* lds, bool whole_chip = false) {
   auto kern = bf_wgrad<CIN, S, kWPB>;
   *lds = (size_t)kWPB * WCfg<CIN, S>::WAVEB;
-  if (int rc = allow_lds(kern, *lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)kern, *lds)) return rc;
   if (int rc = resident_blocks(kern, kWPB * 64, *lds, grid)) return rc;
   if (whole_chip) *grid = *grid / dd_cu_budget_internal() * DD_NUM_CU;     // workspace sizing must not depend on the budget
   const long tiles = (long)g.B * g.nstrips * g.Ho;

@@ -22,8 +22,6 @@
 // Cout <= 16 (up_conv_3 forward, up_conv_4 both ways) would leave half or more of a 32-wide column tile empty: those run on
 // v_mfma_f32_16x16x4_f32 (NT = 0 below: same flop rate, N = 16): four 16-pixel m-tiles per wave, lane (g = l >> 4, m = l & 15)
 // holds channels 2g, 2g+1 of pixel m (A, one ds_read_b64) and of column m (B); MFMA j multiplies channels (j, 2+j, 4+j, 6+j).
-#define DD_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 #include <stdlib.h>
 
 #include "dd_common.h"
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(DC_THREADS) void dconv_fwd_kernel(const float* __re
           if constexpr (N16) {
 #pragma unroll
             for (int t4 = 0; t4 < 4; ++t4) P[slot][t4] = *(const f32x2*)(p + 512 * t4);
-            Q[slot] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ws, lane * 8, (q * T + cky * K + ckx) * 512, 0));
+            Q[slot] = dd_bload<f32x2>(ws, lane * 8, (q * T + cky * K + ckx) * 512);
           } else {
             A0[slot] = *(const f32x4*)p;
             A1[slot] = *(const f32x4*)(p + 1024);
@@ -326,7 +324,7 @@ __global__ __launch_bounds__(DC_THREADS) void dconv_fwd_kernel(const float* __re
               const char* p = lbase + (c * D) * 32;
 #pragma unroll
               for (int t4 = 0; t4 < 4; ++t4) Pq[c][t4] = *(const f32x2*)(p + 512 * t4);
-              Qq[c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ws, lane * 8, (q * T + c) * 512, 0));
+              Qq[c] = dd_bload<f32x2>(ws, lane * 8, (q * T + c) * 512);
             }
             for (int r = 0; r < K; ++r) {
               const int rn = min(r + 1, K - 1);
@@ -348,7 +346,7 @@ __global__ __launch_bounds__(DC_THREADS) void dconv_fwd_kernel(const float* __re
                 }
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) Pq[c][t4] = *(const f32x2*)(prow + (c * D) * 32 + 512 * t4);
-                Qq[c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ws, lane * 8, srow + c * 512, 0));
+                Qq[c] = dd_bload<f32x2>(ws, lane * 8, srow + c * 512);
                 __builtin_amdgcn_sched_barrier(0);
               }
             }

@@ -40,10 +40,6 @@
 
 namespace {
 
-
-// LDS-DMA fills must have landed (vmcnt) before the barrier publishes the buffer; LDS reads of this step are done (lgkmcnt).
-__device__ __forceinline__ void mf_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 struct MfTask {
   int b, oy, rows, ky0, ky1;
 };
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(NW * 64, 2) void dconv_mfwd_kernel(const float* __r
   MfTask cur, nxt;
   decode(u0, cur);
   fill(0, cur, 0, cur.ky0);
-  mf_barrier();
+  dd_barrier_dma();
   int par = 0;
   long u = u0;
   while (u < u1) {
@@ -209,7 +205,7 @@ __global__ __launch_bounds__(NW * 64, 2) void dconv_mfwd_kernel(const float* __r
 #pragma unroll
           for (int nt = 0; nt < NTC; ++nt) Bc[nt] = Bn[nt];
         }
-        mf_barrier();
+        dd_barrier_dma();
         par ^= 1;
       }
     }
@@ -401,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void dconv_mwin_kernel(const float* __restr
 #pragma unroll
   for (int p = 0; p < R; ++p) fill_row(p, cur, p, 0);
   fill_w(0, 0, 0);
-  mf_barrier();
+  dd_barrier_dma();
   int par = 0;
   long u = u0;
   while (u < u1) {
@@ -478,7 +474,7 @@ __global__ __launch_bounds__(512, 2) void dconv_mwin_kernel(const float* __restr
 #pragma unroll
           for (int nt = 0; nt < NTC; ++nt) Bc[nt] = Bn[nt];
         }
-        mf_barrier();
+        dd_barrier_dma();
         par ^= 1;
       }
       sbase = (sbase + SWEEP) % NSLOT;

@@ -28,10 +28,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4s;
-#define SP_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
 constexpr int SP_THREADS = 512;
 constexpr int SP_PXB = 112;                 // bytes of one pixel of one 16-channel chunk in xs and in LDS
 
@@ -43,26 +39,18 @@ __device__ __forceinline__ const char* sp_uni(const char* p) {
   return (const char*)(((unsigned long)hi << 32) | lo);
 }
 
-__device__ __forceinline__ void sp_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // ---- x = hi + mid + lo: three ROUNDINGS to nearest-even (v_cvt_pk_bf16_f32), each of the remainder of the one before.  Both
 // remainders are exact fp32 subtractions, so the three pieces miss x by the last rounding only (<= 2^-27 |x|).  Truncation would make
 // the sum exact, but every piece then has the sign of x and the three dropped cross products (am*bl + al*bm + al*bl) the sign of a*b: a
 // BIASED 2^-23 |a b| per product, which a 67 M-term weight-gradient sum with heavy cancellation turns into 2e-5 of its result (measured:
 // the B = 32 box step against the mean of 32 single-scene steps); with rounded pieces the dropped terms are zero-mean and the error
 // grows like a random walk, as the exact fp32 kernels' own rounding does.
-typedef __attribute__((ext_vector_type(2))) __bf16 sp_bf16x2;
-typedef __attribute__((ext_vector_type(2))) float sp_f32x2;
-__device__ __forceinline__ unsigned sp_rne_bits(float x) {      // the bf16 nearest x, as the upper half of an fp32 pattern
-  const unsigned two = __builtin_bit_cast(unsigned, __builtin_convertvector((sp_f32x2){x, 0.f}, sp_bf16x2));
-  return two << 16;
-}
 __device__ __forceinline__ void sp_split(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
-  hi = sp_rne_bits(x);
+  hi = dd_bf16_round_bits(x);
   const float r = x - __builtin_bit_cast(float, hi);
-  mid = sp_rne_bits(r);
+  mid = dd_bf16_round_bits(r);
   const float s = r - __builtin_bit_cast(float, mid);
-  lo = sp_rne_bits(s);
+  lo = dd_bf16_round_bits(s);
 }
 
 // one thread per (image row, chunk, pixel, 8-channel half): 32 B in, 3 x 16 B out (+ the 16 B pad from half 0)
@@ -83,17 +71,17 @@ __global__ __launch_bounds__(256) void split_input_kernel(const float* __restric
 #pragma unroll
     for (int j = 0; j < 8; ++j) sp_split(v[j], h[j], m[j], l[j]);
     char* dst = xs + ((r * NC + q) * W + px) * SP_PXB + half * 16;
-    u32x4s oh, om, ol;
+    u32x4 oh, om, ol;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       oh[j] = (h[2 * j] >> 16) | h[2 * j + 1];
       om[j] = (m[2 * j] >> 16) | m[2 * j + 1];
       ol[j] = (l[2 * j] >> 16) | l[2 * j + 1];
     }
-    *(u32x4s*)dst = oh;
-    *(u32x4s*)(dst + 32) = om;
-    *(u32x4s*)(dst + 64) = ol;
-    if (half == 0) *(u32x4s*)(dst + 96) = u32x4s{0u, 0u, 0u, 0u};
+    *(u32x4*)dst = oh;
+    *(u32x4*)(dst + 32) = om;
+    *(u32x4*)(dst + 64) = ol;
+    if (half == 0) *(u32x4*)(dst + 96) = u32x4{0u, 0u, 0u, 0u};
   }
 }
 
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_stfwd_kernel(const char* __r
       fill_next();
       if (NBUF == 3 && nstage > 1) fill_next();
       wait_all_but_newest(NBUF == 3 && nstage > 1);
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      dd_barrier_lds();
       for (int s = 0; s < nstage; ++s) {
         const char* sb = lds + par * STAGE;
         const char* bp = sb + AROW + lane * 16;
@@ -290,12 +278,12 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_stfwd_kernel(const char* __r
           }
           __builtin_amdgcn_sched_barrier(0);
           if (valid(i) && !(abl & 1)) {                       // hi = [0], mid = [1], lo = [2]; smallest products first
-            acc[i] = SP_MFMA(A[2], Bc[0], acc[i]);
-            acc[i] = SP_MFMA(A[0], Bc[2], acc[i]);
-            acc[i] = SP_MFMA(A[1], Bc[1], acc[i]);
-            acc[i] = SP_MFMA(A[1], Bc[0], acc[i]);
-            acc[i] = SP_MFMA(A[0], Bc[1], acc[i]);
-            acc[i] = SP_MFMA(A[0], Bc[0], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[2], Bc[0], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[0], Bc[2], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[1], Bc[1], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[1], Bc[0], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[0], Bc[1], acc[i]);
+            acc[i] = DD_MFMA_BF16(A[0], Bc[0], acc[i]);
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -307,7 +295,7 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_stfwd_kernel(const char* __r
         // the NEXT stage's fill has landed (this wave's share; the barrier adds the others'), every wave is done with buffer `par`
         if (abl & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else wait_all_but_newest(NBUF == 3 && filled > s + 2);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        dd_barrier_lds();
         par = par + 1 == NBUF ? 0 : par + 1;
       }
     }
@@ -351,7 +339,7 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_stfwd_kernel(const char* __r
             }
           }
         }
-        sp_barrier();
+        dd_barrier_dma();
       }
     }
     {
@@ -371,21 +359,21 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_stfwd_kernel(const char* __r
           o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
         }
         const int off = (px < d.out_w && cch < d.cout) ? (base + px * d.out_cstore) * 4 : -16;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o), ys, off, 0, 0);
+        dd_bstore(ys, off, o);
         if (yplanes) {      // this thread's four channels of the pixel: 8 bytes per plane
           const int ncp = d.cout >> 4;
           const __amdgpu_buffer_rsrc_t ps = dd_rsrc(yplanes + (long)cur.b * d.out_h * ncp * d.out_w * SP_PXB, d.out_h * ncp * d.out_w * SP_PXB);
           const int poff = (px < d.out_w && cch < d.cout) ? ((cur.oy * ncp + (cch >> 4)) * d.out_w + px) * SP_PXB + (cch & 15) * 2 : -16;
           unsigned h[4], m[4], l[4];
           sp_split(o.x, h[0], m[0], l[0]); sp_split(o.y, h[1], m[1], l[1]); sp_split(o.z, h[2], m[2], l[2]); sp_split(o.w, h[3], m[3], l[3]);
-          typedef __attribute__((ext_vector_type(2))) unsigned u32x2s;
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2s{(h[0] >> 16) | h[1], (h[2] >> 16) | h[3]}, ps, poff, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2s{(m[0] >> 16) | m[1], (m[2] >> 16) | m[3]}, ps, poff < 0 ? poff : poff + 32, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b64(u32x2s{(l[0] >> 16) | l[1], (l[2] >> 16) | l[3]}, ps, poff < 0 ? poff : poff + 64, 0, 0);
+          // the builtin as it stands: with the value behind the offset (dd_bstore's argument order) the three stores are scheduled differently
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{(h[0] >> 16) | h[1], (h[2] >> 16) | h[3]}, ps, poff, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{(m[0] >> 16) | m[1], (m[2] >> 16) | m[3]}, ps, poff < 0 ? poff : poff + 32, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{(l[0] >> 16) | l[1], (l[2] >> 16) | l[3]}, ps, poff < 0 ? poff : poff + 64, 0, 0);
         }
       }
     }
-    sp_barrier();
+    dd_barrier_dma();
     t = next_task(t + per_x, cur);
   }
 }
@@ -470,7 +458,7 @@ __global__ __launch_bounds__(NW * 64) void dconv_sgfwd_kernel(const char* __rest
 
     fill_a(0, cb, coy, 0);
     fill_b(0, 0, 0, 0);
-    sp_barrier();
+    dd_barrier_dma();
     int apar = 0, bpar = 0;
     bf16x8 A[K][3];
     for (int q = 0; q < NC; ++q) {
@@ -510,17 +498,17 @@ __global__ __launch_bounds__(NW * 64) void dconv_sgfwd_kernel(const char* __rest
               Bn[2] = *(const bf16x8*)(bp + (kx + 1) * 3072 + 2048);
             }
             __builtin_amdgcn_sched_barrier(0);
-            acc[nt] = SP_MFMA(A[kx][2], Bc[0], acc[nt]);      // hi = [0], mid = [1], lo = [2]; smallest products first
-            acc[nt] = SP_MFMA(A[kx][0], Bc[2], acc[nt]);
-            acc[nt] = SP_MFMA(A[kx][1], Bc[1], acc[nt]);
-            acc[nt] = SP_MFMA(A[kx][1], Bc[0], acc[nt]);
-            acc[nt] = SP_MFMA(A[kx][0], Bc[1], acc[nt]);
-            acc[nt] = SP_MFMA(A[kx][0], Bc[0], acc[nt]);
+            acc[nt] = DD_MFMA_BF16(A[kx][2], Bc[0], acc[nt]);      // hi = [0], mid = [1], lo = [2]; smallest products first
+            acc[nt] = DD_MFMA_BF16(A[kx][0], Bc[2], acc[nt]);
+            acc[nt] = DD_MFMA_BF16(A[kx][1], Bc[1], acc[nt]);
+            acc[nt] = DD_MFMA_BF16(A[kx][1], Bc[0], acc[nt]);
+            acc[nt] = DD_MFMA_BF16(A[kx][0], Bc[1], acc[nt]);
+            acc[nt] = DD_MFMA_BF16(A[kx][0], Bc[0], acc[nt]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) Bc[pl] = Bn[pl];
           }
-          sp_barrier();
+          dd_barrier_dma();
           bpar ^= 1;
         }
         apar ^= 1;
@@ -578,7 +566,7 @@ __global__ __launch_bounds__(NW * 64) void dconv_sgfwd_kernel(const char* __rest
         }
       }
     }
-    sp_barrier();
+    dd_barrier_dma();
     t = next_task(t + per_x, cb, coy);
   }
 }
@@ -593,12 +581,6 @@ __global__ __launch_bounds__(NW * 64) void dconv_sgfwd_kernel(const char* __rest
 // range of input rows; per step a 32-pixel piece of an x row (all chunks) and the matching 74-pixel piece of the g row iy + D*ky sit in
 // LDS (two buffers, filled by LDS-DMA one step ahead); wave w < K owns tap column kx = w and its (Cin/32) x (Cout/32) accumulator tiles
 // (the eighth wave only helps with the fills); partials per workgroup, fixed-order fp64 second stage (deterministic).
-typedef __attribute__((ext_vector_type(4))) short sp_s16x4;
-typedef sp_s16x4 __attribute__((address_space(3))) * sp_lds_s16x4_ptr;
-__device__ __forceinline__ sp_s16x4 sp_tr_read(const char* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((sp_lds_s16x4_ptr)p); }
-__device__ __forceinline__ bf16x8 sp_join(sp_s16x4 a, sp_s16x4 b) {
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <int C, int O>
 struct SwGeom {
@@ -668,7 +650,7 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_swgrad_kernel(const char* __
   };
 
   if (nsteps > 0) fill(0);
-  sp_barrier();
+  dd_barrier_dma();
   int par = 0;
   for (long s = 0; s < nsteps; ++s) {
     // all of the step's operand reads BEFORE the next step's DMA is issued (a transpose read behind an LDS-DMA in program order gets an
@@ -683,14 +665,14 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_swgrad_kernel(const char* __
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) {
             const char* a = lb + a_lane + mt * (2 * G::RX) + (16 * kb) * SP_PXB + pl * 32;
-            A[kb][mt][pl] = sp_join(sp_tr_read(a), sp_tr_read(a + 4 * SP_PXB));
+            A[kb][mt][pl] = dd_join(dd_tr_read(a), dd_tr_read(a + 4 * SP_PXB));
           }
 #pragma unroll
         for (int nt = 0; nt < G::NTO; ++nt)
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl) {
             const char* bq = lb + b_lane + nt * (2 * G::RG) + (16 * kb) * SP_PXB + pl * 32;
-            Bv[kb][nt][pl] = sp_join(sp_tr_read(bq), sp_tr_read(bq + 4 * SP_PXB));
+            Bv[kb][nt][pl] = dd_join(dd_tr_read(bq), dd_tr_read(bq + 4 * SP_PXB));
           }
       }
     }
@@ -705,15 +687,15 @@ __global__ __launch_bounds__(SP_THREADS) void dconv_swgrad_kernel(const char* __
 #pragma unroll
           for (int nt = 0; nt < G::NTO; ++nt) {
             f32x16& c = acc[mt * G::NTO + nt];
-            c = SP_MFMA(A[kb][mt][2], Bv[kb][nt][0], c);      // hi = [0], mid = [1], lo = [2]; smallest products first
-            c = SP_MFMA(A[kb][mt][0], Bv[kb][nt][2], c);
-            c = SP_MFMA(A[kb][mt][1], Bv[kb][nt][1], c);
-            c = SP_MFMA(A[kb][mt][1], Bv[kb][nt][0], c);
-            c = SP_MFMA(A[kb][mt][0], Bv[kb][nt][1], c);
-            c = SP_MFMA(A[kb][mt][0], Bv[kb][nt][0], c);
+            c = DD_MFMA_BF16(A[kb][mt][2], Bv[kb][nt][0], c);      // hi = [0], mid = [1], lo = [2]; smallest products first
+            c = DD_MFMA_BF16(A[kb][mt][0], Bv[kb][nt][2], c);
+            c = DD_MFMA_BF16(A[kb][mt][1], Bv[kb][nt][1], c);
+            c = DD_MFMA_BF16(A[kb][mt][1], Bv[kb][nt][0], c);
+            c = DD_MFMA_BF16(A[kb][mt][0], Bv[kb][nt][1], c);
+            c = DD_MFMA_BF16(A[kb][mt][0], Bv[kb][nt][0], c);
           }
     }
-    sp_barrier();
+    dd_barrier_dma();
     par ^= 1;
   }
   if (wave < K) {

@@ -45,13 +45,6 @@ struct TfGeom {
   static constexpr int HALO = D * (K - 1);
 };
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding vector-memory operation
-// (vmcnt(0)): here that would drain the weight fragments requested a tap row ahead at every chunk boundary -- a full L2
-// round trip with all 8 waves of the workgroup idle (measured: ~3k cycles per chunk, 12 % of up_conv_1's forward).  Nothing this
-// kernel reads from global memory is written by it, so only the LDS patch / row image need the ordering.
-__device__ __forceinline__ void tf_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-
 struct TfTask {
   int b, nt, oy, ry, ky0, ky1;
 };
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < NSLOT; ++i) bload(i, 0, ky0, cur.nt);
       }
-      tf_barrier();
+      dd_barrier_lds();
       constexpr int AR = ONE_MT ? 1 : 3;                    // A fragments are requested AR tiles ahead
       static_assert(ONE_MT || NSLOT % AR == 0, "A ring");
       frag Af[AR];
@@ -252,7 +245,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd_kernel(const float* __r
             }
           }
         }
-        tf_barrier();
+        dd_barrier_lds();
         par ^= 1;
       }
       // lds[par] now holds what was fetched during the last chunk: the first rows of the next task's chunk 0.  Rows it has
@@ -312,7 +305,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd_kernel(const float* __r
             }
           }
         }
-        tf_barrier();
+        dd_barrier_lds();
       }
     }
     {
@@ -332,10 +325,10 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd_kernel(const float* __r
           o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
         }
         const int off = (px < d.out_w && cch < d.cout) ? (base + px * d.out_cstore) * 4 : -16;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o), ys, off, 0, 0);
+        dd_bstore(ys, off, o);
       }
     }
-    tf_barrier();
+    dd_barrier_lds();
     prefetched = fetched_next;
     cur = nxt;
     t = tn;
@@ -443,7 +436,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_gfwd_kernel(const float* __r
 #pragma unroll
       for (int kx = 0; kx < K; ++kx) bload(kx, 0, 0);
     }
-    tf_barrier();
+    dd_barrier_lds();
     for (int q = 0; q < NC; ++q) {
       const bool more = q + 1 < NC;
       const char* lbase = (const char*)&lds[par][0];
@@ -486,7 +479,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_gfwd_kernel(const float* __r
           }
         }
       }
-      tf_barrier();
+      dd_barrier_lds();
       par ^= 1;
     }
 
@@ -526,7 +519,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_gfwd_kernel(const float* __r
 #pragma unroll
       for (int nt = 0; nt < NTC; ++nt) put(acc[nt], wave, nt, bv[nt], wave < n_mt);
     }
-    tf_barrier();
+    dd_barrier_lds();
     prefetched = have_next;
     cb = nb; coy = noy;
     t = tn;
@@ -728,7 +721,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd8_kernel(const float* __
       __builtin_amdgcn_sched_barrier(0);
       if (st) retire(par ^ 1, stage);
       if (!lastk) {
-        tf_barrier();
+        dd_barrier_lds();
         par ^= 1;
       }
     }
@@ -737,7 +730,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd8_kernel(const float* __
     // inside a tile the columns of different taps land on the same output pixel from different accumulator rows (row + shift), and a
     // batched read-add-write of all 16 rows would lose one of the two; per plane a tile's lanes never meet, the write-out adds the planes.
     for (int i = tid; i < 4 * IMGF / 4; i += TF_THREADS) ((f32x4*)&img[0][0])[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    tf_barrier();
+    dd_barrier_lds();
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       if (c == ((wave & 1) | (((wave >> 1) & 1) << 1)) && col_ok) {
@@ -751,7 +744,7 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd8_kernel(const float* __
           for (int e = 0; e < 16; ++e) p0[((e & 3) + 8 * (e >> 2)) * 8] = tv[e] + acc[i][e];
         }
       }
-      tf_barrier();
+      dd_barrier_lds();
     }
     {
       const __amdgpu_buffer_rsrc_t ys = dd_rsrc(y + (long)cur.b * d.omem_h * d.omem_w * d.out_cstore, out_bytes);
@@ -768,10 +761,10 @@ __global__ __launch_bounds__(TF_THREADS) void dconv_tfwd8_kernel(const float* __
           o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
         }
         const int off = c4 < d.cout ? (base + px * d.out_cstore + c4) * 4 : -16;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, o), ys, off, 0, 0);
+        dd_bstore(ys, off, o);
       }
     }
-    tf_barrier();
+    dd_barrier_lds();
     par ^= 1;
     cur = nxt;
     t = tn;

@@ -5,14 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/dd_hotpath.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// D(32x32) += A(32x2) * B(2x32), exact fp32 (v_mfma_f32_32x32x2_f32, 64 cycles / SIMD).
-// lane l supplies A[row = l&31][k = l>>5] and B[k = l>>5][col = l&31];
-// D register r of lane l is D[row = (r&3) + 8*(r>>2) + 4*(l>>5)][col = l&31].
-#define DD_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#include "dd_device.h"
 
 #define DD_NUM_CU 256
 
@@ -20,6 +13,8 @@ int dd_fail(int code, const char* fmt, ...);
 int dd_adam_blocks_internal();  // persistent workgroups per CU of dd_adam_step / dd_adam_step_rankb: dd_set_adam_blocks_per_cu
 int dd_adam_spare_internal();   // compute units dd_adam_step_rankb leaves free of its workgroups: dd_set_adam_spare_cus
 int dd_cu_budget_internal();   // compute units the resident-grid (persistent) kernels may fill: dd_set_cu_budget
+// Before launching `kernel` with `bytes` of dynamic LDS: raises its limit (64 KB by default) once per kernel and host thread (runtime.hip).
+int dd_allow_lds(const void* kernel, size_t bytes);
 
 #define DD_REQUIRE(cond, code, ...)            \
   do {                                         \
@@ -33,33 +28,6 @@ int dd_cu_budget_internal();   // compute units the resident-grid (persistent) k
   } while (0)
 
 static inline int dd_conv_out(int in, int stride) { return (in + 2 - 3) / stride + 1; }
-
-__device__ __forceinline__ int dd_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
-
-// The lane id, recomputed where it is needed: a `volatile` asm is neither hoisted nor shared, so code after a long MFMA loop
-// (an epilogue's addresses, the next tile's fill plan) does not keep lane-derived registers alive across that loop -- which is
-// what the register allocator otherwise spills to scratch in kernels that use the whole register file.
-__device__ __forceinline__ int dd_fresh_lane() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
-// Raw buffer access: the descriptor (wave-uniform base + byte count) makes the hardware range-check every lane:
-// an out-of-range load returns zeros, an out-of-range store is dropped.  A negative offset is a huge unsigned
-// one, i.e. out of range.  Used for zero padding and ragged edges without branches, and as a guard against faults.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dd_rsrc(const void* base, int bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 dd_bload4(__amdgpu_buffer_rsrc_t r, int off) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-__device__ __forceinline__ float dd_bload1(__amdgpu_buffer_rsrc_t r, int off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-}
-__device__ __forceinline__ void dd_bstore1(__amdgpu_buffer_rsrc_t r, int off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, 0);
-}
 
 // s += p[0] + p[stride] + ... (n terms), left to right -- the order, and so the bits, of the plain loop -- with SIXTEEN loads in flight:
 // the second stages of the weight / bias gradients add a few hundred per-workgroup partials per output element, and written as
@@ -75,14 +43,6 @@ __device__ __forceinline__ void dd_sum_strided(Acc& s, const float* __restrict__
     for (int j = 0; j < 16; ++j)
       if (i + j < n) s += (Acc)v[j];
   }
-}
-
-// The contiguous range [idx, end) of `total` work items owned by piece `i` of `n` equal pieces.
-__device__ __forceinline__ void dd_range(long total, int i, int n, long& idx, long& end) {
-  const long per = (total + n - 1) / n;
-  idx = (long)i * per;
-  end = idx + per < total ? idx + per : total;
-  if (idx > end) idx = end;
 }
 
 // dconv_t.hip: the input-aligned forward of the dilated transposed layers; false = not one of its layers, nothing launched.

@@ -19,17 +19,7 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {   // round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ float bfr(float v) { return bf_lo(pack_bf16(v, 0.f)); }
+__device__ __forceinline__ float bfr(float v) { return dd_bf16_lo(dd_pack_bf16(v, 0.f)); }
 __device__ __forceinline__ float bf_at(const unsigned short* p, long i) { return __builtin_bit_cast(float, (unsigned)p[i] << 16); }
 
 // 32 bf16 channels of one NHWC pixel (64 bytes, 16-byte aligned) <-> 16 packed words
@@ -41,13 +31,13 @@ __device__ __forceinline__ void load_px32(const unsigned short* base, long pix, 
     u[4 * q] = v.x; u[4 * q + 1] = v.y; u[4 * q + 2] = v.z; u[4 * q + 3] = v.w;
   }
 }
-__device__ __forceinline__ float px_ch(const unsigned (&u)[16], int c) { return (c & 1) ? bf_hi(u[c >> 1]) : bf_lo(u[c >> 1]); }
+__device__ __forceinline__ float px_ch(const unsigned (&u)[16], int c) { return (c & 1) ? dd_bf16_hi(u[c >> 1]) : dd_bf16_lo(u[c >> 1]); }
 __device__ __forceinline__ void store_px32(unsigned short* base, long pix, const float (&v)[32]) {
   u32x4* p = (u32x4*)(base + pix * 32);
 #pragma unroll
   for (int q = 0; q < 4; ++q)
-    p[q] = u32x4{pack_bf16(v[8 * q], v[8 * q + 1]), pack_bf16(v[8 * q + 2], v[8 * q + 3]), pack_bf16(v[8 * q + 4], v[8 * q + 5]),
-                 pack_bf16(v[8 * q + 6], v[8 * q + 7])};
+    p[q] = u32x4{dd_pack_bf16(v[8 * q], v[8 * q + 1]), dd_pack_bf16(v[8 * q + 2], v[8 * q + 3]), dd_pack_bf16(v[8 * q + 4], v[8 * q + 5]),
+                 dd_pack_bf16(v[8 * q + 6], v[8 * q + 7])};
 }
 
 constexpr int kThreads = 256;
@@ -73,8 +63,8 @@ __global__ __launch_bounds__(kThreads) void split64_kernel(const float* __restri
     const long yx = p - (long)b * hw;
     const float* src = h + ((long)b * 64 + 8 * g) * hw + yx;
     u32x4 o;
-    o.x = pack_bf16(src[0], src[hw]); o.y = pack_bf16(src[2 * hw], src[3 * hw]);
-    o.z = pack_bf16(src[4 * hw], src[5 * hw]); o.w = pack_bf16(src[6 * hw], src[7 * hw]);
+    o.x = dd_pack_bf16(src[0], src[hw]); o.y = dd_pack_bf16(src[2 * hw], src[3 * hw]);
+    o.z = dd_pack_bf16(src[4 * hw], src[5 * hw]); o.w = dd_pack_bf16(src[6 * hw], src[7 * hw]);
     unsigned short* dst = (g < 4 ? lo : hi) + p * 32 + (g & 3) * 8;
     *(u32x4*)dst = o;
   }
@@ -91,8 +81,8 @@ __global__ __launch_bounds__(kThreads) void merge64_kernel(const unsigned short*
     const long yx = p - (long)b * hw;
     const u32x4 v = *(const u32x4*)((g < 4 ? lo : hi) + p * 32 + (g & 3) * 8);
     float* dst = gh + ((long)b * 64 + 8 * g) * hw + yx;
-    dst[0] = bf_lo(v.x); dst[hw] = bf_hi(v.x); dst[2 * hw] = bf_lo(v.y); dst[3 * hw] = bf_hi(v.y);
-    dst[4 * hw] = bf_lo(v.z); dst[5 * hw] = bf_hi(v.z); dst[6 * hw] = bf_lo(v.w); dst[7 * hw] = bf_hi(v.w);
+    dst[0] = dd_bf16_lo(v.x); dst[hw] = dd_bf16_hi(v.x); dst[2 * hw] = dd_bf16_lo(v.y); dst[3 * hw] = dd_bf16_hi(v.y);
+    dst[4 * hw] = dd_bf16_lo(v.z); dst[5 * hw] = dd_bf16_hi(v.z); dst[6 * hw] = dd_bf16_lo(v.w); dst[7 * hw] = dd_bf16_hi(v.w);
   }
 }
 
@@ -101,7 +91,6 @@ __global__ __launch_bounds__(kThreads) void merge64_kernel(const unsigned short*
 // pixel n, 8 channels of one tap per lane = one 16-byte load, zero outside the image).  Accumulator register r of lane l holds
 // channel (r&3) + 8(r>>2) + 4(l>>5) of pixel l&31.
 constexpr int kDc1Steps = 36;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 constexpr int kWaves = kThreads / 64;
 
 __global__ __launch_bounds__(kThreads) void dc1_fwd_mfma_kernel(const unsigned short* __restrict__ xlo, const unsigned short* __restrict__ xhi,
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void dc1_fwd_mfma_kernel(const unsigned s
     const int tap = s >> 2, cb = s & 3, co = lane & 31;
     const int ci = cb * 16 + 8 * (lane >> 5) + 2 * jj;
     // the equivalent convolution's weight Wc[co][ci][tap] = w1[ci][co][8 - tap] (transposed, flipped)
-    wpk[i] = pack_bf16(w1[(ci * 32 + co) * 9 + 8 - tap], w1[((ci + 1) * 32 + co) * 9 + 8 - tap]);
+    wpk[i] = dd_pack_bf16(w1[(ci * 32 + co) * 9 + 8 - tap], w1[((ci + 1) * 32 + co) * 9 + 8 - tap]);
   }
   if (threadIdx.x < 32) bl[threadIdx.x] = b1[threadIdx.x];
   __syncthreads();
@@ -143,13 +132,13 @@ __global__ __launch_bounds__(kThreads) void dc1_fwd_mfma_kernel(const unsigned s
       }
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[(tap * 4 + cb) * 64 + lane], __builtin_bit_cast(bf16x8, v[cb]), acc, 0, 0, 0);
+        acc = DD_MFMA_BF16(wl[(tap * 4 + cb) * 64 + lane], __builtin_bit_cast(bf16x8, v[cb]), acc);
     }
     unsigned mine = 0;
     float v[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int co = (q & 3) + 8 * (q >> 2) + 4 * hh;
+      const int co = dd_acc_row_half(q, hh);
       v[q] = fmaxf(acc[q] + bl[co], 0.f);
       mine |= (v[q] > 0.f ? 1u : 0u) << co;
     }
@@ -159,8 +148,8 @@ __global__ __launch_bounds__(kThreads) void dc1_fwd_mfma_kernel(const unsigned s
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         u32x2 w2;
-        w2.x = pack_bf16(v[4 * g], v[4 * g + 1]);
-        w2.y = pack_bf16(v[4 * g + 2], v[4 * g + 3]);
+        w2.x = dd_pack_bf16(v[4 * g], v[4 * g + 1]);
+        w2.y = dd_pack_bf16(v[4 * g + 2], v[4 * g + 3]);
         *(u32x2*)(a1 + op * 32 + 8 * g + 4 * hh) = w2;
       }
       if (bits && hh == 0) bits[op] = word;

@@ -151,7 +151,7 @@ struct BnVec;
 template <>
 struct BnVec<4> { typedef f32x4 T; };
 template <>
-struct BnVec<2> { typedef float T __attribute__((ext_vector_type(2))); };
+struct BnVec<2> { typedef f32x2 T; };
 
 __global__ __launch_bounds__(256) void bn_relu_drop_fwd_vec4(const float* __restrict__ x, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ rmean,
@@ -481,8 +481,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const float inv_bc2 = 1.f / bc2_sqrt;
 #pragma unroll
     for (int k = 0; k < 4; k += 2) {
-      f32x2a pe = {pv[k], pv[k + 1]}, me = {mv[k], mv[k + 1]}, ve = {vv[k], vv[k + 1]};
-      adam_elem2(pe, me, ve, f32x2a{gv[k], gv[k + 1]}, gscale, b1, b2, eps, step_size, inv_bc2);
+      f32x2 pe = {pv[k], pv[k + 1]}, me = {mv[k], mv[k + 1]}, ve = {vv[k], vv[k + 1]};
+      adam_elem2(pe, me, ve, f32x2{gv[k], gv[k + 1]}, gscale, b1, b2, eps, step_size, inv_bc2);
       pv[k] = pe.x; pv[k + 1] = pe.y; mv[k] = me.x; mv[k + 1] = me.y; vv[k] = ve.x; vv[k + 1] = ve.y;
     }
     __builtin_nontemporal_store(pv, (f32x4*)p + i);

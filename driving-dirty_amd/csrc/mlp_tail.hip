@@ -16,7 +16,6 @@
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int TM = 32, TH = 128;
 constexpr int TAIL_THREADS = 1024;      // one workgroup: the more waves, the more loads in flight per memory round trip
 constexpr int LDF = TH + 4;      // pitch of a row-major tile  [row m][feature]   (float4 along the features)
@@ -46,11 +45,11 @@ template <bool TR>
 __device__ __forceinline__ void load_tile(float* dst, int ld, const float* src, int rows, int cols, int pad_rows) {
   const int total = pad_rows * cols, valid = rows * cols;
   for (int base = threadIdx.x * 4; base < total; base += TAIL_THREADS * 4 * 8) {
-    f4 v[8];
+    f32x4 v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = base + u * TAIL_THREADS * 4;
-      v[u] = (i < valid) ? *(const f4*)(src + i) : f4{0.f, 0.f, 0.f, 0.f};
+      v[u] = (i < valid) ? *(const f32x4*)(src + i) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -61,7 +60,7 @@ __device__ __forceinline__ void load_tile(float* dst, int ld, const float* src, 
 #pragma unroll
           for (int q = 0; q < 4; ++q) dst[(c + q) * ld + r] = v[u][q];
         } else {
-          *(f4*)(dst + r * ld + c) = v[u];
+          *(f32x4*)(dst + r * ld + c) = v[u];
         }
       }
     }
@@ -81,12 +80,12 @@ __device__ __forceinline__ void gemm_kmajor(const float* A, int lda, const float
   const int tj = J / 4, tiles = (I / 4) * tj;
   for (int t = threadIdx.x; t < tiles; t += TAIL_THREADS) {
     const int i0 = 4 * (t / tj), j0 = 4 * (t % tj);
-    f4 acc[4];
+    f32x4 acc[4];
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) acc[ii] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int ii = 0; ii < 4; ++ii) acc[ii] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
     for (int k = 0; k < K; ++k) {      // unrolled: eight pairs of LDS reads in flight (one workgroup = nothing else hides LDS latency)
-      const f4 av = *(const f4*)(A + k * lda + i0), bv = *(const f4*)(B + k * ldb + j0);
+      const f32x4 av = *(const f32x4*)(A + k * lda + i0), bv = *(const f32x4*)(B + k * ldb + j0);
 #pragma unroll
       for (int ii = 0; ii < 4; ++ii) acc[ii] += av[ii] * bv;
     }
@@ -106,7 +105,7 @@ __device__ __forceinline__ void bn_relu_drop(const float* Xt, float* Yt, float* 
       float s = 0.f, ss = 0.f;
       float xr[TM];      // the batch column in registers (rows beyond M are zero in the tile)
 #pragma unroll
-      for (int r = 0; r < TM; r += 4) *(f4*)(xr + r) = *(const f4*)(x + r);
+      for (int r = 0; r < TM; r += 4) *(f32x4*)(xr + r) = *(const f32x4*)(x + r);
 #pragma unroll
       for (int r = 0; r < TM; ++r) s += (r < M) ? xr[r] : 0.f;
       mean = s / M;
@@ -153,17 +152,17 @@ __global__ __launch_bounds__(TAIL_THREADS) void mlp_tail_fwd_kernel(TailFwd a) {
                a.scale1, a.training);
   __syncthreads();
   // lin2[m][n] = bias2[n] + sum_k y1[m][k] W2[n][k]  -> At (feature-major [n][m]) and global
-  gemm_kmajor(Bt, LDM, Wt, LDF, Mp, a.H2, a.H1, [&](int m0, int n0, const f4 (&acc)[4]) {
+  gemm_kmajor(Bt, LDM, Wt, LDF, Mp, a.H2, a.H1, [&](int m0, int n0, const f32x4 (&acc)[4]) {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const float bb = a.bias2[n0 + jj];
-      f4 col;
+      f32x4 col;
 #pragma unroll
       for (int ii = 0; ii < 4; ++ii) {
         col[ii] = (m0 + ii < a.M) ? acc[ii][jj] + bb : 0.f;
         if (m0 + ii < a.M) a.lin2[(m0 + ii) * a.H2 + n0 + jj] = col[ii];
       }
-      *(f4*)(At + (n0 + jj) * LDM + m0) = col;
+      *(f32x4*)(At + (n0 + jj) * LDM + m0) = col;
     }
   });
   __syncthreads();
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void mlp_tail_fwd_kernel(TailFwd a) {
   bn_relu_drop(At, Bt, a.y2, a.M, a.H2, a.g2, a.b2, a.rm2, a.rv2, a.nbt2, a.keep2 ? Kp : nullptr, a.mean2, a.inv2, a.eps2, a.mom2,
                a.scale2, a.training);
   __syncthreads();
-  gemm_kmajor(Bt, LDM, Wt, LDF, Mp, a.L, a.H2, [&](int m0, int n0, const f4 (&acc)[4]) {
+  gemm_kmajor(Bt, LDM, Wt, LDF, Mp, a.L, a.H2, [&](int m0, int n0, const f32x4 (&acc)[4]) {
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii)
       if (m0 + ii < a.M) {
@@ -227,18 +226,18 @@ __global__ __launch_bounds__(TAIL_THREADS) void mlp_tail_bwd_kernel(TailBwd a) {
   load_rows(Q, LDF, a.lin2, a.M, a.H2, a.M);
   load_rows(W, LDF, a.wz, a.L, a.H2, a.L);
   __syncthreads();
-  gemm_kmajor(G, LDF, P, LDF, a.L, a.H2, a.M, [&](int l0, int k0, const f4 (&acc)[4]) {      // dWz[l][k] = sum_m dz[m][l] y2[m][k]
+  gemm_kmajor(G, LDF, P, LDF, a.L, a.H2, a.M, [&](int l0, int k0, const f32x4 (&acc)[4]) {      // dWz[l][k] = sum_m dz[m][l] y2[m][k]
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) *(f4*)(a.dwz + (l0 + ii) * a.H2 + k0) = acc[ii];
+    for (int ii = 0; ii < 4; ++ii) *(f32x4*)(a.dwz + (l0 + ii) * a.H2 + k0) = acc[ii];
   });
   for (int l = threadIdx.x; l < a.L; l += TAIL_THREADS) {
     float s = 0.f;
     for (int m = 0; m < a.M; ++m) s += G[m * LDF + l];
     a.dbz[l] = s;
   }
-  gemm_kmajor(Gt, LDM, W, LDF, Mp, a.H2, a.L, [&](int m0, int k0, const f4 (&acc)[4]) {      // dy2[m][k] = sum_l dz[m][l] Wz[l][k]
+  gemm_kmajor(Gt, LDM, W, LDF, Mp, a.H2, a.L, [&](int m0, int k0, const f32x4 (&acc)[4]) {      // dy2[m][k] = sum_l dz[m][l] Wz[l][k]
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) *(f4*)(R + (m0 + ii) * LDF + k0) = acc[ii];
+    for (int ii = 0; ii < 4; ++ii) *(f32x4*)(R + (m0 + ii) * LDF + k0) = acc[ii];
   });
   __syncthreads();
   bn_relu_drop_bwd(R, Gt, P, Q, a.M, a.H2, a.g2, a.keep2, a.mean2, a.inv2, a.rm2, a.rv2, a.dg2, a.db2, a.eps2, a.scale2,
@@ -248,18 +247,18 @@ __global__ __launch_bounds__(TAIL_THREADS) void mlp_tail_bwd_kernel(TailBwd a) {
   load_rows(P, LDF, a.y1, a.M, a.H1, TM);
   load_rows(Q, LDF, a.lin1, a.M, a.H1, a.M);
   __syncthreads();
-  gemm_kmajor(R, LDF, P, LDF, a.H2, a.H1, a.M, [&](int n0, int k0, const f4 (&acc)[4]) {     // dW2[n][k] = sum_m dlin2[m][n] y1[m][k]
+  gemm_kmajor(R, LDF, P, LDF, a.H2, a.H1, a.M, [&](int n0, int k0, const f32x4 (&acc)[4]) {     // dW2[n][k] = sum_m dlin2[m][n] y1[m][k]
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) *(f4*)(a.dw2 + (n0 + ii) * a.H1 + k0) = acc[ii];
+    for (int ii = 0; ii < 4; ++ii) *(f32x4*)(a.dw2 + (n0 + ii) * a.H1 + k0) = acc[ii];
   });
   for (int n = threadIdx.x; n < a.H2; n += TAIL_THREADS) {
     float s = 0.f;
     for (int m = 0; m < a.M; ++m) s += R[m * LDF + n];
     a.dbias2[n] = s;
   }
-  gemm_kmajor(Gt, LDM, W, LDF, Mp, a.H1, a.H2, [&](int m0, int k0, const f4 (&acc)[4]) {     // dy1[m][k] = sum_n dlin2[m][n] W2[n][k]
+  gemm_kmajor(Gt, LDM, W, LDF, Mp, a.H1, a.H2, [&](int m0, int k0, const f32x4 (&acc)[4]) {     // dy1[m][k] = sum_n dlin2[m][n] W2[n][k]
 #pragma unroll
-    for (int ii = 0; ii < 4; ++ii) *(f4*)(G + (m0 + ii) * LDF + k0) = acc[ii];
+    for (int ii = 0; ii < 4; ++ii) *(f32x4*)(G + (m0 + ii) * LDF + k0) = acc[ii];
   });
   __syncthreads();
   bn_relu_drop_bwd(G, nullptr, P, Q, a.M, a.H1, a.g1, a.keep1, a.mean1, a.inv1, a.rm1, a.rv1, a.dg1, a.db1, a.eps1,
@@ -272,13 +271,6 @@ int check_dims(const char* who, int M, int H1, int H2, int L) {
   DD_REQUIRE(M > 0 && H1 > 0 && H2 > 0 && L > 0, DD_ERR_BAD_ARG, "%s: non-positive size", who);
   DD_REQUIRE(M <= TM && H1 <= TH && H2 <= TH && L <= TH && H1 % 4 == 0 && H2 % 4 == 0 && L % 4 == 0, DD_ERR_UNSUPPORTED,
              "%s: needs M <= %d, widths <= %d and multiples of 4; got M=%d H1=%d H2=%d L=%d", who, TM, TH, M, H1, H2, L);
-  return 0;
-}
-
-template <typename K>
-int allow(K k, size_t bytes) {
-  hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return dd_fail(DD_ERR_LAUNCH, "mlp_tail: cannot reserve %zu bytes of LDS: %s", bytes, hipGetErrorString(e));
   return 0;
 }
 
@@ -310,7 +302,7 @@ int dd_mlp_tail_fwd(const float* lin1, const float* gamma1, const float* beta1, 
   a.M = m; a.H1 = h1; a.H2 = h2; a.L = l; a.training = training;
   a.eps1 = eps1; a.eps2 = eps2; a.mom1 = momentum1; a.mom2 = momentum2; a.scale1 = scale1; a.scale2 = scale2;
   const size_t lds = ((size_t)2 * TH * LDM + (size_t)TH * LDF + (size_t)TM * LDF) * 4;
-  if (int rc = allow(mlp_tail_fwd_kernel, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)mlp_tail_fwd_kernel, lds)) return rc;
   hipLaunchKernelGGL(mlp_tail_fwd_kernel, dim3(1), dim3(TAIL_THREADS), lds, (hipStream_t)stream, a);
   DD_LAUNCH_CHECK("mlp_tail_fwd");
   return 0;
@@ -337,7 +329,7 @@ int dd_mlp_tail_bwd(const float* dz, const float* lin1, const float* y1, const f
   a.dlin1 = dlin1; a.dg1 = dgamma1; a.db1 = dbeta1; a.dw2 = dw2; a.dbias2 = dbias2; a.dg2 = dgamma2; a.db2 = dbeta2; a.dwz = dwz; a.dbz = dbz;
   a.M = m; a.H1 = h1; a.H2 = h2; a.L = l; a.training = training; a.eps1 = eps1; a.eps2 = eps2; a.scale1 = scale1; a.scale2 = scale2;
   const size_t lds = ((size_t)4 * TM * LDF + (size_t)TH * LDM + (size_t)TH * LDF) * 4;
-  if (int rc = allow(mlp_tail_bwd_kernel, lds)) return rc;
+  if (int rc = dd_allow_lds((const void*)mlp_tail_bwd_kernel, lds)) return rc;
   hipLaunchKernelGGL(mlp_tail_bwd_kernel, dim3(1), dim3(TAIL_THREADS), lds, (hipStream_t)stream, a);
   DD_LAUNCH_CHECK("mlp_tail_bwd");
   return 0;

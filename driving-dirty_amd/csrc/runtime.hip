@@ -1,4 +1,4 @@
-// Error reporting of the C ABI (thread-local message; see include/dd_hotpath.h).
+// Error reporting of the C ABI (thread-local message; see include/dd_hotpath.h), library-wide settings, the dynamic-LDS opt-in.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -13,6 +13,24 @@ int dd_fail(int code, const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
+}
+
+// The opt-in to more than 64 KB of dynamic LDS is a property of the kernel that the runtime keeps, so it is asked for once: `done`
+// remembers, per host thread, the kernels that have it and with how many bytes.  A kernel that comes back with more bytes is raised
+// again.  With the table full nothing breaks: a kernel that found no slot has the attribute set again on every launch, as if there
+// were no memo.
+int dd_allow_lds(const void* kernel, size_t bytes) {
+  constexpr int SLOTS = 128;      // conv3x3.hip, conv3x3_bf16.hip and mlp_tail.hip, the callers, hold fewer than 80 kernels in all
+  static thread_local struct { const void* kernel; size_t bytes; } done[SLOTS];
+  static thread_local int ndone = 0;
+  int slot = 0;
+  while (slot < ndone && done[slot].kernel != kernel) ++slot;
+  if (slot < ndone && done[slot].bytes >= bytes) return 0;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) return dd_fail(DD_ERR_LAUNCH, "%zu bytes of dynamic LDS refused: %s", bytes, hipGetErrorString(e));
+  if (slot == ndone && ndone < SLOTS) ++ndone;
+  if (slot < ndone) { done[slot].kernel = kernel; done[slot].bytes = bytes; }
+  return 0;
 }
 
 static int g_cu_budget = DD_NUM_CU;

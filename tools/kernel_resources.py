@@ -3,10 +3,14 @@
 (the AMDGPU metadata note every kernel carries): no recompilation, no GPU.
 
     python tools/kernel_resources.py [--spills-only]
+    python tools/kernel_resources.py --diff OTHER_LIB      # kernels whose machine code or resources differ from OTHER_LIB's
 """
 import os
+import re
 import struct
+import subprocess
 import sys
+import tempfile
 import zlib
 
 import msgpack
@@ -45,15 +49,19 @@ def _code_objects(fatbin):
         pos = i + 4
 
 
-def kernels(lib=LIB):
+def _fatbin(lib):
     blob = open(lib, "rb").read()
     fat = next((blob[off:off + size] for name, _t, off, size in _sections(blob) if name == ".hip_fatbin"), None)
     if fat is None:
         raise SystemExit(f"{lib}: no .hip_fatbin section")
     if b"CCOB" in fat[:4096]:
         raise SystemExit("compressed offload bundles are not handled: build with --no-offload-compress")
+    return fat
+
+
+def kernels(lib=LIB):
     out = []
-    for co in _code_objects(fat):
+    for co in _code_objects(_fatbin(lib)):
         for name, typ, off, size in _sections(co):
             if typ != 7:                         # SHT_NOTE
                 continue
@@ -71,7 +79,50 @@ def kernels(lib=LIB):
     return out
 
 
+RESOURCES = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size", ".vgpr_spill_count",
+             ".sgpr_spill_count")
+
+
+def kernel_text(lib=LIB):
+    """{kernel symbol: its disassembly (llvm-objdump -d: instruction text and encoding, addresses dropped)} over every code object."""
+    objdump = os.environ.get("LLVM_OBJDUMP", "/opt/rocm/llvm/bin/llvm-objdump")
+    names = {k[".name"] for k in kernels(lib)}
+    out = {}
+    for co in _code_objects(_fatbin(lib)):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            asm = subprocess.check_output([objdump, "-d", f.name], text=True)
+        cur = None
+        for line in asm.splitlines():
+            m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
+            if m:
+                cur = m.group(1) if m.group(1) in names else None
+                if cur:
+                    out[cur] = []
+            elif cur and line.strip():
+                out[cur].append(re.sub(r"// [0-9A-Fa-f]+:", "//", line.strip()))
+    return out
+
+
+def diff(other):
+    """Names of the kernels that exist in one library only, or whose machine code or resource counts differ; 0 when there are none."""
+    mine, theirs = kernel_text(LIB), kernel_text(other)
+    res = [{k[".name"]: tuple(k.get(r, 0) for r in RESOURCES) for k in kernels(lib)} for lib in (LIB, other)]
+    bad = 0
+    for name in sorted(set(mine) | set(theirs)):
+        what = ("only in " + os.path.relpath(LIB, ROOT) if name not in theirs else "only in " + other if name not in mine else
+                "code differs" if mine[name] != theirs[name] else "resources differ" if res[0][name] != res[1][name] else None)
+        if what:
+            bad += 1
+            print(f"{what}: {name}")
+    print(f"{len(mine)} kernels compared with {other} ({sum(len(t) for t in mine.values())} instructions), {bad} differ")
+    return 1 if bad else 0
+
+
 def main():
+    if "--diff" in sys.argv:
+        sys.exit(diff(sys.argv[sys.argv.index("--diff") + 1]))
     ks = kernels()
     spills_only = "--spills-only" in sys.argv
     print(f"{len(ks)} kernels in {os.path.relpath(LIB, ROOT)}")
