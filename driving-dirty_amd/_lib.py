@@ -165,6 +165,12 @@ SIGNATURES = {
     "dd_component_boxes": (_i32, [_p, _f32, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "dd_component_obb_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "dd_component_obb": (_i32, [_p, _f32, _i32, _i32, _f32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_split_components_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "dd_split_components": (_i32, [_p, _f32, _i32, _i32, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_labelled_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dd_labelled_boxes": (_i32, [_p, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_labelled_obb_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "dd_labelled_obb": (_i32, [_p, _i32, _i32, _f32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "dd_box_iou_ats_workspace_bytes": (_i64, [_p, _p, _i32]),
     "dd_box_iou_ats": (_i32, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
     "dd_conv_wino_packed_floats": (_i64, [_p]),

@@ -31,6 +31,13 @@
 //    corners.  Integer add and integer max only: bit-identical from launch to launch.  Every thread that needs the heading evaluates
 //    the one function heading() on the same integers, so all of them agree bit for bit.  No loop in any of the four kernels except the
 //    slot kernel's walk along its row (W / 256 rounds, as in emit_boxes_kernel).
+// b''. dd_split_components / dd_labelled_boxes / dd_labelled_obb: marker-based splitting of blobs joined by a neck (the rule
+//    is stated in include/dd_hotpath.h).  erode (LDS, separable minimum) -> a.'s launches on the core map -> grow (g Jacobi rounds between two
+//    LDS buffers, one barrier per round, smallest neighbouring label wins) -> a.'s launches on what is left -> merge.  The result is a LABEL
+//    IMAGE whose regions are sets of equal labels, label - 1 being SOME pixel of the region (not its first).  The kernels of b. and b'. take
+//    such an image through their kRegions = true instantiations: a horizontal run ends where the label changes, the record that is zeroed
+//    is the one at pixel label - 1, and the top row is a real maximum of H - 1 - y.  The kRegions = false instantiations are the kernels of
+//    b. and b'., instruction for instruction.  LOOP BOUNDS: erode 2 r + 1 <= 17 taps, grow g <= 16 rounds of at most 16 pixels per thread.
 // c. dd_box_iou_ats: one thread per box pair, fp64, Green's theorem over the boundary of the intersection (fully unrolled: no
 //    indexed local array, no scratch), then one workgroup per sample for max over set 1, the five thresholds and the weighted mean.
 #include "dd_common.h"
@@ -48,6 +55,8 @@ constexpr int kMaxBatch = 65535;          // gridDim.z
 constexpr int kMaxSet = 4096;             // boxes per sample and set in dd_box_iou_ats
 constexpr int kObbMaxSide = 1024;         // H, W in dd_component_obb: N <= 2^20 and Sxx <= N * 1023^2 < 2^40, so N * Sxx < 2^60 fits int64
 constexpr int kObbMaxBoxes = kObbMaxSide * kObbMaxSide;      // no sample has more components than pixels
+constexpr int kMaxSplit = 8;              // split_px: the erode tile with its halo is (32 + 16)^2 bytes of LDS
+constexpr int kMaxGrow = 16;              // grow_iters: two label buffers of (32 + 32)^2 ints = 32 KB of LDS
 
 // ------------------------------------------------------------------------------------------------ a. labelling
 __device__ __forceinline__ int lds_parent(const int* par, int x) { return __hip_atomic_load(par + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -204,19 +213,60 @@ bool shape_ok(int batch, int H, int W) { return batch >= 1 && batch <= kMaxBatch
 // ------------------------------------------------------------------------------------------------ b. component boxes
 // One wave per 64-pixel segment of a row.  Horizontally adjacent foreground pixels share their label, so a run of set bits in the
 // ballot is one component: its first lane adds the run to the root's slot.
-__global__ __launch_bounds__(kThreads) void run_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int H, int W) {
+// region_run (kRegions, a label image, b''.): the length of the run of EQUAL labels that begins at this lane, 0 when none does -- a run
+// also ends where the label changes.  A label outside [1, n], or one whose pixel label - 1 does not carry it, belongs to no region and
+// starts no run, so no record outside the sample's n slots is ever touched, whatever the image holds.  v: sanitised in place.
+__device__ __forceinline__ int region_run(const int* lab, int n, int& v, int lane) {
+  if (v < 0 || v > n) v = 0;
+  const unsigned long long mask = __ballot(v != 0);
+  const int left = __shfl_up(v, 1);
+  const bool start = v != 0 && (lane == 0 || left != v);
+  const unsigned long long brk = __ballot(start) | ~mask;             // where a run cannot go on
+  if (!start || lab[v - 1] != v) return 0;
+  const unsigned long long rest = (brk >> lane) >> 1;                 // lanes after this one
+  return rest ? __ffsll((long long)rest) : 64 - lane;
+}
+
+template <bool kRegions>
+__device__ __forceinline__ void run_stats_body(const int* __restrict__ labels, Stats* __restrict__ stats, int* __restrict__ top, int H, int W) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
-  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
-  const unsigned long long mask = __ballot(v != 0);
-  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-  const unsigned long long inv = ~(mask >> lane);                     // lowest zero bit = end of the run; none: the run fills the segment
-  const int len = inv ? __ffsll((long long)inv) - 1 : 64;
+  int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  int len;
+  if constexpr (kRegions) {
+    len = region_run(labels + base, H * W, v, lane);
+    if (len == 0) return;
+  } else {
+    const unsigned long long mask = __ballot(v != 0);
+    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+    const unsigned long long inv = ~(mask >> lane);                   // lowest zero bit = end of the run; none: the run fills the segment
+    len = inv ? __ffsll((long long)inv) - 1 : 64;
+  }
   Stats* s = stats + base + (v - 1);
   atomicAdd(&s->count, len);
   atomicMax(&s->w1_minus_c0, W - 1 - x);
   atomicMax(&s->c1, x + len - 1);
   atomicMax(&s->r1, y);
+  if (kRegions) atomicMax(top + base + (v - 1), H - 1 - y);            // label - 1 need not lie in the region's first row
+}
+
+__global__ __launch_bounds__(kThreads) void run_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int H, int W) {
+  run_stats_body<false>(labels, stats, nullptr, H, W);
+}
+
+__global__ __launch_bounds__(kThreads) void region_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int* __restrict__ top, int H,
+                                                                int W) {
+  run_stats_body<true>(labels, stats, top, H, W);
+}
+
+// flatten_kernel's second duty for a label image: the records of the pixels that name a region (labels[p] == p + 1) start at zero
+__global__ __launch_bounds__(kThreads) void region_init_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int* __restrict__ top, int n) {
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= n) return;
+  const long i = (long)blockIdx.y * n + p;
+  if (labels[i] != p + 1) return;
+  stats[i] = Stats{0, 0, 0, 0};
+  top[i] = 0;
 }
 
 // exclusive prefix sum of v over the workgroup's 256 threads; total = the sum.  wsum: 4 ints of LDS.
@@ -300,6 +350,37 @@ __global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restr
   }
 }
 
+// emit_boxes_kernel for a label image (b''.): the pixel label - 1 that names a region need not lie in its top row, so r0 comes from `top`.
+// A kernel of its own, not an instantiation of a shared body as the run kernels are: with the body inlined the compiler orders one
+// scalar OR of emit_boxes_kernel differently, and that kernel is kept instruction for instruction.
+__global__ __launch_bounds__(kThreads) void emit_region_boxes_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
+                                                                     const int* __restrict__ top, const int* __restrict__ rowcnt,
+                                                                     const int* __restrict__ rowbase, float* __restrict__ boxes, int H, int W,
+                                                              int min_pixels, int max_boxes) {
+  __shared__ int wsum[kThreads / 64];
+  const int y = blockIdx.x, s = blockIdx.y;
+  if (rowcnt[s * H + y] == 0) return;                                 // uniform
+  const long base = (long)s * H * W;
+  int carry = rowbase[s * H + y];
+  for (int x0 = 0; x0 < W; x0 += kThreads) {
+    const int x = x0 + threadIdx.x;
+    const bool f = x < W && survivor(labels + base, stats + base, y * W + x, min_pixels);
+    int total;
+    const int slot = carry + block_scan(f, wsum, total);
+    carry += total;
+    if (f && slot < max_boxes) {                                      // the only store: slot in [0, max_boxes)
+      const Stats st = stats[base + y * W + x];
+      const int c0 = W - 1 - st.w1_minus_c0, c1 = st.c1, r0 = H - 1 - top[base + y * W + x], r1 = st.r1;      // a real maximum over the region's rows
+      const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;        // exact: multiples of 0.5 far below 2^23
+      const float xmin = ((float)c0 - hw) / 10.f, xmax = ((float)(c1 + 1) - hw) / 10.f;
+      const float ymin = (hh - (float)(r1 + 1)) / 10.f, ymax = (hh - (float)r0) / 10.f;
+      float* o = boxes + ((long)s * max_boxes + slot) * 8;
+      o[0] = xmax; o[1] = xmax; o[2] = xmin; o[3] = xmin;
+      o[4] = ymax; o[5] = ymin; o[6] = ymax; o[7] = ymin;
+    }
+  }
+}
+
 long align16(long v) { return (v + 15) & ~15L; }
 
 // ------------------------------------------------------------------------------------------------ b'. oriented boxes
@@ -360,15 +441,22 @@ __device__ __forceinline__ Obb* obb_record(const Stats* __restrict__ stats, Obb*
 }
 
 // run_stats_kernel's structure.  The run [x, x + len) of row y adds sum 1, X, Y, X^2, X Y, Y^2 in closed form (len <= 64: no overflow).
-__global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
-                                                              int H, int W, int min_pixels, int max_boxes) {
+template <bool kRegions>
+__device__ __forceinline__ void obb_moment_body(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs, int H, int W,
+                                                int min_pixels, int max_boxes) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
-  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
-  const unsigned long long mask = __ballot(v != 0);
-  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-  const unsigned long long inv = ~(mask >> lane);
-  const long long len = inv ? __ffsll((long long)inv) - 1 : 64;
+  int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  long long len;
+  if constexpr (kRegions) {
+    len = region_run(labels + base, H * W, v, lane);
+    if (len == 0) return;
+  } else {
+    const unsigned long long mask = __ballot(v != 0);
+    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+    const unsigned long long inv = ~(mask >> lane);
+    len = inv ? __ffsll((long long)inv) - 1 : 64;
+  }
   Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
   if (!r) return;
   const long long tri = len * (len - 1) / 2, sx = len * x + tri;
@@ -380,17 +468,34 @@ __global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restr
   atomicAdd((unsigned long long*)&r->syy, (unsigned long long)(len * y * y));
 }
 
+__global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
+  obb_moment_body<false>(labels, stats, recs, H, W, min_pixels, max_boxes);
+}
+
+__global__ __launch_bounds__(kThreads) void obb_region_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
+                                                                     Obb* __restrict__ recs, int H, int W, int min_pixels, int max_boxes) {
+  obb_moment_body<true>(labels, stats, recs, H, W, min_pixels, max_boxes);
+}
+
 // After the moment launch.  u = (X + .5) c + (Y + .5) s and v = -(X + .5) s + (Y + .5) c are monotone in X along a row (a rounded product
 // and a rounded sum are monotone in their operand), so the run's extremes are at its two end pixels.
-__global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
-                                                              int H, int W, int min_pixels, int max_boxes) {
+template <bool kRegions>
+__device__ __forceinline__ void obb_extent_body(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs, int H, int W,
+                                                int min_pixels, int max_boxes) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
-  const int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
-  const unsigned long long mask = __ballot(v != 0);
-  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-  const unsigned long long inv = ~(mask >> lane);
-  const int len = inv ? __ffsll((long long)inv) - 1 : 64;
+  int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
+  int len;
+  if constexpr (kRegions) {
+    len = region_run(labels + base, H * W, v, lane);
+    if (len == 0) return;
+  } else {
+    const unsigned long long mask = __ballot(v != 0);
+    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
+    const unsigned long long inv = ~(mask >> lane);
+    len = inv ? __ffsll((long long)inv) - 1 : 64;
+  }
   Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
   if (!r) return;
   double c, s;
@@ -401,6 +506,16 @@ __global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restr
   atomicMax(&r->neg_u0, code(-fmin(ua, ub)));
   atomicMax(&r->v1, code(fmax(va, vb)));
   atomicMax(&r->neg_v0, code(-fmin(va, vb)));
+}
+
+__global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
+  obb_extent_body<false>(labels, stats, recs, H, W, min_pixels, max_boxes);
+}
+
+__global__ __launch_bounds__(kThreads) void obb_region_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
+                                                                     Obb* __restrict__ recs, int H, int W, int min_pixels, int max_boxes) {
+  obb_extent_body<true>(labels, stats, recs, H, W, min_pixels, max_boxes);
 }
 
 // one thread per stored box: extents moved outwards by pad (|c| + |s|), the ring (u1,v1), (u1,v0), (u0,v0), (u0,v1) rotated back to
@@ -433,6 +548,138 @@ __global__ __launch_bounds__(kThreads) void obb_emit_kernel(const Obb* __restric
 
 bool obb_shape_ok(int batch, int H, int W, int max_boxes) {
   return batch >= 1 && batch <= kMaxBatch && H >= 1 && W >= 1 && H <= kObbMaxSide && W <= kObbMaxSide && max_boxes >= 1 && max_boxes <= kObbMaxBoxes;
+}
+
+// ------------------------------------------------------------------------------------------------ b''. splitting by markers
+constexpr int kErodeSide = kTile + 2 * kMaxSplit;      // 48
+constexpr int kGrowSide = kTile + 2 * kMaxGrow;        // 64
+
+// core[p] = 1.f iff the (2r+1)^2 square round p lies in `maps > threshold` (outside the image: background), else 0.f -- the float map
+// that a.'s launches label with threshold 0.5.  One workgroup per 32x32 tile: the tile with a halo of r as bytes in LDS, then the
+// minimum (AND) over 2r+1 columns, then over 2r+1 rows.  Every LDS index is below side * side <= 48 * 48.
+__global__ __launch_bounds__(kThreads) void erode_kernel(const float* __restrict__ maps, float threshold, float* __restrict__ core, int H, int W, int r) {
+  __shared__ unsigned char in[kErodeSide * kErodeSide];
+  __shared__ unsigned char row[kErodeSide * kTile];
+  const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile, side = kTile + 2 * r;
+  const long base = (long)blockIdx.z * H * W;
+  for (int i = threadIdx.x; i < side * side; i += kThreads) {         // at most 9 rounds
+    const int y = y0 - r + i / side, x = x0 - r + i % side;
+    in[i] = y >= 0 && y < H && x >= 0 && x < W && maps[base + (long)y * W + x] > threshold;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < side * kTile; i += kThreads) {        // at most 6 rounds
+    const int ly = i / kTile, lx = i % kTile;
+    unsigned char a = 1;
+    for (int d = 0; d <= 2 * r; ++d) a &= in[ly * side + lx + d];     // lx + d <= 31 + 2r < side
+    row[i] = a;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kTilePix / kThreads; ++k) {
+    const int i = threadIdx.x + kThreads * k;
+    const int ly = i / kTile, lx = i % kTile, y = y0 + ly, x = x0 + lx;
+    if (y >= H || x >= W) continue;
+    unsigned char a = 1;
+    for (int d = 0; d <= 2 * r; ++d) a &= row[(ly + d) * kTile + lx]; // ly + d <= 31 + 2r < side
+    core[base + (long)y * W + x] = a ? 1.f : 0.f;
+  }
+}
+
+// g synchronous rounds of growth inside the mask, from `seeds` (the labels of the cores) to `out`; `rest` = 1.f where a mask pixel is
+// still unlabelled (what a.'s launches label next), else 0.f.  One workgroup per 32x32 tile: labels and mask of the tile with a halo of g
+// in LDS, then g rounds from one label buffer to the other with one barrier each.  A pixel at distance d from the edge of the loaded
+// square is right after round k whenever d >= k (its value depends on the pixels within Chebyshev distance k only, and those within the
+// square are all loaded); the centre has d >= g.  The smallest label among the 8 neighbours wins: the result does not depend on the
+// order in which anything runs.  Plain LDS reads and writes; nothing waits for another workgroup.
+__global__ __launch_bounds__(kThreads) void grow_kernel(const float* __restrict__ maps, float threshold, const int* __restrict__ seeds,
+                                                        int* __restrict__ out, float* __restrict__ rest, int H, int W, int g) {
+  __shared__ int buf[2][kGrowSide * kGrowSide];
+  __shared__ unsigned char msk[kGrowSide * kGrowSide];
+  const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile, side = kTile + 2 * g, cells = side * side;
+  const long base = (long)blockIdx.z * H * W;
+  for (int i = threadIdx.x; i < cells; i += kThreads) {               // at most 16 rounds
+    const int y = y0 - g + i / side, x = x0 - g + i % side;
+    const bool in = y >= 0 && y < H && x >= 0 && x < W;
+    const bool m = in && maps[base + (long)y * W + x] > threshold;
+    msk[i] = m;
+    buf[0][i] = m ? seeds[base + (long)y * W + x] : 0;
+  }
+  __syncthreads();
+  for (int round = 0; round < g; ++round) {                           // g <= 16, uniform: every thread reaches every barrier
+    const int* src = buf[round & 1];
+    int* dst = buf[(round & 1) ^ 1];
+    for (int i = threadIdx.x; i < cells; i += kThreads) {
+      int l = src[i];
+      if (l == 0 && msk[i]) {
+        const int ly = i / side, lx = i % side;
+        unsigned best = ~0u;                                          // label - 1 as unsigned: 0 (no label) becomes the largest value
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+          for (int dx = -1; dx <= 1; ++dx) {
+            const int ny = ly + dy, nx = lx + dx;
+            if ((dy || dx) && ny >= 0 && ny < side && nx >= 0 && nx < side) best = min(best, (unsigned)src[ny * side + nx] - 1u);
+          }
+        l = (int)(best + 1u);
+      }
+      dst[i] = l;
+    }
+    __syncthreads();
+  }
+  const int* fin = buf[g & 1];
+#pragma unroll
+  for (int k = 0; k < kTilePix / kThreads; ++k) {
+    const int i = threadIdx.x + kThreads * k;
+    const int ly = i / kTile, lx = i % kTile, y = y0 + ly, x = x0 + lx;
+    if (y >= H || x >= W) continue;
+    const int c = (ly + g) * side + lx + g;
+    out[base + (long)y * W + x] = fin[c];
+    rest[base + (long)y * W + x] = (msk[c] && fin[c] == 0) ? 1.f : 0.f;
+  }
+}
+
+// the grown regions and the labelled leftovers are disjoint: take whichever is there
+__global__ __launch_bounds__(kThreads) void merge_labels_kernel(int* __restrict__ labels, const int* __restrict__ rest, long n) {
+  const long p = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (p < n && labels[p] == 0) labels[p] = rest[p];
+}
+
+bool split_ok(int split_px, int grow_iters) { return split_px >= 1 && split_px <= kMaxSplit && grow_iters >= 0 && grow_iters <= kMaxGrow; }
+
+// the launches that fit a label image: shared by dd_labelled_boxes and dd_labelled_obb up to the row scan
+struct RegionWs {
+  Stats* stats;
+  int *top, *rowcnt, *rowbase;
+  Obb* recs;
+};
+
+long region_ws_bytes(int batch, int H, int W) {
+  const long n = (long)batch * H * W;
+  return n * (long)sizeof(Stats) + align16(n * (long)sizeof(int)) + 2 * align16((long)batch * H * (long)sizeof(int));
+}
+
+RegionWs region_ws(void* workspace, int batch, int H, int W) {
+  const long n = (long)batch * H * W;
+  RegionWs r;
+  r.stats = (Stats*)workspace;
+  r.top = (int*)((char*)r.stats + n * (long)sizeof(Stats));
+  r.rowcnt = (int*)((char*)r.top + align16(n * (long)sizeof(int)));
+  r.rowbase = (int*)((char*)r.rowcnt + align16((long)batch * H * (long)sizeof(int)));
+  r.recs = (Obb*)((char*)r.rowbase + align16((long)batch * H * (long)sizeof(int)));
+  return r;
+}
+
+int region_count_launch(const int* labels, const RegionWs& ws, int* counts, int min_pixels, int batch, int H, int W, hipStream_t st) {
+  const int n = H * W;
+  hipLaunchKernelGGL(region_init_kernel, dim3((n + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, labels, ws.stats, ws.top, n);
+  DD_LAUNCH_CHECK("labelled boxes init");
+  hipLaunchKernelGGL(region_stats_kernel, dim3((W + 63) / 64, (H + 3) / 4, batch), dim3(64, 4), 0, st, labels, ws.stats, ws.top, H, W);
+  DD_LAUNCH_CHECK("labelled boxes stats");
+  hipLaunchKernelGGL(row_count_kernel, dim3(H, batch), dim3(kThreads), 0, st, labels, (const Stats*)ws.stats, ws.rowcnt, H, W, min_pixels);
+  DD_LAUNCH_CHECK("labelled boxes row counts");
+  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, (const int*)ws.rowcnt, ws.rowbase, counts, H);
+  DD_LAUNCH_CHECK("labelled boxes row scan");
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ c. IoU and ATS
@@ -683,6 +930,106 @@ int dd_component_obb(const float* maps, float threshold, int32_t min_pixels, int
   hipLaunchKernelGGL(obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, recs, counts, pad_px, boxes,
                      (long long*)moments, height, width, max_boxes);
   DD_LAUNCH_CHECK("component_obb emit");
+  return 0;
+}
+
+int64_t dd_split_components_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t split_px, int32_t grow_iters) {
+  if (!shape_ok(batch, height, width) || !split_ok(split_px, grow_iters)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "split_components: batch in [1,%d], height and width in [1,%d], split_px in [1,%d], grow_iters in [0,%d] (got "
+            "%d x %d x %d, split_px %d, grow_iters %d)", kMaxBatch, kMaxSide, kMaxSplit, kMaxGrow, batch, height, width, split_px, grow_iters);
+    return -1;
+  }
+  return 2 * align16((long)batch * height * width * 4);      // one float map (cores, then leftovers) and one label image
+}
+
+int dd_split_components(const float* maps, float threshold, int32_t split_px, int32_t grow_iters, int32_t* labels, int32_t batch, int32_t height,
+                        int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(maps && labels && workspace, DD_ERR_BAD_ARG, "split_components: null pointer");
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "split_components: workspace must be 16-byte aligned");
+  const int64_t need = dd_split_components_workspace_bytes(batch, height, width, split_px, grow_iters);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "split_components: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)need);
+  const long n = (long)batch * height * width;
+  float* fmap = (float*)workspace;
+  int* tmp = (int*)((char*)workspace + align16(n * 4));
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 tiles((width + kTile - 1) / kTile, (height + kTile - 1) / kTile, batch);
+  hipLaunchKernelGGL(erode_kernel, tiles, dim3(kThreads), 0, st, maps, threshold, fmap, height, width, split_px);
+  DD_LAUNCH_CHECK("split_components erode");
+  int rc = label_launch(fmap, 0.5f, tmp, nullptr, batch, height, width, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(grow_kernel, tiles, dim3(kThreads), 0, st, maps, threshold, (const int*)tmp, labels, fmap, height, width, grow_iters);
+  DD_LAUNCH_CHECK("split_components grow");
+  rc = label_launch(fmap, 0.5f, tmp, nullptr, batch, height, width, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(merge_labels_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, labels, (const int*)tmp, n);
+  DD_LAUNCH_CHECK("split_components merge");
+  return 0;
+}
+
+int64_t dd_labelled_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
+  if (!shape_ok(batch, height, width)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "labelled_boxes: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", kMaxBatch, kMaxSide, batch,
+            height, width);
+    return -1;
+  }
+  return region_ws_bytes(batch, height, width);
+}
+
+int dd_labelled_boxes(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch, int32_t height,
+                      int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(labels && boxes && counts && workspace, DD_ERR_BAD_ARG, "labelled_boxes: null pointer");
+  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "labelled_boxes: min_pixels and max_boxes must be positive");
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "labelled_boxes: workspace must be 16-byte aligned");
+  const int64_t need = dd_labelled_boxes_workspace_bytes(batch, height, width);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "labelled_boxes: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)need);
+  const RegionWs ws = region_ws(workspace, batch, height, width);
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = region_count_launch(labels, ws, counts, min_pixels, batch, height, width, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(emit_region_boxes_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, (const Stats*)ws.stats, (const int*)ws.top,
+                     (const int*)ws.rowcnt, (const int*)ws.rowbase, boxes, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("labelled_boxes emit");
+  return 0;
+}
+
+int64_t dd_labelled_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes) {
+  if (!obb_shape_ok(batch, height, width, max_boxes)) {
+    dd_fail(DD_ERR_UNSUPPORTED, "labelled_obb: batch in [1,%d], height and width in [1,%d] (the second moments are exact in 64-bit integers up to "
+            "there), max_boxes in [1,%d] (got %d x %d x %d, max_boxes %d)", kMaxBatch, kObbMaxSide, kObbMaxBoxes, batch, height, width, max_boxes);
+    return -1;
+  }
+  return region_ws_bytes(batch, height, width) + (long)batch * max_boxes * (long)sizeof(Obb);
+}
+
+int dd_labelled_obb(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts, int64_t* moments,
+                    int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
+  DD_REQUIRE(labels && boxes && counts && workspace, DD_ERR_BAD_ARG, "labelled_obb: null pointer");
+  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "labelled_obb: min_pixels and max_boxes must be positive");
+  DD_REQUIRE(pad_px >= 0.f && pad_px <= (float)kObbMaxSide, DD_ERR_BAD_ARG, "labelled_obb: pad_px must lie in [0,%d]", kObbMaxSide);
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "labelled_obb: workspace must be 16-byte aligned");
+  const int64_t need = dd_labelled_obb_workspace_bytes(batch, height, width, max_boxes);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "labelled_obb: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+             (long long)need);
+  const RegionWs ws = region_ws(workspace, batch, height, width);
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = region_count_launch(labels, ws, counts, min_pixels, batch, height, width, st);
+  if (rc) return rc;
+  const dim3 runs((width + 63) / 64, (height + 3) / 4, batch);
+  hipLaunchKernelGGL(obb_slot_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, ws.stats, (const int*)ws.rowcnt, (const int*)ws.rowbase,
+                     ws.recs, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("labelled_obb slots");
+  hipLaunchKernelGGL(obb_region_moment_kernel, runs, dim3(64, 4), 0, st, labels, (const Stats*)ws.stats, ws.recs, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("labelled_obb moments");
+  hipLaunchKernelGGL(obb_region_extent_kernel, runs, dim3(64, 4), 0, st, labels, (const Stats*)ws.stats, ws.recs, height, width, min_pixels, max_boxes);
+  DD_LAUNCH_CHECK("labelled_obb extents");
+  hipLaunchKernelGGL(obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, (const Obb*)ws.recs, (const int*)counts,
+                     pad_px, boxes, (long long*)moments, height, width, max_boxes);
+  DD_LAUNCH_CHECK("labelled_obb emit");
   return 0;
 }
 

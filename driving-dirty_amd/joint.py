@@ -47,10 +47,10 @@ class JointRoadMapBBox(LightningModule):
         logits = ops.linear(z, self.fc1.weight, self.fc1.bias).reshape(-1, 800, 800)
         return logits, boxes
 
-    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5):
+    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
         """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4]."""
         with torch.no_grad():
-            return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px)
+            return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
     def training_step(self, batch, batch_idx):
         sample, target, road_image = batch

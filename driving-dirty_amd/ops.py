@@ -210,7 +210,66 @@ def label_components(maps, threshold=0.5):
     return labels
 
 
-def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False):
+def _split_args(split_px, grow_iters, who):
+    """(split_px, grow_iters) as ints, ``grow_iters=None`` meaning ``2 * split_px``; anything that is no whole number is refused."""
+    for name, v in (("split_px", split_px), ("grow_iters", grow_iters)):
+        if not (v is None and name == "grow_iters") and (isinstance(v, bool) or int(v) != v):
+            raise ValueError(f"{who}: {name} must be a whole number, got {v!r}")
+    split_px = int(split_px)
+    return split_px, 2 * split_px if grow_iters is None else int(grow_iters)
+
+
+def split_components(maps, threshold=0.5, split_px=4, grow_iters=None):
+    """fp32 maps [B,H,W] -> int32 labels [B,H,W]: ``maps > threshold`` partitioned into regions by marker-based splitting, which takes
+    apart blobs that are joined through a neck narrower than ``2 * split_px + 1`` pixels (two cars in contact).  Erode by ``split_px``,
+    label the cores, grow them back inside the mask for ``grow_iters`` synchronous rounds (default ``2 * split_px``; the smallest
+    neighbouring label wins), label what is left as components of its own (include/dd_hotpath.h states the rule).  A label minus 1 is
+    some pixel of its region, not necessarily the first.  ``split_px`` in [1,8], ``grow_iters`` in [0,16].  Integer only: deterministic."""
+    b, h, w = _maps(maps, "split_components")
+    split_px, grow_iters = _split_args(split_px, grow_iters, "split_components")
+    nbytes = _lib.lib().dd_split_components_workspace_bytes(b, h, w, split_px, grow_iters)
+    if nbytes < 0:
+        raise _lib.HotpathError(f"split_components: {_lib.lib().dd_last_error().decode()}")
+    labels = torch.empty((b, h, w), device=maps.device, dtype=torch.int32)
+    ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
+    check(_lib.lib().dd_split_components(_p(maps), float(threshold), split_px, grow_iters, _p(labels), b, h, w, _p(ws), nbytes, _stream()),
+          "dd_split_components")
+    return labels
+
+
+def labelled_boxes(labels, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False):
+    """``component_boxes`` for regions given as an int32 label image [B,H,W] (``split_components``' or ``label_components``' output: the
+    pixels of one label L form a region, and pixel L - 1 carries L).  Same survivors, order, counts, formats and roundings."""
+    if fit not in ("extent", "oriented"):
+        raise ValueError(f"labelled_boxes: fit must be 'extent' or 'oriented', got {fit!r}")
+    if want_moments and fit != "oriented":
+        raise ValueError("labelled_boxes: want_moments needs fit='oriented' (the extent fit forms no moments)")
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
+        raise _lib.HotpathError(f"labelled_boxes: expected int32 labels [B,H,W], got {getattr(labels, 'dtype', None)} "
+                                f"{tuple(getattr(labels, 'shape', ()))}")
+    if not labels.is_cuda or not labels.is_contiguous():
+        raise _lib.HotpathError("labelled_boxes: labels must be a contiguous GPU tensor (there is no CPU fallback)")
+    if int(min_pixels) < 1 or int(max_boxes) < 1:
+        raise _lib.HotpathError("labelled_boxes: min_pixels and max_boxes must be positive")
+    b, h, w = labels.shape
+    lib = _lib.lib()
+    nbytes = lib.dd_labelled_obb_workspace_bytes(b, h, w, int(max_boxes)) if fit == "oriented" else lib.dd_labelled_boxes_workspace_bytes(b, h, w)
+    if b == 0 or nbytes < 0:
+        raise _lib.HotpathError(f"labelled_boxes: unsupported shape {tuple(labels.shape)}: {lib.dd_last_error().decode()}")
+    boxes = torch.zeros((b, int(max_boxes), 2, 4), device=labels.device, dtype=torch.float32)
+    counts = torch.empty((b,), device=labels.device, dtype=torch.int32)
+    ws = torch.empty(nbytes, device=labels.device, dtype=torch.uint8)
+    if fit == "oriented":
+        moments = torch.zeros((b, int(max_boxes), 6), device=labels.device, dtype=torch.int64) if want_moments else None
+        check(lib.dd_labelled_obb(_p(labels), int(min_pixels), int(max_boxes), float(pad_px), _p(boxes), _p(counts), _p(moments), b, h, w,
+                                  _p(ws), nbytes, _stream()), "dd_labelled_obb")
+        return (boxes, counts, moments) if want_moments else (boxes, counts)
+    check(lib.dd_labelled_boxes(_p(labels), int(min_pixels), int(max_boxes), _p(boxes), _p(counts), b, h, w, _p(ws), nbytes, _stream()),
+          "dd_labelled_boxes")
+    return boxes, counts
+
+
+def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False, split_px=0, grow_iters=None):
     """fp32 maps [B,H,W] -> (boxes fp32 [B,max_boxes,2,4], counts int32 [B]): one box for each component of ``maps > threshold`` with
     at least ``min_pixels`` pixels, in the data set's box format (metres, ego at the centre: the inverse of
     ``boxes_to_binary_map``'s pixel mapping), ordered by component label.  ``counts`` is the UNCAPPED number of such components:
@@ -221,11 +280,18 @@ def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="exten
     0.5 = the support of the pixel squares, 0 = the hull of the centres; include/dd_hotpath.h states the fit).  Same components, same
     order, same counts; sides up to 1024.  A principal-axis fit, not a minimum-area rectangle (for a filled rectangle the two agree);
     which end of the box is its front is arbitrary.  ``want_moments`` (oriented only) also returns int64 [B,max_boxes,6]:
-    N, Sx, Sy, Sxx, Sxy, Syy of each stored box."""
+    N, Sx, Sy, Sxx, Sxy, Syy of each stored box.
+
+    ``split_px > 0``: the boxes are fitted to the regions of ``split_components(maps, threshold, split_px, grow_iters)`` instead of to the
+    components (touching cars joined through a neck come apart; ``grow_iters=None`` = ``2 * split_px``).  ``split_px = 0``, the default,
+    launches nothing new and changes no output."""
     if fit not in ("extent", "oriented"):
         raise ValueError(f"component_boxes: fit must be 'extent' or 'oriented', got {fit!r}")
     if want_moments and fit != "oriented":
         raise ValueError("component_boxes: want_moments needs fit='oriented' (the extent fit forms no moments)")
+    split_px, grow_iters = _split_args(split_px, grow_iters, "component_boxes")
+    if split_px != 0:
+        return labelled_boxes(split_components(maps, threshold, split_px, grow_iters), min_pixels, max_boxes, fit, pad_px, want_moments)
     b, h, w = _maps(maps, "component_boxes")
     if int(min_pixels) < 1 or int(max_boxes) < 1:
         raise _lib.HotpathError("component_boxes: min_pixels and max_boxes must be positive")

@@ -135,10 +135,13 @@ def compute_ats_bounding_boxes(boxes1, boxes2):
     return ops.ats_bounding_boxes([boxes1], [boxes2])[0]
 
 
-def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5):
+def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
     """[b,H,W] occupancy maps -> tuple of b [n_i,2,4] box tensors (``ops.component_boxes`` cut to each sample's count).
-    ``fit="oriented"`` fits each component along its principal axis instead of taking its axis-aligned extent."""
-    boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes, fit=fit, pad_px=pad_px)
+    ``fit="oriented"`` fits each component along its principal axis instead of taking its axis-aligned extent.  ``split_px > 0`` first
+    splits blobs joined through a neck narrower than ``2 * split_px + 1`` pixels (``ops.split_components``; ``grow_iters=None`` =
+    ``2 * split_px``)."""
+    boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes, fit=fit, pad_px=pad_px,
+                                        split_px=split_px, grow_iters=grow_iters)
     counts = counts.tolist()
     over = [i for i, c in enumerate(counts) if c > max_boxes]
     if over:
@@ -219,12 +222,13 @@ class BBSpatialRoadMap(LightningModule):
         train_loss, _, _ = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
-    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5):
+    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
         """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
         [n_i,2,4] in the data set's format.  A sample with more than ``max_boxes`` components is cut there, with a warning.
-        ``fit="oriented"``: rotated rectangles along each component's principal axis (which end is the front is arbitrary)."""
+        ``fit="oriented"``: rotated rectangles along each component's principal axis (which end is the front is arbitrary).
+        ``split_px > 0``: touching cars joined through a neck are split first (``ops.split_components``)."""
         with torch.no_grad():
-            return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px)
+            return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
     def validation_step(self, batch, batch_idx):
         val_loss, target_bb_img, pred_bb_img = self._run_step(batch, batch_idx, step_name="valid")
@@ -236,7 +240,8 @@ class BBSpatialRoadMap(LightningModule):
                 if missing:
                     raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
                 pred = pred_bb_img.detach().reshape(-1, 800, 800).contiguous()
-                fitted = boxes_from_map(pred, fit=hparam(self.hparams, "box_fit", "extent"), pad_px=hparam(self.hparams, "box_pad_px", 0.5))
+                fitted = boxes_from_map(pred, fit=hparam(self.hparams, "box_fit", "extent"), pad_px=hparam(self.hparams, "box_pad_px", 0.5),
+                                        split_px=hparam(self.hparams, "box_split_px", 0), grow_iters=hparam(self.hparams, "box_grow_iters", None))
                 out["val_ats"] = ops.ats_bounding_boxes(fitted, [t["bounding_box"] for t in batch[1]]).mean()
                 out["val_ts"] = ops.threat_score(target_bb_img.contiguous(), pred_bb_img.detach().contiguous(), round_b=True)
         return out
@@ -267,6 +272,11 @@ class BBSpatialRoadMap(LightningModule):
                             "along its principal axis (the data set's boxes are rotated)")
         p.add_argument("--box_pad_px", type=float, default=0.5,
                        help="oriented fit: pixels added on each side of the pixel centres' extents (0.5 = the pixel squares, 0 = the centres)")
+        p.add_argument("--box_split_px", type=int, default=0,
+                       help="box_metrics: split blobs joined through a neck narrower than 2 * box_split_px + 1 pixels before fitting "
+                            "(touching cars); 0 = off, at most 8")
+        p.add_argument("--box_grow_iters", type=int, default=None,
+                       help="box_metrics with --box_split_px: rounds the eroded cores grow back inside the map (default 2 * box_split_px, at most 16)")
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)

@@ -609,6 +609,41 @@ int64_t dd_component_obb_workspace_bytes(int32_t batch, int32_t height, int32_t 
 int dd_component_obb(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts,
                      int64_t* moments, int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Marker-based splitting of blobs that are joined through a neck (two cars in contact at a corner, T-, L- and X-shaped overlaps,
+ * lengthwise-shifted neighbours): a label image int32 [batch,height,width] that partitions `mask = maps > threshold` into regions.
+ * For one sample, r = split_px in [1,8], g = grow_iters in [0,16]:
+ *   1. ERODE.  core[p] = 1 iff every pixel of the (2r+1) x (2r+1) square centred on p is in the mask; pixels outside the image count
+ *      as background.
+ *   2. LABEL THE CORES.  The 4-connected components of core with the labels of dd_label_components: 1 + the raster index of the
+ *      component's first pixel.
+ *   3. GROW.  g synchronous rounds, each reading only the image of the round before: every mask pixel with label 0 that has at least
+ *      one labelled pixel among its 8 neighbours takes the SMALLEST such label.  Independent of scheduling by construction.
+ *   4. LEFTOVERS.  The mask pixels that are still 0 (blobs too thin to have a core, tips that g rounds did not reach) are labelled as
+ *      the 4-connected components of the leftover set, again 1 + the raster index of the component's first leftover pixel.
+ * A label minus 1 is always a pixel of its own region and the regions are disjoint, so labels are unique across both kinds.  The
+ * pixel label - 1 is NOT necessarily the region's first pixel in raster order.  A blob joined through a neck narrower than 2r+1
+ * pixels falls apart; two cars that share a whole edge form one fat rectangle, which no erosion separates.  Integer only: the same
+ * bytes from launch to launch, and a sample's labels do not depend on the rest of the batch.
+ * Anything outside the limits on split_px and grow_iters is refused: the query returns -1, the call DD_ERR_UNSUPPORTED, with the
+ * limits in the message.  Shapes as dd_label_components.  workspace: 16-byte aligned, 8 bytes per pixel. */
+int64_t dd_split_components_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t split_px, int32_t grow_iters);
+int dd_split_components(const float* maps, float threshold, int32_t split_px, int32_t grow_iters, int32_t* labels, int32_t batch, int32_t height,
+                        int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* dd_component_boxes / dd_component_obb for regions given as a LABEL IMAGE (dd_split_components' or dd_label_components' output): a
+ * region = the pixels of one label L > 0, where pixel L - 1 of the sample carries L itself (any pixel of the region, not necessarily
+ * its first).  Regions need not be connected; horizontally adjacent pixels with different labels belong to different regions.  The
+ * same survivor rule (min_pixels), order (by label), uncapped counts, corner formats and roundings as the two entry points above, and
+ * on the output of dd_label_components the same bytes.  A label outside [1, height*width], or one whose pixel L - 1 does not carry
+ * L, belongs to no region and is ignored.  labels is only read.  workspace: 16-byte aligned; dd_labelled_boxes_workspace_bytes is
+ * 20 bytes per pixel, dd_labelled_obb_workspace_bytes adds 80 bytes per box slot; limits as dd_component_boxes / dd_component_obb. */
+int64_t dd_labelled_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+int dd_labelled_boxes(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch, int32_t height,
+                      int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t dd_labelled_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes);
+int dd_labelled_obb(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts, int64_t* moments,
+                    int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Pairwise IoU and the average threat score of two box lists per sample.  boxes1 / boxes2 = the samples' [n,2,4] corner tensors
  * concatenated on the DEVICE (dtype 0 = f64, 1 = f32), offsets1 / offsets2 = HOST arrays of batch+1 box indices, the convention of
  * dd_boxes_to_binary_map; at most 4096 boxes per sample and set (more: DD_ERR_UNSUPPORTED).
