@@ -156,9 +156,11 @@ SIGNATURES = {
     "dd_linear_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dd_linear_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "dd_linear_dgrad": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "dd_linear_sigmoid_gt": (_i32, [_p, _p, _p, _f32, _p, _i32, _i32, _i32, _p]),
     "dd_linear_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
     "dd_threat_score_workspace_bytes": (_i64, []),
     "dd_threat_score": (_i32, [_p, _p, _p, _i64, _i32, _p, _p]),
+    "dd_ts_hist": (_i32, [_p, _p, _i32, _i64, _i32, _p, _p]),
     "dd_label_components_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "dd_label_components": (_i32, [_p, _f32, _p, _i32, _i32, _i32, _p]),
     "dd_component_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),

@@ -113,3 +113,18 @@ __device__ __forceinline__ void dd_barrier_lds() { asm volatile("s_waitcnt lgkmc
 // Barrier behind LDS-DMA fills: they must have landed (vmcnt) before the barrier publishes the buffer; the LDS reads of this step
 // are done (lgkmcnt).
 __device__ __forceinline__ void dd_barrier_dma() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// sigmoid(z) and softplus(-|z|) = log1p(exp(-|z|)) from the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32,
+// 1 ulp each) instead of libm's expf + log1pf + IEEE divisions: 145 -> ~25 instructions per element, which is what
+// made the loss pass compute-bound (87 us for 184 MB).  log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e) undoes the
+// rounding of 1 + e (u - 1 is exact); one Newton step on the reciprocal keeps sigmoid within 1 ulp.
+// Here because it is the ONE sigmoid of the dense head: dd_sigmoid, the BCE pass (dense.hip) and dd_linear_sigmoid_gt (linear.hip) all
+// take theirs from it, so their probabilities agree bit for bit.
+__device__ __forceinline__ void dd_sigmoid_softplus(float z, float& sig, float& l1p) {
+  const float e = __builtin_amdgcn_exp2f(-fabsf(z) * 1.4426950408889634f);      // in [0, 1]; flushes to 0 below 2^-126
+  const float u = 1.f + e, d = u - 1.f;
+  float r = __builtin_amdgcn_rcpf(u);
+  r = fmaf(r, fmaf(-u, r, 1.f), r);
+  sig = z >= 0.f ? r : e * r;
+  l1p = d == 0.f ? e : (__builtin_amdgcn_logf(u) * 0.6931471805599453f) * (e * __builtin_amdgcn_rcpf(d));
+}

@@ -276,19 +276,6 @@ __device__ __forceinline__ f32x4 load_target4<unsigned char>(const unsigned char
   return f32x4{(float)(w & 0xff), (float)((w >> 8) & 0xff), (float)((w >> 16) & 0xff), (float)(w >> 24)};
 }
 
-// sigmoid(z) and softplus(-|z|) = log1p(exp(-|z|)) from the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32,
-// 1 ulp each) instead of libm's expf + log1pf + IEEE divisions: 145 -> ~25 instructions per element, which is what
-// made the loss pass compute-bound (87 us for 184 MB).  log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e) undoes the
-// rounding of 1 + e (u - 1 is exact); one Newton step on the reciprocal keeps sigmoid within 1 ulp.
-__device__ __forceinline__ void sigmoid_softplus(float z, float& sig, float& l1p) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(z) * 1.4426950408889634f);      // in [0, 1]; flushes to 0 below 2^-126
-  const float u = 1.f + e, d = u - 1.f;
-  float r = __builtin_amdgcn_rcpf(u);
-  r = fmaf(r, fmaf(-u, r, 1.f), r);
-  sig = z >= 0.f ? r : e * r;
-  l1p = d == 0.f ? e : (__builtin_amdgcn_logf(u) * 0.6931471805599453f) * (e * __builtin_amdgcn_rcpf(d));
-}
-
 // The road masks as the collate hands them over: a TUPLE of per-sample bool tensors (helper.py:22-23), which the reference
 // stacks (and casts) first (roadmap_bce_v2.py:87).  Reading through a table of per-sample pointers skips that copy.
 struct MaskPtrs {
@@ -307,7 +294,7 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float sig, l1p;
-      sigmoid_softplus(zv[k], sig, l1p);
+      dd_sigmoid_softplus(zv[k], sig, l1p);
       s += fmaxf(zv[k], 0.f) - zv[k] * tv[k] + l1p;
       p[k] = sig;
       g[k] = (sig - tv[k]) * gscale;
@@ -319,7 +306,7 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float* __restrict
     const long i = 4 * n4 + threadIdx.x;
     const float ti = (float)t[i];
     float sig, l1p;
-    sigmoid_softplus(z[i], sig, l1p);
+    dd_sigmoid_softplus(z[i], sig, l1p);
     s += fmaxf(z[i], 0.f) - z[i] * ti + l1p;
     if (dz) dz[i] = (sig - ti) * gscale;
     if (probs) probs[i] = sig;
@@ -342,7 +329,7 @@ __global__ __launch_bounds__(256) void bce_logits_ptrs_kernel(const float* __res
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float sig, l1p;
-      sigmoid_softplus(zv[k], sig, l1p);
+      dd_sigmoid_softplus(zv[k], sig, l1p);
       s += fmaxf(zv[k], 0.f) - zv[k] * tv[k] + l1p;
       p[k] = sig;
       g[k] = (sig - tv[k]) * gscale;
@@ -372,7 +359,7 @@ __global__ __launch_bounds__(256) void sigmoid_kernel(const f32x4* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float sg, l1p;
-      sigmoid_softplus(v[k], sg, l1p);
+      dd_sigmoid_softplus(v[k], sg, l1p);
       o[k] = sg;
     }
     p[i] = o;

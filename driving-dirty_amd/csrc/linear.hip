@@ -19,11 +19,13 @@ constexpr int NTD = 32;         // n-chunk of the dgrad kernel
 
 // ---------------------------------------------------------------------------------------------- forward
 // grid (ceil(N/128), ksplit); 4 waves, wave w owns output columns [nb*128 + 32w, +32); MT M-tiles of 32 rows.
-template <int MT>
-__global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
-                                                         const float* __restrict__ bias, float* __restrict__ Y,
-                                                         float* __restrict__ part, int M, int N, int K,
-                                                         int tiles_per_split) {
+// The body of two kernels: linear_fwd_kernel (GT = false) stores y into Y (or its split-K partial into `part`);
+// linear_sigmoid_gt_kernel (GT = true, ksplit = 1) runs the same tiles and the same contraction and stores sigmoid(y) > tau as one
+// byte per element into Y8.
+template <int MT, bool GT>
+__device__ __forceinline__ void linear_fwd_body(const float* __restrict__ X, const float* __restrict__ Wt, const float* __restrict__ bias,
+                                                float* __restrict__ Y, float* __restrict__ part, int M, int N, int K, int tiles_per_split,
+                                                unsigned char* __restrict__ Y8, float tau) {
   __shared__ __attribute__((aligned(16))) float wl[128 * WROW];
   __shared__ __attribute__((aligned(16))) float xl[MT * 32 * WROW];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -85,14 +87,57 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict
   const int n = n0 + wave * 32 + r;
   const bool direct = gridDim.y == 1;
   const float bv = (direct && bias && n < N) ? bias[n] : 0.f;
-  float* dst = direct ? Y : part + (long)blockIdx.y * M * N;
+  if constexpr (GT) {
+    // The accumulators hold one column per lane; the map is row-major bytes.  The block's MT*32 x 128 byte tile is put together in
+    // LDS (the operand tiles are done with: the loop ends on a barrier) and leaves as 16-byte stores, a row's 128 bytes from 8 lanes.
+    unsigned char* tile = (unsigned char*)wl;
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
+    for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int m = mt * 32 + dd_acc_row(i, lane);
-      if (m < M && n < N) dst[(long)m * N + n] = acc[mt][i] + bv;
+      for (int i = 0; i < 16; ++i) {
+        float sig, l1p;
+        dd_sigmoid_softplus(acc[mt][i] + bv, sig, l1p);
+        tile[(mt * 32 + dd_acc_row(i, lane)) * 128 + wave * 32 + r] = sig > tau;
+      }
+    __syncthreads();
+    const bool vec = N % 16 == 0 && (uintptr_t)Y8 % 16 == 0;      // then a 16-byte piece is aligned, and all inside a row or all outside
+    const int c = (tid & 7) * 16;
+#pragma unroll
+    for (int p = 0; p < MT; ++p) {
+      const int m = p * 32 + (tid >> 3);
+      if (m >= M || n0 + c >= N) continue;
+      unsigned char* dst8 = Y8 + (long)m * N + n0 + c;
+      if (vec) {
+        *(u32x4*)dst8 = *(const u32x4*)(tile + m * 128 + c);
+      } else {
+        for (int j = 0; j < min(16, N - n0 - c); ++j) dst8[j] = tile[m * 128 + c + j];
+      }
     }
+  } else {
+    float* dst = direct ? Y : part + (long)blockIdx.y * M * N;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int m = mt * 32 + dd_acc_row(i, lane);
+        if (m < M && n < N) dst[(long)m * N + n] = acc[mt][i] + bv;
+      }
+  }
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
+                                                         const float* __restrict__ bias, float* __restrict__ Y,
+                                                         float* __restrict__ part, int M, int N, int K,
+                                                         int tiles_per_split) {
+  linear_fwd_body<MT, false>(X, Wt, bias, Y, part, M, N, K, tiles_per_split, nullptr, 0.f);
+}
+
+template <int MT>
+__global__ __launch_bounds__(256) void linear_sigmoid_gt_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
+                                                                const float* __restrict__ bias, unsigned char* __restrict__ Y8, float tau,
+                                                                int M, int N, int K) {
+  linear_fwd_body<MT, true>(X, Wt, bias, nullptr, nullptr, M, N, K, (K + KT - 1) / KT, Y8, tau);
 }
 
 // out[e] = sum_s part[s][e] (+ bias[e % ncols]); fixed order -> deterministic.
@@ -434,6 +479,30 @@ int dd_linear_fwd(const float* x, const float* w, const float* bias, float* y, i
       launch_splits_reduce(part, bias, yc, elems, nsplit, n, st);
       DD_LAUNCH_CHECK("linear_fwd reduce");
     }
+  }
+  return 0;
+}
+
+int dd_linear_sigmoid_gt(const float* x, const float* w, const float* bias, float tau, uint8_t* out, int32_t m, int32_t n, int32_t k,
+                         void* stream) {
+  DD_REQUIRE(m > 0 && n > 0 && k > 0, DD_ERR_BAD_ARG, "linear_sigmoid_gt: non-positive size");
+  DD_REQUIRE(k % 4 == 0, DD_ERR_UNSUPPORTED, "linear_sigmoid_gt: K = %d must be a multiple of 4", k);
+  DD_REQUIRE(x && w && out, DD_ERR_BAD_ARG, "linear_sigmoid_gt: NULL pointer");
+  const int nblk = (n + 127) / 128, ntiles = (k + KT - 1) / KT;
+  // one workgroup walks the whole contraction, which is what dd_linear_fwd does up to here too: the logits are then the same bits
+  DD_REQUIRE(pick_split(nblk, ntiles) == 1, DD_ERR_UNSUPPORTED, "linear_sigmoid_gt: dd_linear_fwd splits K = %d over workgroups at N = %d (no split up to K = %d)",
+             k, n, 8 * KT);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(nblk, 1);
+  for (int m0 = 0; m0 < m; m0 += MCHUNK) {
+    const int mc = min(MCHUNK, m - m0);
+    const float* xc = x + (long)m0 * k;
+    unsigned char* oc = out + (long)m0 * n;
+    switch (pick_mt(mc)) {
+      case 1: hipLaunchKernelGGL(linear_sigmoid_gt_kernel<1>, grid, dim3(256), 0, st, xc, w, bias, oc, tau, mc, n, k); break;
+      default: hipLaunchKernelGGL(linear_sigmoid_gt_kernel<2>, grid, dim3(256), 0, st, xc, w, bias, oc, tau, mc, n, k); break;
+    }
+    DD_LAUNCH_CHECK("linear_sigmoid_gt");
   }
   return 0;
 }

@@ -13,6 +13,7 @@ from torch import nn
 from . import ops
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
+from .roadmap import predict_map
 from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, boxes_from_map, per_sample_inputs
 
 
@@ -51,6 +52,11 @@ class JointRoadMapBBox(LightningModule):
         """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4]."""
         with torch.no_grad():
             return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
+
+    def predict_road_map(self, x, threshold=None):
+        """The road-map branch as a boolean map, as ``RoadMapBCE.predict_road_map``: torch.bool [B,800,800]; the box branch is not run."""
+        views = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
+        return predict_map(self, lambda: self.ae.encoder.forward_nhwc4(ops.wide_image(views)), threshold)
 
     def training_step(self, batch, batch_idx):
         sample, target, road_image = batch

@@ -190,6 +190,45 @@ def threat_score(a, b, round_b=False):
     return out
 
 
+TS_BINS = 256            # default resolution of the threshold calibration: thresholds k / 256
+
+
+def ts_histogram(prob, target, bins=TS_BINS, out=None):
+    """Histogram of the probabilities split by the target (dd_ts_hist): int64 [2, bins + 1], slot ``ceil(p * bins)`` (NaN: 0), row 1 for a
+    non-zero target.  Holds the data set's exact threat score at every threshold ``k / bins`` (``ts_curve``).  The counts are ADDED to
+    ``out`` when one is given: the batches of a validation epoch accumulate in one buffer.  ``target``: fp32, uint8 or bool."""
+    _dev(prob, "prob")
+    if not (isinstance(target, torch.Tensor) and target.is_cuda and target.is_contiguous() and target.numel() == prob.numel()
+            and target.dtype in (torch.float32, torch.uint8, torch.bool)):
+        raise _lib.HotpathError(f"ts_histogram: target must be a contiguous fp32 / uint8 / bool device tensor of {prob.numel()} elements, got "
+                                f"{getattr(target, 'dtype', type(target))} {tuple(getattr(target, 'shape', ()))}")
+    if out is None:
+        out = torch.zeros((2, bins + 1), device=prob.device, dtype=torch.int64)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (2, bins + 1)):
+        raise _lib.HotpathError(f"ts_histogram: out must be a contiguous int64 device tensor [2, {bins + 1}]")
+    kind = 0 if target.dtype == torch.float32 else 1      # DD_TARGET_F32 / DD_TARGET_U8
+    check(_lib.lib().dd_ts_hist(_p(prob), _p(target), kind, prob.numel(), int(bins), _p(out), _stream()), "dd_ts_hist")
+    return out
+
+
+def ts_curve(hist):
+    """``ts_histogram``'s counts -> (ts float64 [bins], best_k): ts[k] = TP_k / (P_k + T - TP_k) for the prediction ``p > k / bins``,
+    with T every positive target; a threshold whose denominator is 0 scores 0.  best_k: the maximum; ties go to the k nearest
+    bins / 2 (the reference's round()), then to the lower k.  Plain torch on 2 x (bins + 1) integers."""
+    if hist.dim() != 2 or hist.size(0) != 2 or hist.size(1) < 3:
+        raise ValueError(f"ts_curve: expected counts [2, bins + 1], got {tuple(hist.shape)}")
+    h = hist.detach().to("cpu", torch.int64)
+    bins = h.size(1) - 1
+    above = torch.flip(torch.cumsum(torch.flip(h[:, 1:], [1]), 1), [1])      # [row, k]: elements with slot > k
+    tp, p, t = above[1], above[0] + above[1], h[1].sum()
+    den = p + t - tp
+    ts = torch.where(den > 0, tp.double() / den.clamp(min=1).double(), torch.zeros(bins, dtype=torch.float64))
+    k = torch.arange(bins)
+    ties = k[ts == ts.max()]
+    best = ties[torch.argmin((ties - bins // 2).abs() * (bins + 1) + ties)]
+    return ts, int(best)
+
+
 # ------------------------------------------------------------------------------------------------ box-level validation
 def _maps(maps, who):
     if not isinstance(maps, torch.Tensor) or maps.dim() != 3:
@@ -1086,6 +1125,22 @@ def linear(x, weight, bias):
         if sync is not None:
             sync.linear_input(weight, x)
     return Linear.apply(x, weight, bias)
+
+
+def linear_sigmoid_gt(x, weight, bias, tau):
+    """``sigmoid(x W^T + b) > tau`` as torch.bool [M, N] from one kernel (dd_linear_sigmoid_gt): element for element what
+    ``sigmoid(linear(x, W, b)) > tau`` gives, without the logits or the probabilities ever reaching memory.  The road-map head at
+    prediction time; outside autograd."""
+    x = x.detach().contiguous()
+    m, k = x.shape
+    n = weight.shape[0]
+    _dev(x, "x")
+    _dev(weight.detach(), "weight", (n, k))
+    if bias is not None:
+        _dev(bias.detach(), "bias", (n,))
+    out = torch.empty((m, n), device=x.device, dtype=torch.uint8)
+    check(_lib.lib().dd_linear_sigmoid_gt(_p(x), _p(weight), _p(bias), float(tau), _p(out), m, n, k, _stream()), "dd_linear_sigmoid_gt")
+    return out.view(torch.bool)
 
 
 def column_sum(dy):

@@ -16,6 +16,24 @@ from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 
 
+def predict_map(module, latent, threshold):
+    """``module``'s road-map head as a boolean map: ``latent()`` (the encoder) -> ``ops.linear_sigmoid_gt`` with ``module.fc1``, under
+    ``no_grad`` and in ``eval()`` mode; every submodule's mode is put back afterwards (a frozen extractor stays in eval inside a
+    training model).  ``threshold=None``: the calibrated ``rm_threshold`` where there is one, else the reference's 0.5."""
+    if threshold is None:
+        threshold = hparam(module.hparams, "rm_threshold", None)
+    tau = 0.5 if threshold is None else float(threshold)
+    modes = [(m, m.training) for m in module.modules()]
+    module.eval()
+    try:
+        with torch.no_grad():
+            y = ops.linear_sigmoid_gt(latent(), module.fc1.weight, module.fc1.bias, tau)
+    finally:
+        for m, was in modes:
+            m.training = was
+    return y.reshape(y.size(0), 800, 800)
+
+
 def compute_ts_road_map(road_map1, road_map2):
     """Threat score, reference src/utils/helper.py:74-77 (one fused pass on the device)."""
     return ops.threat_score(road_map1.contiguous(), road_map2.contiguous())
@@ -59,6 +77,23 @@ class RoadMapBCE(LightningModule):
         """-> (logits [B,800,800], sigmoid(logits)).  roadmap_bce_v2.py:66-81."""
         y = self._logits(x, keeps)
         return y, ops.sigmoid(y.detach())
+
+    @property
+    def rm_threshold(self):
+        """The operating point ``validation_epoch_end`` calibrated (hparams.calibrate_threshold), a plain float, or None.  Kept in
+        ``hparams`` -- not a buffer, not in the state_dict -- so ``save_checkpoint`` / ``load_from_checkpoint`` carry it."""
+        return hparam(self.hparams, "rm_threshold", None)
+
+    @rm_threshold.setter
+    def rm_threshold(self, value):
+        self.hparams.rm_threshold = None if value is None else float(value)
+
+    def predict_road_map(self, x, threshold=None):
+        """The reference's "Predicting test images" step (run_test.py) for one batch: torch.bool [B,800,800], equal to ``forward``'s
+        probabilities ``> threshold`` in eval mode.  ``x``: whatever ``forward`` takes.  Encoder, then the head, the sigmoid and the
+        comparison in one kernel: neither logits nor probabilities are written.  (The dense blocks' dropout is on in eval mode too, as
+        in the reference, components.py:108.)"""
+        return predict_map(self, lambda: self._encode(x), threshold)
 
     def _run_step(self, batch, batch_idx, step_name, keeps=(None, None)):
         sample, target, road_image = batch
@@ -104,11 +139,23 @@ class RoadMapBCE(LightningModule):
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
         val_ts = compute_ts_road_map(target_rm, pred_logit_rm)
         val_ts_rounded = ops.threat_score(target_rm.contiguous(), pred_logit_rm.contiguous(), round_b=True)
-        return {"val_loss": val_loss, "val_ts_rounded": val_ts_rounded, "val_ts": val_ts}
+        out = {"val_loss": val_loss, "val_ts_rounded": val_ts_rounded, "val_ts": val_ts}
+        return self._with_ts_hist(out, pred_logit_rm, target_rm)
+
+    def _with_ts_hist(self, out, probs, target_rm):
+        if hparam(self.hparams, "calibrate_threshold", False):
+            out["ts_hist"] = ops.ts_histogram(probs.detach().contiguous(), target_rm.contiguous())
+        return out
 
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
+        if hparam(self.hparams, "calibrate_threshold", False):
+            # the DATA SET's threat score at every threshold k / bins (the averages above are means of per-batch scores)
+            hist = torch.stack([x["ts_hist"] for x in outputs]).sum(0)
+            ts, best = ops.ts_curve(hist)
+            self.rm_threshold = best / ts.numel()
+            logs.update(best_threshold=self.rm_threshold, best_val_ts=float(ts[best]), val_ts_at_half=float(ts[ts.numel() // 2]))
         return {"val_loss": avg["val_loss"], "log": logs}
 
     def configure_optimizers(self):
@@ -125,6 +172,8 @@ class RoadMapBCE(LightningModule):
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)
+        p.add_argument("--calibrate_threshold", action="store_true",
+                       help="validation also finds the threshold with the best data-set threat score (rm_threshold)")
         return p
 
 
@@ -152,5 +201,6 @@ class RoadMap(RoadMapBCE):
 
     def validation_step(self, batch, batch_idx):
         val_loss, target_rm, pred_rm = self._run_step(batch, batch_idx, step_name="valid")
-        return {"val_loss": val_loss, "val_ts": compute_ts_road_map(target_rm, pred_rm),
-                "val_ts_rounded": ops.threat_score(target_rm.contiguous(), pred_rm.contiguous(), round_b=True)}
+        out = {"val_loss": val_loss, "val_ts": compute_ts_road_map(target_rm, pred_rm),
+               "val_ts_rounded": ops.threat_score(target_rm.contiguous(), pred_rm.contiguous(), round_b=True)}
+        return self._with_ts_hist(out, pred_rm, target_rm)

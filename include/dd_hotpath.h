@@ -556,6 +556,13 @@ int dd_linear_fwd(const float* x, const float* w, const float* bias, float* y, i
                   void* workspace, int64_t workspace_bytes, void* stream);
 int dd_linear_dgrad(const float* dy, const float* w, float* dx, int32_t m, int32_t n, int32_t k, void* workspace,
                     int64_t workspace_bytes, void* stream);
+/* The road-map head as a boolean map in one kernel: out[m][n] = sigmoid(x[m,:] . w[n,:] + bias[n]) > tau, one byte (0 / 1) per
+ * element, row-major [M,N] (16-byte stores where N % 16 == 0 and out is 16-byte aligned).  dd_linear_fwd's tiles and contraction
+ * order and dd_sigmoid's expression, so the result equals dd_sigmoid(dd_linear_fwd(...)) > tau element for element; neither the
+ * logits nor the probabilities are written.  Any M and N, K % 4 == 0; refused where dd_linear_fwd would split K over workgroups
+ * (it does not up to K = 512).  bias may be NULL. */
+int dd_linear_sigmoid_gt(const float* x, const float* w, const float* bias, float tau, uint8_t* out, int32_t m, int32_t n, int32_t k,
+                         void* stream);
 int dd_linear_wgrad(const float* dy, const float* x, float* dw, float* dbias, int32_t m, int32_t n, int32_t k,
                     void* stream);
 /* dbias[N] = sum_m dy[m,:] alone: the bias gradient of a layer whose weight gradient is formed inside its optimizer pass
@@ -566,6 +573,16 @@ int dd_column_sum(const float* dy, float* dbias, int32_t m, int32_t n, void* str
  * round(b) (roadmap_bce_v2.py:140).  One pass, deterministic. */
 int64_t dd_threat_score_workspace_bytes(void);
 int dd_threat_score(const float* a, const float* b, float* out, int64_t n, int32_t round_b, void* workspace, void* stream);
+
+/* Threat score at every threshold: histogram of the probabilities, split by the target.  For each of the n elements (n % 4 == 0,
+ * as for dd_sigmoid; 16-byte loads, nothing is read past n) slot = ceil(prob * bins) clamped to [0, bins], NaN -> 0; bins a power
+ * of two in [2, 1024], so the scaling is exact and slot > k <=> prob > k / bins in fp32 (k = bins / 2 is round()'s p > 0.5).
+ * hist is int64 [2][bins + 1]: row 1 counts the elements whose target is non-zero, row 0 the rest.  The counts are ADDED to hist
+ * (64-bit integer atomics): the caller zeroes it once and the batches of a validation epoch accumulate; integer adds only, so the
+ * result is the same bits on every run.  target: fp32 (16-byte aligned) or one byte per element (uint8 / bool, 4-byte aligned).
+ * An unsupported bins, n or dtype is refused before anything is written. */
+enum { DD_TARGET_F32 = 0, DD_TARGET_U8 = 1 };
+int dd_ts_hist(const float* prob, const void* target, int32_t target_dtype, int64_t n, int32_t bins, int64_t* hist, void* stream);
 
 /* ---- box-level validation: map -> components -> boxes -> IoU -> average threat score ---------
  * The inverse direction of dd_boxes_to_binary_map, and compute_ats_bounding_boxes / compute_iou (src/utils/helper.py:33-83).
