@@ -222,6 +222,16 @@ SIGNATURES = {
     "dd_adam_step_rankb": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
     "dd_column_sum": (_i32, [_p, _p, _i32, _i32, _p]),
     "dd_adam_step_multi": (_i32, [C.POINTER(AdamTensor), _i32, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
+    "dd_adam_step_dev": (_i32, [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _i32, _p, _p]),
+    "dd_adam_step_rankb_dev": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _f32, _f32, _f32, _f32, _i32, _p, _p]),
+    "dd_adam_step_multi_dev": (_i32, [C.POINTER(AdamTensor), _i32, _f32, _f32, _f32, _f32, _i32, _p, _p]),
+    "dd_sqnorm_workspace_bytes": (_i64, [_i64]),
+    "dd_sqnorm": (_i32, [_p, _i64, _p, _p, _i64, _p]),
+    "dd_sqnorm_multi_workspace_bytes": (_i64, [C.POINTER(AdamTensor), _i32]),
+    "dd_sqnorm_multi": (_i32, [C.POINTER(AdamTensor), _i32, _p, _p, _i64, _p]),
+    "dd_rankb_sqnorm_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "dd_rankb_sqnorm": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
+    "dd_clip_scale": (_i32, [_p, _i32, _f32, _f32, _p, _p]),
 }
 
 ABI_VERSION = 4      # include/dd_hotpath.h: DD_ABI_VERSION

@@ -1473,23 +1473,44 @@ def sigmoid_and_loss(logits, target):
 
 
 # ------------------------------------------------------------------------------------------------ optimizer
-def adam_step_multi(tensors, lr, beta1, beta2, eps, step, grad_scale=1.0):
-    """One launch for a list of small (p, g, m, v) quadruples that share ``step`` (dd_adam_step_multi)."""
-    if not tensors:
-        return
+def _scale_arg(grad_scale):
+    """(by value, device pointer) of an optimizer shim's ``grad_scale``: a Python number goes to the host-scalar entry point, a one-element
+    fp32 device tensor (what ``clip_scale`` wrote) to the ``_dev`` one, which reads it when the kernel starts."""
+    if isinstance(grad_scale, torch.Tensor):
+        if not (grad_scale.is_cuda and grad_scale.dtype == torch.float32 and grad_scale.numel() == 1):
+            raise _lib.HotpathError("grad_scale: a tensor must be one fp32 element on the device")
+        return None, grad_scale
+    return float(grad_scale), None
+
+
+def _adam_table(tensors):
     table = (_lib.AdamTensor * len(tensors))()
     for i, quad in enumerate(tensors):
         for name, t in zip("pgmv", quad):
             _dev(t, name, quad[0].shape)
         table[i] = _lib.AdamTensor(_p(quad[0]), _p(quad[1]), _p(quad[2]), _p(quad[3]), quad[0].numel())
-    check(_lib.lib().dd_adam_step_multi(table, len(tensors), lr, beta1, beta2, eps, int(step), grad_scale, _stream()),
+    return table
+
+
+def adam_step_multi(tensors, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    """One launch for a list of small (p, g, m, v) quadruples that share ``step`` (dd_adam_step_multi; ``grad_scale`` a device tensor:
+    dd_adam_step_multi_dev)."""
+    if not tensors:
+        return
+    table = _adam_table(tensors)
+    scale, scale_dev = _scale_arg(grad_scale)
+    if scale_dev is not None:
+        check(_lib.lib().dd_adam_step_multi_dev(table, len(tensors), lr, beta1, beta2, eps, int(step), _p(scale_dev), _stream()),
+              "dd_adam_step_multi_dev")
+        return
+    check(_lib.lib().dd_adam_step_multi(table, len(tensors), lr, beta1, beta2, eps, int(step), scale, _stream()),
           "dd_adam_step_multi")
 
 
 def adam_step_rankb(p, m, v, dy, x, bias, bias_m, bias_v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """Adam on the Linear weight ``p`` [n, k] (moments ``m``, ``v``) with its gradient dy^T x formed inside the pass from the layer's
     output gradient ``dy`` [rows, n] and input ``x`` [rows, k]; ``bias`` (optional, with its moments) is updated from dy's column sums
-    in the same launch (dd_adam_step_rankb)."""
+    in the same launch (dd_adam_step_rankb; ``grad_scale`` a device tensor: dd_adam_step_rankb_dev)."""
     rows, n = dy.shape
     k = x.shape[1]
     _dev(dy, "dy")
@@ -1499,12 +1520,93 @@ def adam_step_rankb(p, m, v, dy, x, bias, bias_m, bias_v, lr, beta1, beta2, eps,
     if bias is not None:
         for name, t in (("bias", bias), ("bias_m", bias_m), ("bias_v", bias_v)):
             _dev(t, name, (n,))
+    scale, scale_dev = _scale_arg(grad_scale)
+    if scale_dev is not None:
+        check(_lib.lib().dd_adam_step_rankb_dev(_p(p), _p(m), _p(v), _p(dy), _p(x), rows, n, k, _p(bias), _p(bias_m), _p(bias_v),
+                                                lr, beta1, beta2, eps, int(step), _p(scale_dev), _stream()), "dd_adam_step_rankb_dev")
+        return
     check(_lib.lib().dd_adam_step_rankb(_p(p), _p(m), _p(v), _p(dy), _p(x), rows, n, k, _p(bias), _p(bias_m), _p(bias_v),
-                                        lr, beta1, beta2, eps, int(step), grad_scale, _stream()), "dd_adam_step_rankb")
+                                        lr, beta1, beta2, eps, int(step), scale, _stream()), "dd_adam_step_rankb")
 
 
 def adam_step_flat(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _dev(t, name, p.shape)
-    check(_lib.lib().dd_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, int(step), grad_scale,
+    scale, scale_dev = _scale_arg(grad_scale)
+    if scale_dev is not None:
+        check(_lib.lib().dd_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, int(step), _p(scale_dev),
+                                          _stream()), "dd_adam_step_dev")
+        return
+    check(_lib.lib().dd_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, int(step), scale,
                                   _stream()), "dd_adam_step")
+
+
+# ------------------------------------------------------------------------------------------------ gradient norm (clipping)
+_NORM_WS = {}      # device -> persistent workspace of the norm kernels (grown, never shrunk: no allocation in a steady step)
+
+
+def _norm_ws(nbytes, device):
+    """The norm kernels run one after the other on the optimizer's stream, each done with its partials when its own last stage has
+    run: one workspace per device serves them all."""
+    ws = _NORM_WS.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _NORM_WS[device] = torch.empty(max(int(nbytes), 1 << 16), device=device, dtype=torch.uint8)
+    return ws
+
+
+def _slot(out):
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.numel() == 1):
+        raise _lib.HotpathError("out: expected one fp64 element on the device")
+    return out
+
+
+def sqnorm(g, out):
+    """``out`` (one fp64 device element) = sum of squares of the flat fp32 device tensor ``g``, accumulated in fp64 (dd_sqnorm)."""
+    _dev(g, "g")
+    nbytes = _lib.lib().dd_sqnorm_workspace_bytes(g.numel())
+    if nbytes < 0:
+        raise _lib.HotpathError(f"dd_sqnorm_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    ws = _norm_ws(nbytes, g.device)
+    check(_lib.lib().dd_sqnorm(_p(g), g.numel(), _p(_slot(out)), _p(ws), ws.numel(), _stream()), "dd_sqnorm")
+    return out
+
+
+def sqnorm_multi(grads, out):
+    """The same over a list of (small) fp32 device tensors: one launch per 48 of them (dd_sqnorm_multi)."""
+    if not grads:
+        raise _lib.HotpathError("sqnorm_multi: no tensors")
+    table = (_lib.AdamTensor * len(grads))()
+    for i, g in enumerate(grads):
+        _dev(g, "g")
+        table[i] = _lib.AdamTensor(None, _p(g), None, None, g.numel())
+    nbytes = _lib.lib().dd_sqnorm_multi_workspace_bytes(table, len(grads))
+    if nbytes < 0:
+        raise _lib.HotpathError(f"dd_sqnorm_multi_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    ws = _norm_ws(nbytes, grads[0].device)
+    check(_lib.lib().dd_sqnorm_multi(table, len(grads), _p(_slot(out)), _p(ws), ws.numel(), _stream()), "dd_sqnorm_multi")
+    return out
+
+
+def rankb_sqnorm(dy, x, with_bias, out):
+    """``out`` = ||dy^T x||_F^2 (+ ||dy.sum(0)||^2 with ``with_bias``) from the factors of a Linear layer, in fp64, without forming the
+    weight gradient (dd_rankb_sqnorm)."""
+    rows, n = dy.shape
+    k = x.shape[1]
+    _dev(dy, "dy")
+    _dev(x, "x", (rows, k))
+    nbytes = _lib.lib().dd_rankb_sqnorm_workspace_bytes(rows, n, k)
+    if nbytes < 0:
+        raise _lib.HotpathError(f"dd_rankb_sqnorm_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    ws = _norm_ws(nbytes, dy.device)
+    check(_lib.lib().dd_rankb_sqnorm(_p(dy), _p(x), rows, n, k, 1 if with_bias else 0, _p(_slot(out)), _p(ws), ws.numel(), _stream()),
+          "dd_rankb_sqnorm")
+    return out
+
+
+def clip_scale(sq, max_norm, grad_scale, out3):
+    """``out3`` (3 fp32 device elements) = {grad_scale * coef, norm, coef} from the fp64 squared norms ``sq`` (dd_clip_scale)."""
+    if not (isinstance(sq, torch.Tensor) and sq.is_cuda and sq.dtype == torch.float64 and sq.is_contiguous() and sq.numel() > 0):
+        raise _lib.HotpathError("sq: expected a contiguous fp64 device tensor")
+    _dev(out3, "out3", (3,))
+    check(_lib.lib().dd_clip_scale(_p(sq), sq.numel(), float(max_norm), float(grad_scale), _p(out3), _stream()), "dd_clip_scale")
+    return out3

@@ -44,6 +44,12 @@ class HipAdam(torch.optim.Optimizer):
         self._held = []            # factors read by launches on the side stream: kept until step() has joined it
         self._fac_now = {}         # weight -> gathered Factors that have arrived (factor mode of ddp.GradSync + rank-B)
         self._last = False         # passes_last(): c2's data gradient first, the queued passes beside its weight gradient
+        self._clip_max = 0.0       # set_clip(): clip the step's gradients to this global 2-norm (0: off)
+        self._clip_track = False   # set_clip(): measure the global norm every step
+        self._slots = None         # persistent fp64 buffer, one squared norm per launch of the norm kernels
+        self._out3 = None          # persistent fp32 {grad_scale * coef, norm, coef} (dd_clip_scale)
+        self.grad_norm = None      # device scalars, valid after a step() with set_clip(): views of _out3
+        self.clip_coef = None
 
     SMALL_NUMEL = 1 << 16      # tensors up to this size go into one multi-tensor launch (0: never; tests set it per instance)
 
@@ -211,7 +217,7 @@ class HipAdam(torch.optim.Optimizer):
         ops.adam_step_rankb(p.data, st["exp_avg"], st["exp_avg_sq"], dy, x, None if bias is None else bias.data,
                             None if bst is None else bst["exp_avg"], None if bst is None else bst["exp_avg_sq"],
                             group["lr"], b1, b2, group["eps"], st["step"], grad_scale)
-        self._held.append((x, dy))
+        self._held.append((x, dy, bias is not None))      # (the flag: what rankb_sqnorm needs when it measures a pass that already ran)
         self._early.add(p)
 
     def _take_rankb(self, p, group, grad_scale):
@@ -405,6 +411,9 @@ class HipAdam(torch.optim.Optimizer):
         bandwidth idle -- so ~0.8 of the 1.0 ms Adam time disappears under them.  With ``grad_sync`` (data parallel)
         the side stream first waits for that parameter's all-reduce.  ``step()`` then only handles the small
         parameters and joins the side stream."""
+        if self._clip_max > 0:
+            raise RuntimeError("HipAdam: a clipped step (set_clip) runs its passes after the backward: no pass may start before every "
+                               "gradient exists")
         self._side = torch.cuda.Stream()
         ops.check(ops._lib.lib().dd_set_adam_blocks_per_cu(1), "dd_set_adam_blocks_per_cu")      # beside conv kernels: nothing queued ahead of them
         self._scale = grad_scale
@@ -473,6 +482,66 @@ class HipAdam(torch.optim.Optimizer):
         self._side = None
         self._sync = None
 
+    # ---- global gradient norm: clipping and logging ------------------------------------------------------------------------------
+    def set_clip(self, max_norm=0.0, track=False):
+        """Clip every step's gradients to the global 2-norm ``max_norm`` (torch.nn.utils.clip_grad_norm_'s formula; 0: no clipping)
+        and / or -- ``track`` -- only measure it.  The norm is taken over every tensor the step updates, on the device, in fp64: of a
+        rank-B layer from its factors (``dd_rankb_sqnorm``: no gradient tensor is formed for it either), of the materialised gradients
+        by ``dd_sqnorm`` / ``dd_sqnorm_multi``; ``dd_clip_scale`` turns the sums into {grad_scale x coef, norm, coef}, and with
+        ``max_norm > 0`` every update of the step reads its scale from there (the ``_dev`` entry points): nothing comes back to the
+        host.  ``grad_norm`` and ``clip_coef`` are device scalars, valid after ``step()``.  The norm is that of the gradients as Adam
+        sees them (``step(grad_scale=...)`` included).
+        A clipped step cannot start a pass before the last gradient exists: not with ``overlap_with_backward``.  ``track`` alone only
+        reads the gradients and factors and works in either arrangement."""
+        max_norm = float(max_norm or 0.0)
+        if not max_norm >= 0.0:
+            raise ValueError(f"HipAdam.set_clip: max_norm = {max_norm}")
+        if max_norm > 0 and self._side is not None:
+            raise RuntimeError("HipAdam.set_clip: with overlap_with_backward the passes of the big tensors run before the last gradient "
+                               "exists; a clipped step needs the after-backward arrangement (TrainStep(adam_overlap=False))")
+        self._clip_max, self._clip_track = max_norm, bool(track)
+
+    def _measure(self, grad_scale):
+        """The norm kernels of this step (on the current stream) and ``dd_clip_scale``; returns the one-element device tensor
+        grad_scale x coef, or None when the step has no gradient at all.  No host synchronisation, no allocation once the buffers exist."""
+        s = self._sync
+        if s is not None and (getattr(s, "active", False) or getattr(s, "shard", False) or getattr(s, "factor", False)):
+            raise NotImplementedError("HipAdam.set_clip: the global norm under a live GradSync (all-reduce, sharded, factor gather) is "
+                                      "not implemented")
+        factors = [(x, dy, has_bias) for x, dy, has_bias in self._held]                  # passes that already ran (track, overlap mode)
+        factors += [(x, dy, bias is not None) for x, dy, bias in self._rankb_now.values()]
+        big, small = [], []
+        for group in self.param_groups:
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.dtype != torch.float32 or not g.is_contiguous():
+                    raise RuntimeError(f"HipAdam.set_clip: a gradient of dtype {g.dtype}, contiguous={g.is_contiguous()}: the norm "
+                                       "kernels take contiguous fp32 gradients")
+                (big if g.numel() > self.SMALL_NUMEL else small).append(g.view(-1))
+        count = len(factors) + len(big) + (1 if small else 0)
+        if count == 0:
+            return None
+        dev = (factors[0][0] if factors else (big or small)[0]).device
+        if self._slots is None or self._slots.numel() < count or self._slots.device != dev:
+            self._slots = torch.zeros(max(count, 8), device=dev, dtype=torch.float64)
+        if self._out3 is None or self._out3.device != dev:
+            self._out3 = torch.zeros(3, device=dev, dtype=torch.float32)
+            self.grad_norm, self.clip_coef = self._out3[1], self._out3[2]
+        i = 0
+        for x, dy, has_bias in factors:
+            ops.rankb_sqnorm(dy, x, has_bias, self._slots[i:i + 1])
+            i += 1
+        for g in big:
+            ops.sqnorm(g, self._slots[i:i + 1])
+            i += 1
+        if small:
+            ops.sqnorm_multi(small, self._slots[i:i + 1])
+            i += 1
+        ops.clip_scale(self._slots[:count], self._clip_max, grad_scale, self._out3)
+        return self._out3[0:1]
+
     def _early_step(self, p, group):
         if p.grad is not None:
             self._pending.append((p, group))      # launched when backward reaches its MFMA-bound stretch
@@ -506,6 +575,10 @@ class HipAdam(torch.optim.Optimizer):
     def step(self, grad_scale=1.0):
         if self._side is not None:
             self._flush_pending()                 # backward never reached an MFMA phase hook (other models)
+        if self._clip_max > 0 or self._clip_track:
+            scale = self._measure(grad_scale)
+            if self._clip_max > 0 and scale is not None:
+                grad_scale = scale                # every update below reads grad_scale x coef from the device
         self._factored.clear()
         for group in self.param_groups:
             small = {}                            # step count -> [(p, g, m, v)]: one launch for all the small tensors

@@ -11,6 +11,8 @@ exactly that (torch.optim.Adam): a caller with its own loop keeps working.  This
     beside the MFMA-bound stretch of the backward (``overlap_with_backward``); the big ``nn.Linear`` weights (encoder fc1, head,
     decoder fc2) take a rank-B update: their gradient is formed inside the Adam pass from the layer's input and output gradient and
     never written (``fuse_linear_wgrad``; ``weight.grad`` of those layers stays None -- pass ``fuse_linear_wgrad=False`` to keep it);
+  * ``gradient_clip_val`` / ``track_grad_norm`` (Lightning's Trainer arguments): the global gradient norm measured and applied on the
+    device, the rank-B layers' from their factors (``HipAdam.set_clip``); a clipped step runs its optimizer passes after the backward;
   * ``ddp.GradSync`` when ``torch.distributed`` is initialised: per-tensor asynchronous all-reduce from autograd hooks, or -- with
     ``shard_optimizer=True`` -- reduce-scatter, Adam on the owned 1/N, in-place all-gather under the next forward; or -- with
     ``factor_linear=True``, for 2-4 ranks -- the big Linear layers send their factors (input, output gradient) instead of their
@@ -32,13 +34,24 @@ from .optim import HipAdam
 class TrainStep:
     def __init__(self, model, lr=None, adam_overlap="auto", shard_optimizer=False, reserve_cus=None, process_group=None,
                  force_collectives=False, simulate_world=0, scheduler="auto", big_numel=1 << 20, chunk_numel=1 << 25, factor_linear=False,
-                 fuse_linear_wgrad=True, passes_last="auto"):
+                 fuse_linear_wgrad=True, passes_last="auto", gradient_clip_val=None, track_grad_norm=False):
         self.model = model
         hp = getattr(model, "hparams", None)
         if lr is None:
             lr = getattr(hp, "learning_rate", None)
             if lr is None:
                 raise ValueError("TrainStep: no lr given and model.hparams has no learning_rate")
+        # Lightning 0.7.5's --gradient_clip_val / --track_grad_norm (Trainer.from_argparse_args, submit.py:40; its parser leaves 0 in
+        # hparams): clip the step to a global 2-norm, log the norm.  On the device, rank-B layers included (HipAdam.set_clip).
+        if gradient_clip_val is None:
+            gradient_clip_val = getattr(hp, "gradient_clip_val", 0)
+        self.clip = float(gradient_clip_val or 0.0)
+        self.track = bool(track_grad_norm)
+        if self.clip < 0:
+            raise ValueError(f"TrainStep: gradient_clip_val = {gradient_clip_val}")
+        if self.clip > 0 and adam_overlap is not False and adam_overlap != "auto" and adam_overlap:
+            raise ValueError("TrainStep: gradient_clip_val needs the optimizer passes after the backward; adam_overlap=True starts them "
+                             "beside it")
         distributed = dist.is_available() and dist.is_initialized()
         world = dist.get_world_size(process_group) if distributed else 1
         comm = distributed and (world > 1 or force_collectives)
@@ -51,6 +64,12 @@ class TrainStep:
                              force_collectives=force_collectives, shard_optimizer=shard_optimizer, simulate_world=simulate_world,
                              factor_linear=factor_linear)
         self.optimizer.attach(self.sync)
+        if (self.clip > 0 or self.track) and (self.sync.active or self.sync.shard or self.sync.factor):
+            self.sync.remove()
+            raise NotImplementedError("TrainStep: gradient_clip_val / track_grad_norm under a live GradSync (all-reduce, sharded, factor "
+                                      "gather) is not implemented: one GPU only")
+        if self.clip > 0 and adam_overlap == "auto":
+            adam_overlap = False      # no optimizer pass may start before every gradient exists: the after-backward arrangement
         if adam_overlap == "auto":
             # fp32 models: the passes of the big tensors ride beside the MFMA-bound c2 weight gradient.  A bf16 encoder has no MFMA-bound
             # stretch -- its conv kernels are HBM-bound, and an 11.6 GB optimizer stream beside them only time-shares the same HBM
@@ -74,6 +93,8 @@ class TrainStep:
             passes_last = bool(self.fused) and not ((self.sync.active or self.sync.shard) and not self.sync.factor)
         if self.overlap and passes_last:
             self.optimizer.passes_last(True)
+        if self.clip > 0 or self.track:
+            self.optimizer.set_clip(self.clip, track=self.track)
         if scheduler == "auto":      # the modules that return ([optimizer], [scheduler]) from configure_optimizers
             scheduler = self._reference_has_scheduler(model)
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, patience=10) if scheduler else None
@@ -104,6 +125,8 @@ class TrainStep:
         loss.backward(self._one)                 # the root gradient is a kept tensor: no ones_like fill launch per step
         self.sync.finish()
         self.optimizer.step(grad_scale=self.sync.grad_scale)
+        if self.track:                           # Lightning's key for --track_grad_norm 2; the value stays on the device
+            out.setdefault("log", {})["grad_2.0_norm_total"] = self.optimizer.grad_norm
         self.last = out
         return out
 

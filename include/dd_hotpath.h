@@ -706,6 +706,38 @@ int dd_adam_step_rankb(float* p, float* m, float* v, const float* dy, const floa
                        float* bias_p, float* bias_m, float* bias_v, float lr, float beta1, float beta2, float eps, int32_t step,
                        float grad_scale, void* stream);
 
+/* The three entry points above with the gradient scale read from DEVICE memory (one fp32, 4-byte aligned) when the kernel starts
+ * instead of passed by the host: a scale that an earlier kernel on the stream computed -- dd_clip_scale's grad_scale x clip coefficient --
+ * reaches the update without a host round trip.  Same kernels' bodies, same arithmetic: the same value gives the same bits. */
+int dd_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     int32_t step, const float* grad_scale_dev, void* stream);
+int dd_adam_step_multi_dev(const dd_adam_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, int32_t step,
+                           const float* grad_scale_dev, void* stream);
+int dd_adam_step_rankb_dev(float* p, float* m, float* v, const float* dy, const float* x, int32_t rows, int32_t n, int32_t k,
+                           float* bias_p, float* bias_m, float* bias_v, float lr, float beta1, float beta2, float eps, int32_t step,
+                           const float* grad_scale_dev, void* stream);
+
+/* ---- global gradient norm (torch.nn.utils.clip_grad_norm_, norm type 2: Lightning 0.7.5's --gradient_clip_val / --track_grad_norm,
+ * which the reference's Trainer.from_argparse_args accepts, submit.py:40) ------------------------------------------------------------
+ * All sums are fp64 (the square of an fp32 and the product of two are exact there), reduced in two stages in a fixed order: the same
+ * bits on every run.  `out` is ONE fp64 in device memory (8-byte aligned), overwritten; `workspace` holds the per-workgroup partials.
+ * dd_sqnorm: sum g_i^2 of one flat fp32 buffer (16-byte aligned).  dd_sqnorm_multi: the same over the g / n fields of a HOST table
+ * (the other fields are not read; any alignment), one launch per 48 tensors, added in table order. */
+int64_t dd_sqnorm_workspace_bytes(int64_t n);
+int dd_sqnorm(const float* g, int64_t n, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t dd_sqnorm_multi_workspace_bytes(const dd_adam_tensor* tensors, int32_t count);
+int dd_sqnorm_multi(const dd_adam_tensor* tensors, int32_t count, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* ||dy^T x||_F^2 of the weight gradient dd_adam_step_rankb forms, WITHOUT forming it, plus -- with_bias -- ||column sums of dy||^2:
+ * sum_ab (dy dy^T)_ab (x x^T)_ab (+ sum_ab (dy dy^T)_ab), two rows x rows Gram matrices accumulated in fp64 on the matrix cores from one
+ * read of each factor.  Preconditions of dd_adam_step_rankb: rows <= 64, n % 4 == 0, k % 4 == 0, dy and x 16-byte aligned. */
+int64_t dd_rankb_sqnorm_workspace_bytes(int32_t rows, int32_t n, int32_t k);
+int dd_rankb_sqnorm(const float* dy, const float* x, int32_t rows, int32_t n, int32_t k, int32_t with_bias, double* out, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+/* One wave: S = sq[0] + ... + sq[count - 1] (fp64, index order), norm = grad_scale sqrt(S) -- the norm of the gradients as the optimizer
+ * will see them --, coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1 (clip_grad_norm_'s formula; non-finite values propagate as
+ * in torch); out3 (fp32, device) = {grad_scale coef, norm, coef}.  out3 is what the *_dev optimizer entry points take. */
+int dd_clip_scale(const double* sq, int32_t count, float max_norm, float grad_scale, float* out3, void* stream);
+
 /* ---- Winograd F(2,3) along x for the 32 -> 32 stride-1 layer (c2, components.py:20): the same outputs as
  * dd_conv_fwd_relu_bits / dd_conv_dgrad_relu_bits from 2/3 of the multiplies (4 per output-pixel pair and tap row
  * instead of 6), still exact fp32 arithmetic (the transforms are fp32 adds and one halving; results differ from the

@@ -1,0 +1,371 @@
+"""GPU tests of clipping by global gradient norm without materialising the rank-B gradients: the norm kernels (``dd_sqnorm``,
+``dd_sqnorm_multi``, ``dd_rankb_sqnorm``) against fp64 torch, ``dd_clip_scale`` against clip_grad_norm_'s formula, the ``_dev`` optimizer
+entry points against their host-scalar twins bit for bit, and ``TrainStep(gradient_clip_val=..., track_grad_norm=...)`` against the
+materialised path clipped on the host (Lightning 0.7.5's Trainer arguments; reference submit.py:40)."""
+import math
+from argparse import Namespace
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+EPS52, EPS23 = 2.0 ** -52, 2.0 ** -23
+SMALL_SIZES = (1, 32, 288, 9216, 65536)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from driving_dirty_amd import _lib
+    _lib.lib()
+    return torch.device("cuda:0")
+
+
+def _tiny_model(dev):
+    from driving_dirty_amd import synth
+    from driving_dirty_amd.autoencoder import BasicAE
+    from driving_dirty_amd.roadmap import RoadMapBCE
+    ae = BasicAE(Namespace(hidden_dim=16, latent_dim=8, input_height=16, input_width=132))
+    model = RoadMapBCE(Namespace(pretrained_ae=ae, unfreeze_epoch_no=0, learning_rate=1e-2, output_img_freq=500))
+    synth.fill_module(model, seed=77)
+    model = model.to(dev)
+    model.ae.encoder.fc1.drop_p = model.ae.encoder.fc2.drop_p = 0.0
+    return model
+
+
+def _tiny_batch(dev, step):
+    from driving_dirty_amd import synth
+    views = synth.camera_batch(3, 16, 22, seed=100 + 10 * step).to(dev)
+    road = synth.road_maps(3, seed=100 + 10 * step).to(dev)
+    return (tuple(views), None, tuple(road))
+
+
+def _slices(dev, sizes, seed):
+    """Slices of ONE allocation at 16-byte-aligned offsets with live data on both sides of each: an over-read changes the sum."""
+    offs, at = [], 4
+    for n in sizes:
+        offs.append(at)
+        at += (n + 3) // 4 * 4 + 4
+    buf = torch.randn(at, generator=torch.Generator().manual_seed(seed)).to(dev)
+    return [buf[o:o + n] for o, n in zip(offs, sizes)]
+
+
+def _slots(dev, n=2):
+    return torch.full((n,), -1.0, device=dev, dtype=torch.float64)
+
+
+# ------------------------------------------------------------------------------------------------ 1. sqnorm, sqnorm_multi
+@pytest.fixture(scope="module")
+def flat_cases(dev):
+    sizes = (1, 3, 4, 1027, 4 * 256 * 7 + 5, (1 << 21) + 7)
+    return dict(zip(sizes, _slices(dev, sizes, seed=1)))
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 1027, 4 * 256 * 7 + 5, (1 << 21) + 7])
+def test_sqnorm_matches_fp64(dev, flat_cases, n):
+    """A sum of n non-negative fp64 terms (the squares are exact) in any order is within n 2^-53 relative of the true sum; so is the
+    reference: asserted <= n 2^-52.  Deterministic: two runs, the same bits."""
+    from driving_dirty_amd import ops
+    g = flat_cases[n]
+    out = _slots(dev)
+    ops.sqnorm(g, out[0:1])
+    ops.sqnorm(g, out[1:2])
+    ref = float(g.double().pow(2).sum())
+    got = out.tolist()
+    print(n, got[0], ref, abs(got[0] - ref) / ref)
+    assert got[0] == got[1]
+    assert abs(got[0] - ref) <= n * EPS52 * ref
+
+
+@pytest.mark.parametrize("count", [5, 49])
+def test_sqnorm_multi_matches_fp64(dev, count):
+    """One table, and one tensor more than a table holds (48): a second launch whose partials the last stage adds behind the first's."""
+    from driving_dirty_amd import ops
+    sizes = [SMALL_SIZES[i % 5] for i in range(count)]
+    gs = _slices(dev, sizes, seed=2)
+    out = _slots(dev)
+    ops.sqnorm_multi(gs, out[0:1])
+    ops.sqnorm_multi(gs, out[1:2])
+    ref = float(sum(g.double().pow(2).sum() for g in gs))
+    got = out.tolist()
+    print(count, got[0], ref, abs(got[0] - ref) / ref)
+    assert got[0] == got[1]
+    assert abs(got[0] - ref) <= sum(sizes) * EPS52 * ref
+
+
+# ------------------------------------------------------------------------------------------------ 2. rankb_sqnorm
+def _check_rankb_sqnorm(dev, x, dy, with_bias):
+    from driving_dirty_amd import ops
+    rows, k = x.shape
+    n = dy.shape[1]
+    x, dy = x.to(dev), dy.to(dev)
+    xd, yd = x.double(), dy.double()
+    ref = float(((yd.T @ xd) ** 2).sum() + (yd.sum(0).pow(2).sum() if with_bias else 0.0))
+    assert ref > 0
+    # every fp64 sum of the kernel is over at most max(n, k) products (a Gram entry) or rows^2 entries (the contraction); the products are
+    # exact, so the error is bounded by that many half-ulps of the sum of the ABSOLUTE terms
+    mag = float(((xd.abs() @ xd.abs().T) * (yd.abs() @ yd.abs().T)).sum())
+    tol = (max(n, k) + rows * rows) * EPS52 * mag / ref
+    assert tol < 1e-3, tol
+    out = _slots(dev)
+    ops.rankb_sqnorm(dy, x, with_bias, out[0:1])
+    ops.rankb_sqnorm(dy, x, with_bias, out[1:2])
+    got = out.tolist()
+    print(rows, n, k, with_bias, got[0], ref, abs(got[0] - ref) / ref, tol)
+    assert got[0] == got[1]
+    assert abs(got[0] - ref) / ref <= tol, (abs(got[0] - ref) / ref, tol)
+
+
+@pytest.mark.parametrize("with_bias", [0, 1])
+@pytest.mark.parametrize("n,k", [(4, 4), (64, 260), (132, 4100)])
+@pytest.mark.parametrize("rows", [1, 3, 32, 64])
+def test_rankb_sqnorm_matches_fp64(dev, rows, n, k, with_bias):
+    gen = torch.Generator().manual_seed(1000 * rows + n + k)
+    x = torch.relu(torch.randn(rows, k, generator=gen))
+    dy = 1e-3 * torch.randn(rows, n, generator=gen)
+    _check_rankb_sqnorm(dev, x, dy, with_bias)
+
+
+@pytest.mark.parametrize("with_bias", [0, 1])
+def test_rankb_sqnorm_on_a_batch_whose_row_gradients_cancel(dev, with_bias):
+    """All rows of x nearly one vector, rows of dy one vector with alternating sign: dW = dy^T x is what is left after the rows cancel.
+    A Gram matrix accumulated in fp32 loses it (24 % at a conditioning of 1e7); the derived fp64 tolerance stays below 1e-3."""
+    gen = torch.Generator().manual_seed(7)
+    rows, k, n = 32, 4096, 64
+    x = torch.randn(1, k, generator=gen) + 1e-3 * torch.randn(rows, k, generator=gen)
+    sign = torch.tensor([1.0, -1.0]).repeat(rows // 2)[:, None]
+    dy = sign * torch.randn(1, n, generator=gen) + 1e-3 * torch.randn(rows, n, generator=gen)
+    _check_rankb_sqnorm(dev, x, dy, with_bias)
+
+
+# ------------------------------------------------------------------------------------------------ 3. clip_scale
+@pytest.mark.parametrize("max_norm,grad_scale", [(1.0, 1.0), (10.0, 1.0), (0.5, 0.25), (0.0, 1.0)])
+def test_clip_scale_is_clip_grad_norm_s_formula(dev, max_norm, grad_scale):
+    from driving_dirty_amd import ops
+    slots = [4.0, 0.25, 1e-12]
+    sq = torch.tensor(slots, device=dev, dtype=torch.float64)
+    out3 = torch.full((3,), -1.0, device=dev)
+    ops.clip_scale(sq, max_norm, grad_scale, out3)
+    total = 0.0
+    for s in slots:
+        total += s
+    norm = grad_scale * math.sqrt(total)
+    raw = max_norm / (norm + 1e-6) if max_norm > 0 else 1.0
+    coef = min(1.0, raw)
+    got = out3.tolist()
+    print(got, grad_scale * coef, norm, coef)
+    for g, want in zip(got, (grad_scale * coef, norm, coef)):
+        assert abs(g - want) <= EPS23 * abs(want), (got, want)
+    if max_norm == 0 or raw >= 1.0:
+        assert got[2] == 1.0
+
+
+# ------------------------------------------------------------------------------------------------ 4. _dev == host scalar, bit for bit
+def _pgmv(dev, shapes, seed):
+    gen = torch.Generator().manual_seed(seed)
+    mk = lambda s: torch.randn(s, generator=gen).to(dev)
+    return [(mk(s), mk(s), 0.1 * mk(s), 0.01 * mk(s).abs()) for s in shapes]
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.37])
+def test_dev_scale_adam_entry_points_give_the_host_scalar_bits(dev, scale):
+    from driving_dirty_amd import ops
+    adam = (1e-2, 0.9, 0.999, 1e-8, 3)
+    sdev = torch.tensor([scale], device=dev, dtype=torch.float32)
+    host_scale = float(sdev.item())      # the fp32 value both entry points then see
+    # flat
+    (p, g, m, v), = _pgmv(dev, [(4 * 256 + 3,)], seed=11)
+    a, b = [t.clone() for t in (p, g, m, v)], [t.clone() for t in (p, g, m, v)]
+    ops.adam_step_flat(*a, *adam, host_scale)
+    ops.adam_step_flat(*b, *adam, sdev)
+    assert not torch.equal(a[0], p)
+    for s, t in zip(a, b):
+        assert torch.equal(s, t)
+    # multi: one table, and one tensor more than a table holds
+    for count in (5, 49):
+        quads = _pgmv(dev, [(SMALL_SIZES[i % 5],) for i in range(count)], seed=12)
+        qa, qb = [tuple(t.clone() for t in q) for q in quads], [tuple(t.clone() for t in q) for q in quads]
+        ops.adam_step_multi(qa, *adam, host_scale)
+        ops.adam_step_multi(qb, *adam, sdev)
+        for s, t in zip(qa, qb):
+            for u, w in zip(s, t):
+                assert torch.equal(u, w)
+        assert not torch.equal(qa[-1][0], quads[-1][0])
+    # rank-B, with and without bias
+    rows, n, k = 32, 64, 260
+    gen = torch.Generator().manual_seed(13)
+    x = torch.relu(torch.randn(rows, k, generator=gen)).to(dev)
+    dy = (1e-3 * torch.randn(rows, n, generator=gen)).to(dev)
+    for with_bias in (True, False):
+        (p, _, m, v), (bp, _, bm, bv) = _pgmv(dev, [(n, k), (n,)], seed=14)
+        res = []
+        for s in (host_scale, sdev):
+            t = [u.clone() for u in (p, m, v, bp, bm, bv)]
+            bias = t[3:] if with_bias else [None, None, None]
+            ops.adam_step_rankb(t[0], t[1], t[2], dy, x, *bias, *adam, s)
+            res.append(t)
+        assert not torch.equal(res[0][0], p) and torch.equal(res[0][3], bp) == (not with_bias)
+        for u, w in zip(*res):
+            assert torch.equal(u, w)
+
+
+# ------------------------------------------------------------------------------------------------ 5. TrainStep(gradient_clip_val)
+def _host_norm(model):
+    return float(torch.stack([p.grad.double().pow(2).sum() for p in model.parameters() if p.grad is not None]).sum().sqrt())
+
+
+def _restart(src, dst):
+    with torch.no_grad():
+        for p, q in zip(dst.parameters(), src.parameters()):
+            p.copy_(q)
+    for (_, u), (_, v) in zip(dst.named_buffers(), src.named_buffers()):
+        u.copy_(v)
+
+
+def _half_step(ts, batch, idx):
+    """TrainStep.__call__ up to (not including) optimizer.step()."""
+    ts.model.zero_grad(set_to_none=True)
+    out = ts.model.training_step(batch, idx)
+    out["loss"].backward()
+    ts.sync.finish()
+    return out
+
+
+def _peak_rel(a, b):
+    return float((a - b).abs().max() / a.abs().max().clamp_min(1e-30))
+
+
+def test_trainstep_clips_like_the_materialised_path_clipped_on_the_host(dev):
+    """Reference: TrainStep(fuse_linear_wgrad=False, adam_overlap=False) taken apart, with an fp64 host norm over every p.grad, torch's
+    coefficient and g.mul_(coef) in front of optimizer.step().  (a) the same materialised gradients clipped on the device; (b) the
+    rank-B step: fc1 / head gradients never formed, their norm from the factors.  Every step starts from the reference's parameters."""
+    from driving_dirty_amd import ops
+    from driving_dirty_amd.train import TrainStep
+    r, a, b = _tiny_model(dev), _tiny_model(dev), _tiny_model(dev)
+    tr = TrainStep(r, lr=1e-2, adam_overlap=False, big_numel=4096, scheduler=False, fuse_linear_wgrad=False)
+    ta = tb = None
+    coefs = []
+    for step in range(3):
+        batch = _tiny_batch(dev, step)
+        lr_ = _half_step(tr, batch, step)["loss"]
+        norm = _host_norm(r)
+        if step == 0:
+            c = 0.5 * norm
+            ta = TrainStep(a, lr=1e-2, big_numel=4096, scheduler=False, fuse_linear_wgrad=False, gradient_clip_val=c)
+            tb = TrainStep(b, lr=1e-2, big_numel=4096, scheduler=False, gradient_clip_val=c)
+            assert not ta.overlap and not tb.overlap and not ta.fused
+            assert {id(w) for w in tb.fused} == {id(b.fc1.weight), id(b.ae.encoder.fc1.fc1.weight)}
+        else:
+            _restart(r, a)
+            _restart(r, b)
+        # (r's parameters are still those of the step's start: a and b take the step first, then r)
+        la, lb = ta(batch, step)["loss"], tb(batch, step)["loss"]
+        assert float(la.detach()) == float(lb.detach()) == float(lr_.detach())
+        coef = min(1.0, c / (norm + 1e-6))
+        coefs.append(coef)
+        for p in r.parameters():
+            if p.grad is not None:
+                p.grad.mul_(coef)
+        tr.optimizer.step(grad_scale=tr.sync.grad_scale)
+        print(step, "host norm", norm, "coef", coef, "a", float(ta.optimizer.grad_norm), float(ta.optimizer.clip_coef),
+              "b", float(tb.optimizer.grad_norm), float(tb.optimizer.clip_coef))
+        # (a) identical gradients: only the coefficient's last bit may differ
+        assert abs(float(ta.optimizer.grad_norm) - norm) <= EPS23 * norm
+        assert a.fc1.weight.grad is not None
+        for (name, p), (_, q) in zip(r.named_parameters(), a.named_parameters()):
+            sr, sa = tr.optimizer.state[p], ta.optimizer.state[q]
+            assert sr["step"] == sa["step"] == step + 1
+            assert _peak_rel(sr["exp_avg"], sa["exp_avg"]) <= 5e-7, (step, name)
+            assert _peak_rel(sr["exp_avg_sq"], sa["exp_avg_sq"]) <= 1e-6, (step, name)
+            assert _peak_rel(p.detach(), q.detach()) <= 1e-6, (step, name)
+        # (b) rank-B: no gradient tensor for the fused layers, their norm from the factors
+        assert b.fc1.weight.grad is None and b.fc1.bias.grad is None and b.ae.encoder.fc1.fc1.weight.grad is None
+        assert abs(float(tb.optimizer.grad_norm) - norm) <= 1e-6 * norm
+        assert abs(float(tb.optimizer.clip_coef) - coef) <= 2e-6 * coef
+        for (name, p), (_, q) in zip(r.named_parameters(), b.named_parameters()):
+            if name.endswith("fc1.fc1.bias"):      # its gradient is exactly zero in front of a train-mode BatchNorm: Adam steps on the sign
+                continue                           # of rounding noise on either path (tests/test_gpu_round5.py)
+            assert _peak_rel(p.detach(), q.detach()) <= 1e-6, (step, name)
+    # c is half the FIRST step's norm: that step must clip by about a half, otherwise the comparison shows nothing.  The later steps keep
+    # the same c while the norm falls with the training (3.6, 2.0, 0.69 on the tiny model: coef 0.5, 0.89, 1.0), so they also cover a
+    # light clip and the clamp at 1 inside a whole step; nothing is asserted about their coefficients.
+    assert 0.3 < coefs[0] < 0.8, coefs
+    for t in (tr, ta, tb):
+        t.close()
+    assert not ops.RANKB
+
+
+def test_a_clip_value_far_above_the_norm_changes_no_bit(dev):
+    """coef = 1.0 exactly: grad_scale x coef is the host's grad_scale, and the _dev kernels give the host-scalar kernels' bits."""
+    from driving_dirty_amd.train import TrainStep
+    a, b, twin = _tiny_model(dev), _tiny_model(dev), _tiny_model(dev)
+    ta = TrainStep(a, lr=1e-2, adam_overlap=False, big_numel=4096, scheduler=False)
+    tt = TrainStep(twin, lr=1e-2, adam_overlap=False, big_numel=4096, scheduler=False, fuse_linear_wgrad=False)
+    _half_step(tt, _tiny_batch(dev, 0), 0)
+    norm0 = _host_norm(twin)
+    tt.close()
+    tb = TrainStep(b, lr=1e-2, big_numel=4096, scheduler=False, gradient_clip_val=1e6 * norm0)
+    for step in range(3):
+        batch = _tiny_batch(dev, step)
+        ta(batch, step)
+        tb(batch, step)
+        assert float(tb.optimizer.clip_coef) == 1.0
+        if step == 0:
+            assert abs(float(tb.optimizer.grad_norm) - norm0) <= 1e-6 * norm0
+        for (name, p), (_, q) in zip(a.named_parameters(), b.named_parameters()):
+            assert torch.equal(p.detach(), q.detach()), (step, name)
+            sa, sb = ta.optimizer.state[p], tb.optimizer.state[q]
+            assert torch.equal(sa["exp_avg"], sb["exp_avg"]) and torch.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), (step, name)
+    ta.close()
+    tb.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. track_grad_norm alone
+@pytest.mark.parametrize("overlap", [True, False])
+def test_track_grad_norm_alone_changes_nothing_and_logs_the_norm(dev, overlap):
+    from driving_dirty_amd.train import TrainStep
+    a, b, twin = _tiny_model(dev), _tiny_model(dev), _tiny_model(dev)
+    ta = TrainStep(a, lr=1e-2, adam_overlap=overlap, big_numel=4096, scheduler=False)
+    tb = TrainStep(b, lr=1e-2, adam_overlap=overlap, big_numel=4096, scheduler=False, track_grad_norm=True)
+    tt = TrainStep(twin, lr=1e-2, adam_overlap=False, big_numel=4096, scheduler=False, fuse_linear_wgrad=False)
+    assert tb.overlap == overlap and tb.fused
+    for step in range(3):
+        batch = _tiny_batch(dev, step)
+        _restart(b, twin)
+        _half_step(tt, batch, step)
+        norm = _host_norm(twin)
+        ta(batch, step)
+        out = tb(batch, step)
+        got = out["log"]["grad_2.0_norm_total"]
+        assert got.is_cuda and got is tb.optimizer.grad_norm
+        print(overlap, step, float(got), norm)
+        assert abs(float(got) - norm) <= 1e-6 * norm
+        assert b.fc1.weight.grad is None
+        for (name, p), (_, q) in zip(a.named_parameters(), b.named_parameters()):
+            assert torch.equal(p.detach(), q.detach()), (step, name)
+    for t in (ta, tb, tt):
+        t.close()
+
+
+# ------------------------------------------------------------------------------------------------ 7. refusals
+def test_clipping_refuses_the_overlapped_arrangement(dev):
+    from driving_dirty_amd import ops
+    from driving_dirty_amd.optim import HipAdam
+    from driving_dirty_amd.train import TrainStep
+    model = _tiny_model(dev)
+    with pytest.raises(ValueError):
+        TrainStep(model, lr=1e-2, adam_overlap=True, big_numel=4096, scheduler=False, gradient_clip_val=1.0)
+    opt = HipAdam(model.parameters(), lr=1e-2)
+    opt.overlap_with_backward(big_numel=4096)
+    try:
+        with pytest.raises(RuntimeError):
+            opt.set_clip(1.0)
+        opt.set_clip(0.0, track=True)      # reading the gradients is fine in either arrangement
+    finally:
+        opt.close()
+    ts = TrainStep(model, lr=1e-2, big_numel=4096, scheduler=False, gradient_clip_val=1.0)
+    assert ts.fused and ops.RANKB
+    ts.close()
+    assert not ops.RANKB
