@@ -19,10 +19,16 @@
 //    same way.  No kernel waits for another workgroup: an atomicMin that loses a race returns the winner's value and the loop goes on
 //    from there with a strictly smaller pair.  Stale (cached) reads of the parent array are harmless: an old parent is still an
 //    ancestor in the same tree with a smaller index.
-// b. dd_component_boxes: a. into the workspace, then per component pixel count and extents by integer atomics at the root's slot (one
-//    set of atomics per horizontal run inside a 64-pixel segment, found with a ballot -- no loop), then a row-count / row-scan /
-//    in-row-scan compaction that orders the survivors by label.  Integer atomics only, so the result is deterministic.
-// b'. dd_component_obb: the same components, the same survivors in the same order, but each fitted with an ORIENTED box: the principal
+// b. THE FIT: labels -> boxes.  ONE pipeline (fit_launch<kRegions>, the only list of its launches), two instantiations, four entry points:
+//    dd_component_boxes / dd_component_obb (kRegions = false: a. into the workspace, then the fit of those labels) and dd_labelled_boxes /
+//    dd_labelled_obb (kRegions = true: the fit of a label image the caller brings, b''.).  The launches: label (a., whose flatten zeroes the
+//    roots' records) or region_init; stats: per component pixel count and extents by integer atomics at the root's slot (one set of atomics
+//    per horizontal run inside a 64-pixel segment, found with a ballot -- no loop); row count / row scan / in-row scan: a compaction that
+//    orders the survivors by label; then emit, or b'.'s four launches.  Integer atomics only, so the result is deterministic.
+//    The two instantiations differ in three places and nowhere else: where a run ends (run_length: component_run / region_run), which record
+//    is zeroed (the root's / the one at pixel label - 1), and the top row (the root's row / a real maximum of H - 1 - y kept in `top`).
+//    kRegions = false touches no `top` array, loads no lab[v - 1] and launches nothing more than it needs.
+// b'. fit = oriented: the same components, the same survivors in the same order, but each fitted with an ORIENTED box: the principal
 //    axis of its pixel cloud from exact integer second moments, then the extents of the pixel centres along and across that axis.
 //    After b.'s labelling, count and ordering launches: slot (the emit structure) gives every survivor its output slot and a zeroed
 //    record there; moment (the run structure) adds each run's closed-form sums to the record with 64-bit integer atomics; extent (the
@@ -31,13 +37,11 @@
 //    corners.  Integer add and integer max only: bit-identical from launch to launch.  Every thread that needs the heading evaluates
 //    the one function heading() on the same integers, so all of them agree bit for bit.  No loop in any of the four kernels except the
 //    slot kernel's walk along its row (W / 256 rounds, as in emit_boxes_kernel).
-// b''. dd_split_components / dd_labelled_boxes / dd_labelled_obb: marker-based splitting of blobs joined by a neck (the rule
-//    is stated in include/dd_hotpath.h).  erode (LDS, separable minimum) -> a.'s launches on the core map -> grow (g Jacobi rounds between two
-//    LDS buffers, one barrier per round, smallest neighbouring label wins) -> a.'s launches on what is left -> merge.  The result is a LABEL
-//    IMAGE whose regions are sets of equal labels, label - 1 being SOME pixel of the region (not its first).  The kernels of b. and b'. take
-//    such an image through their kRegions = true instantiations: a horizontal run ends where the label changes, the record that is zeroed
-//    is the one at pixel label - 1, and the top row is a real maximum of H - 1 - y.  The kRegions = false instantiations are the kernels of
-//    b. and b'., instruction for instruction.  LOOP BOUNDS: erode 2 r + 1 <= 17 taps, grow g <= 16 rounds of at most 16 pixels per thread.
+// b''. dd_split_components: marker-based splitting of blobs joined by a neck (the rule is stated in include/dd_hotpath.h).
+//    erode (LDS, separable minimum) -> a.'s launches on the core map -> grow (g Jacobi rounds between two LDS buffers, one barrier per
+//    round, smallest neighbouring label wins) -> a.'s launches on what is left -> merge.  The result is a LABEL IMAGE whose regions are
+//    sets of equal labels, label - 1 being SOME pixel of the region (not its first): what b.'s kRegions = true instantiation fits.
+//    LOOP BOUNDS: erode 2 r + 1 <= 17 taps, grow g <= 16 rounds of at most 16 pixels per thread.
 // c. dd_box_iou_ats: one thread per box pair, fp64, Green's theorem over the boundary of the intersection (fully unrolled: no
 //    indexed local array, no scratch), then one workgroup per sample for max over set 1, the five thresholds and the weighted mean.
 #include "dd_common.h"
@@ -208,12 +212,24 @@ int label_launch(const float* maps, float threshold, int* labels, Stats* stats, 
   return 0;
 }
 
+long align16(long v) { return (v + 15) & ~15L; }
+
 bool shape_ok(int batch, int H, int W) { return batch >= 1 && batch <= kMaxBatch && H >= 1 && W >= 1 && H <= kMaxSide && W <= kMaxSide; }
 
 // ------------------------------------------------------------------------------------------------ b. component boxes
 // One wave per 64-pixel segment of a row.  Horizontally adjacent foreground pixels share their label, so a run of set bits in the
 // ballot is one component: its first lane adds the run to the root's slot.
-// region_run (kRegions, a label image, b''.): the length of the run of EQUAL labels that begins at this lane, 0 when none does -- a run
+// component_run (kRegions = false, dd_label_components' labels): whether a run of foreground begins at this lane, and then its length.  (A bool
+// and not "0 when none does", as region_run has it: with that the compiler forms the length before it leaves, for 2-3 more registers.)
+__device__ __forceinline__ bool component_run(int v, int lane, int& len) {
+  const unsigned long long mask = __ballot(v != 0);
+  if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return false;
+  const unsigned long long inv = ~(mask >> lane);                     // lowest zero bit = end of the run; none: the run fills the segment
+  len = inv ? __ffsll((long long)inv) - 1 : 64;
+  return true;
+}
+
+// region_run (kRegions = true, a label image, b''.): the length of the run of EQUAL labels that begins at this lane, 0 when none does -- a run
 // also ends where the label changes.  A label outside [1, n], or one whose pixel label - 1 does not carry it, belongs to no region and
 // starts no run, so no record outside the sample's n slots is ever touched, whatever the image holds.  v: sanitised in place.
 __device__ __forceinline__ int region_run(const int* lab, int n, int& v, int lane) {
@@ -227,36 +243,27 @@ __device__ __forceinline__ int region_run(const int* lab, int n, int& v, int lan
   return rest ? __ffsll((long long)rest) : 64 - lane;
 }
 
+// whether a run begins at this lane of the wave's 64-pixel segment, and then its length; lab = the sample's labels, n = H * W
 template <bool kRegions>
-__device__ __forceinline__ void run_stats_body(const int* __restrict__ labels, Stats* __restrict__ stats, int* __restrict__ top, int H, int W) {
+__device__ __forceinline__ bool run_length(const int* lab, int n, int& v, int lane, int& len) {
+  if constexpr (kRegions) return (len = region_run(lab, n, v, lane)) != 0;
+  else return component_run(v, lane, len);
+}
+
+// `top` exists for a label image only (null otherwise): label - 1 need not lie in the region's first row
+template <bool kRegions>
+__global__ __launch_bounds__(kThreads) void run_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int H, int W, int* __restrict__ top) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
   int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
   int len;
-  if constexpr (kRegions) {
-    len = region_run(labels + base, H * W, v, lane);
-    if (len == 0) return;
-  } else {
-    const unsigned long long mask = __ballot(v != 0);
-    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-    const unsigned long long inv = ~(mask >> lane);                   // lowest zero bit = end of the run; none: the run fills the segment
-    len = inv ? __ffsll((long long)inv) - 1 : 64;
-  }
+  if (!run_length<kRegions>(labels + base, H * W, v, lane, len)) return;
   Stats* s = stats + base + (v - 1);
   atomicAdd(&s->count, len);
   atomicMax(&s->w1_minus_c0, W - 1 - x);
   atomicMax(&s->c1, x + len - 1);
   atomicMax(&s->r1, y);
-  if (kRegions) atomicMax(top + base + (v - 1), H - 1 - y);            // label - 1 need not lie in the region's first row
-}
-
-__global__ __launch_bounds__(kThreads) void run_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int H, int W) {
-  run_stats_body<false>(labels, stats, nullptr, H, W);
-}
-
-__global__ __launch_bounds__(kThreads) void region_stats_kernel(const int* __restrict__ labels, Stats* __restrict__ stats, int* __restrict__ top, int H,
-                                                                int W) {
-  run_stats_body<true>(labels, stats, top, H, W);
+  if constexpr (kRegions) atomicMax(top + base + (v - 1), H - 1 - y);
 }
 
 // flatten_kernel's second duty for a label image: the records of the pixels that name a region (labels[p] == p + 1) start at zero
@@ -323,9 +330,13 @@ __global__ __launch_bounds__(kThreads) void row_scan_kernel(const int* __restric
   if (threadIdx.x == 0) counts[s] = carry;                            // uncapped
 }
 
+// kRegions: the pixel label - 1 that names a region need not lie in its top row, so r0 comes from `top` (null otherwise), a real maximum
+// over the region's rows.  A component's root is its first pixel in raster order: its row is r0.  (While the two were separate kernels the
+// compiler placed one scalar OR of the kRegions = false one differently from what it does for this template; nothing else differs.)
+template <bool kRegions>
 __global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, const int* __restrict__ rowcnt,
                                                               const int* __restrict__ rowbase, float* __restrict__ boxes, int H, int W,
-                                                              int min_pixels, int max_boxes) {
+                                                              int min_pixels, int max_boxes, const int* __restrict__ top) {
   __shared__ int wsum[kThreads / 64];
   const int y = blockIdx.x, s = blockIdx.y;
   if (rowcnt[s * H + y] == 0) return;                                 // uniform
@@ -339,7 +350,9 @@ __global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restr
     carry += total;
     if (f && slot < max_boxes) {                                      // the only store: slot in [0, max_boxes)
       const Stats st = stats[base + y * W + x];
-      const int c0 = W - 1 - st.w1_minus_c0, c1 = st.c1, r0 = y, r1 = st.r1;      // the root is the first pixel in raster order: its row is r0
+      int r0 = y;
+      if constexpr (kRegions) r0 = H - 1 - top[base + y * W + x];
+      const int c0 = W - 1 - st.w1_minus_c0, c1 = st.c1, r1 = st.r1;
       const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;        // exact: multiples of 0.5 far below 2^23
       const float xmin = ((float)c0 - hw) / 10.f, xmax = ((float)(c1 + 1) - hw) / 10.f;
       const float ymin = (hh - (float)(r1 + 1)) / 10.f, ymax = (hh - (float)r0) / 10.f;
@@ -349,39 +362,6 @@ __global__ __launch_bounds__(kThreads) void emit_boxes_kernel(const int* __restr
     }
   }
 }
-
-// emit_boxes_kernel for a label image (b''.): the pixel label - 1 that names a region need not lie in its top row, so r0 comes from `top`.
-// A kernel of its own, not an instantiation of a shared body as the run kernels are: with the body inlined the compiler orders one
-// scalar OR of emit_boxes_kernel differently, and that kernel is kept instruction for instruction.
-__global__ __launch_bounds__(kThreads) void emit_region_boxes_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
-                                                                     const int* __restrict__ top, const int* __restrict__ rowcnt,
-                                                                     const int* __restrict__ rowbase, float* __restrict__ boxes, int H, int W,
-                                                              int min_pixels, int max_boxes) {
-  __shared__ int wsum[kThreads / 64];
-  const int y = blockIdx.x, s = blockIdx.y;
-  if (rowcnt[s * H + y] == 0) return;                                 // uniform
-  const long base = (long)s * H * W;
-  int carry = rowbase[s * H + y];
-  for (int x0 = 0; x0 < W; x0 += kThreads) {
-    const int x = x0 + threadIdx.x;
-    const bool f = x < W && survivor(labels + base, stats + base, y * W + x, min_pixels);
-    int total;
-    const int slot = carry + block_scan(f, wsum, total);
-    carry += total;
-    if (f && slot < max_boxes) {                                      // the only store: slot in [0, max_boxes)
-      const Stats st = stats[base + y * W + x];
-      const int c0 = W - 1 - st.w1_minus_c0, c1 = st.c1, r0 = H - 1 - top[base + y * W + x], r1 = st.r1;      // a real maximum over the region's rows
-      const float hw = 0.5f * (float)W, hh = 0.5f * (float)H;        // exact: multiples of 0.5 far below 2^23
-      const float xmin = ((float)c0 - hw) / 10.f, xmax = ((float)(c1 + 1) - hw) / 10.f;
-      const float ymin = (hh - (float)(r1 + 1)) / 10.f, ymax = (hh - (float)r0) / 10.f;
-      float* o = boxes + ((long)s * max_boxes + slot) * 8;
-      o[0] = xmax; o[1] = xmax; o[2] = xmin; o[3] = xmin;
-      o[4] = ymax; o[5] = ymin; o[6] = ymax; o[7] = ymin;
-    }
-  }
-}
-
-long align16(long v) { return (v + 15) & ~15L; }
 
 // ------------------------------------------------------------------------------------------------ b'. oriented boxes
 struct Obb {          // per survivor, at its output slot; zero initialises all of it (the four extents are maxima of codes that are never 0)
@@ -442,21 +422,14 @@ __device__ __forceinline__ Obb* obb_record(const Stats* __restrict__ stats, Obb*
 
 // run_stats_kernel's structure.  The run [x, x + len) of row y adds sum 1, X, Y, X^2, X Y, Y^2 in closed form (len <= 64: no overflow).
 template <bool kRegions>
-__device__ __forceinline__ void obb_moment_body(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs, int H, int W,
-                                                int min_pixels, int max_boxes) {
+__global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
   int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
-  long long len;
-  if constexpr (kRegions) {
-    len = region_run(labels + base, H * W, v, lane);
-    if (len == 0) return;
-  } else {
-    const unsigned long long mask = __ballot(v != 0);
-    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-    const unsigned long long inv = ~(mask >> lane);
-    len = inv ? __ffsll((long long)inv) - 1 : 64;
-  }
+  int run;
+  if (!run_length<kRegions>(labels + base, H * W, v, lane, run)) return;
+  const long long len = run;
   Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
   if (!r) return;
   const long long tri = len * (len - 1) / 2, sx = len * x + tri;
@@ -468,34 +441,16 @@ __device__ __forceinline__ void obb_moment_body(const int* __restrict__ labels, 
   atomicAdd((unsigned long long*)&r->syy, (unsigned long long)(len * y * y));
 }
 
-__global__ __launch_bounds__(kThreads) void obb_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
-                                                              int H, int W, int min_pixels, int max_boxes) {
-  obb_moment_body<false>(labels, stats, recs, H, W, min_pixels, max_boxes);
-}
-
-__global__ __launch_bounds__(kThreads) void obb_region_moment_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
-                                                                     Obb* __restrict__ recs, int H, int W, int min_pixels, int max_boxes) {
-  obb_moment_body<true>(labels, stats, recs, H, W, min_pixels, max_boxes);
-}
-
 // After the moment launch.  u = (X + .5) c + (Y + .5) s and v = -(X + .5) s + (Y + .5) c are monotone in X along a row (a rounded product
 // and a rounded sum are monotone in their operand), so the run's extremes are at its two end pixels.
 template <bool kRegions>
-__device__ __forceinline__ void obb_extent_body(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs, int H, int W,
-                                                int min_pixels, int max_boxes) {
+__global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
+                                                              int H, int W, int min_pixels, int max_boxes) {
   const int lane = threadIdx.x, x = blockIdx.x * 64 + lane, y = blockIdx.y * 4 + threadIdx.y;
   const long base = (long)blockIdx.z * H * W;
   int v = (x < W && y < H) ? labels[base + (long)y * W + x] : 0;
   int len;
-  if constexpr (kRegions) {
-    len = region_run(labels + base, H * W, v, lane);
-    if (len == 0) return;
-  } else {
-    const unsigned long long mask = __ballot(v != 0);
-    if (v == 0 || (lane > 0 && ((mask >> (lane - 1)) & 1ull))) return;
-    const unsigned long long inv = ~(mask >> lane);
-    len = inv ? __ffsll((long long)inv) - 1 : 64;
-  }
+  if (!run_length<kRegions>(labels + base, H * W, v, lane, len)) return;
   Obb* r = obb_record(stats, recs, base, blockIdx.z, v, min_pixels, max_boxes);
   if (!r) return;
   double c, s;
@@ -506,16 +461,6 @@ __device__ __forceinline__ void obb_extent_body(const int* __restrict__ labels, 
   atomicMax(&r->neg_u0, code(-fmin(ua, ub)));
   atomicMax(&r->v1, code(fmax(va, vb)));
   atomicMax(&r->neg_v0, code(-fmin(va, vb)));
-}
-
-__global__ __launch_bounds__(kThreads) void obb_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats, Obb* __restrict__ recs,
-                                                              int H, int W, int min_pixels, int max_boxes) {
-  obb_extent_body<false>(labels, stats, recs, H, W, min_pixels, max_boxes);
-}
-
-__global__ __launch_bounds__(kThreads) void obb_region_extent_kernel(const int* __restrict__ labels, const Stats* __restrict__ stats,
-                                                                     Obb* __restrict__ recs, int H, int W, int min_pixels, int max_boxes) {
-  obb_extent_body<true>(labels, stats, recs, H, W, min_pixels, max_boxes);
 }
 
 // one thread per stored box: extents moved outwards by pad (|c| + |s|), the ring (u1,v1), (u1,v0), (u0,v0), (u0,v1) rotated back to
@@ -646,41 +591,102 @@ __global__ __launch_bounds__(kThreads) void merge_labels_kernel(int* __restrict_
 
 bool split_ok(int split_px, int grow_iters) { return split_px >= 1 && split_px <= kMaxSplit && grow_iters >= 0 && grow_iters <= kMaxGrow; }
 
-// the launches that fit a label image: shared by dd_labelled_boxes and dd_labelled_obb up to the row scan
-struct RegionWs {
+// ------------------------------------------------------------------------------------------------ b. b'. b''. the fit pipeline on the host
+// One pipeline, two instantiations: kRegions = false labels `maps > threshold` into the workspace first (dd_component_boxes, dd_component_obb),
+// kRegions = true fits the caller's label image (dd_labelled_boxes, dd_labelled_obb).  `who` is the entry's name, for the messages.
+struct FitWs {
+  int* labels;        // components only
   Stats* stats;
-  int *top, *rowcnt, *rowbase;
-  Obb* recs;
+  int *top;           // label image only
+  int *rowcnt, *rowbase;
+  Obb* recs;          // oriented only
 };
 
-long region_ws_bytes(int batch, int H, int W) {
-  const long n = (long)batch * H * W;
-  return n * (long)sizeof(Stats) + align16(n * (long)sizeof(int)) + 2 * align16((long)batch * H * (long)sizeof(int));
+// components: labels | stats | rowcnt | rowbase | recs; label image: stats | top | rowcnt | rowbase | recs.  Every part starts 16-byte aligned.
+FitWs fit_ws(void* workspace, bool regions, int batch, int H, int W) {
+  const long n = (long)batch * H * W, ints = align16(n * (long)sizeof(int)), rows = align16((long)batch * H * (long)sizeof(int));
+  char* p = (char*)workspace;
+  FitWs w{};
+  if (!regions) { w.labels = (int*)p; p += ints; }
+  w.stats = (Stats*)p; p += n * (long)sizeof(Stats);
+  if (regions) { w.top = (int*)p; p += ints; }
+  w.rowcnt = (int*)p; p += rows;
+  w.rowbase = (int*)p; p += rows;
+  w.recs = (Obb*)p;
+  return w;
 }
 
-RegionWs region_ws(void* workspace, int batch, int H, int W) {
-  const long n = (long)batch * H * W;
-  RegionWs r;
-  r.stats = (Stats*)workspace;
-  r.top = (int*)((char*)r.stats + n * (long)sizeof(Stats));
-  r.rowcnt = (int*)((char*)r.top + align16(n * (long)sizeof(int)));
-  r.rowbase = (int*)((char*)r.rowcnt + align16((long)batch * H * (long)sizeof(int)));
-  r.recs = (Obb*)((char*)r.rowbase + align16((long)batch * H * (long)sizeof(int)));
-  return r;
+// refuses with the entry's limits in the message
+bool fit_shape_ok(const char* who, bool oriented, int batch, int H, int W, int max_boxes) {
+  if (oriented ? obb_shape_ok(batch, H, W, max_boxes) : shape_ok(batch, H, W)) return true;
+  if (oriented)
+    dd_fail(DD_ERR_UNSUPPORTED, "%s: batch in [1,%d], height and width in [1,%d] (the second moments are exact in 64-bit integers up to "
+            "there), max_boxes in [1,%d] (got %d x %d x %d, max_boxes %d)", who, kMaxBatch, kObbMaxSide, kObbMaxBoxes, batch, H, W, max_boxes);
+  else
+    dd_fail(DD_ERR_UNSUPPORTED, "%s: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", who, kMaxBatch, kMaxSide, batch, H, W);
+  return false;
 }
 
-int region_count_launch(const int* labels, const RegionWs& ws, int* counts, int min_pixels, int batch, int H, int W, hipStream_t st) {
-  const int n = H * W;
-  hipLaunchKernelGGL(region_init_kernel, dim3((n + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, labels, ws.stats, ws.top, n);
-  DD_LAUNCH_CHECK("labelled boxes init");
-  hipLaunchKernelGGL(region_stats_kernel, dim3((W + 63) / 64, (H + 3) / 4, batch), dim3(64, 4), 0, st, labels, ws.stats, ws.top, H, W);
-  DD_LAUNCH_CHECK("labelled boxes stats");
-  hipLaunchKernelGGL(row_count_kernel, dim3(H, batch), dim3(kThreads), 0, st, labels, (const Stats*)ws.stats, ws.rowcnt, H, W, min_pixels);
-  DD_LAUNCH_CHECK("labelled boxes row counts");
-  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, (const int*)ws.rowcnt, ws.rowbase, counts, H);
-  DD_LAUNCH_CHECK("labelled boxes row scan");
+// the same for both layouts: one int and one Stats per pixel, two ints per row, one Obb per box of the oriented fit; -1 after dd_fail
+int64_t fit_ws_bytes(const char* who, bool oriented, int batch, int H, int W, int max_boxes) {
+  if (!fit_shape_ok(who, oriented, batch, H, W, max_boxes)) return -1;
+  const long n = (long)batch * H * W;
+  return align16(n * (long)sizeof(int)) + n * (long)sizeof(Stats) + 2 * align16((long)batch * H * (long)sizeof(int)) +
+         (oriented ? (long)batch * max_boxes * (long)sizeof(Obb) : 0);
+}
+
+int fit_check(const char* who, bool oriented, const void* src, const float* boxes, const int32_t* counts, int min_pixels, int max_boxes, float pad_px,
+              int batch, int H, int W, const void* workspace, int64_t workspace_bytes) {
+  DD_REQUIRE(src && boxes && counts && workspace, DD_ERR_BAD_ARG, "%s: null pointer", who);
+  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "%s: min_pixels and max_boxes must be positive", who);
+  DD_REQUIRE(!oriented || (pad_px >= 0.f && pad_px <= (float)kObbMaxSide), DD_ERR_BAD_ARG, "%s: pad_px must lie in [0,%d]", who, kObbMaxSide);
+  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "%s: workspace must be 16-byte aligned", who);
+  const int64_t need = fit_ws_bytes(who, oriented, batch, H, W, max_boxes);
+  if (need < 0) return DD_ERR_UNSUPPORTED;
+  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
   return 0;
 }
+
+int fit_launched(const char* who, const char* stage) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : dd_fail(DD_ERR_LAUNCH, "%s %s: %s", who, stage, hipGetErrorString(e));
+}
+
+#define FIT_LAUNCH(stage, kernel, grid, block, ...)                        \
+  do {                                                                     \
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);            \
+    if (const int rc_ = fit_launched(who, stage)) return rc_;             \
+  } while (0)
+
+// THE list of the fit's launches.  src: the maps (kRegions = false; flatten_kernel zeroes the roots' Stats) or the label image.
+template <bool kRegions>
+int fit_launch(const char* who, bool oriented, const void* src, float threshold, int min_pixels, int max_boxes, float pad_px, float* boxes,
+               int32_t* counts, int64_t* moments, int batch, int H, int W, void* workspace, hipStream_t st) {
+  const FitWs ws = fit_ws(workspace, kRegions, batch, H, W);
+  const int* labels = kRegions ? (const int*)src : ws.labels;
+  const dim3 runs((W + 63) / 64, (H + 3) / 4, batch), run_block(64, 4), rows(H, batch), block(kThreads);
+  if constexpr (kRegions) {
+    FIT_LAUNCH("init", region_init_kernel, dim3((H * W + kThreads - 1) / kThreads, batch), block, labels, ws.stats, ws.top, H * W);
+  } else {
+    const int rc = label_launch((const float*)src, threshold, ws.labels, ws.stats, batch, H, W, st);
+    if (rc) return rc;
+  }
+  FIT_LAUNCH("stats", run_stats_kernel<kRegions>, runs, run_block, labels, ws.stats, H, W, ws.top);
+  FIT_LAUNCH("row counts", row_count_kernel, rows, block, labels, ws.stats, ws.rowcnt, H, W, min_pixels);
+  FIT_LAUNCH("row scan", row_scan_kernel, dim3(batch), block, ws.rowcnt, ws.rowbase, counts, H);
+  if (!oriented) {
+    FIT_LAUNCH("emit", emit_boxes_kernel<kRegions>, rows, block, labels, ws.stats, ws.rowcnt, ws.rowbase, boxes, H, W, min_pixels, max_boxes, ws.top);
+    return 0;
+  }
+  FIT_LAUNCH("slots", obb_slot_kernel, rows, block, labels, ws.stats, ws.rowcnt, ws.rowbase, ws.recs, H, W, min_pixels, max_boxes);
+  FIT_LAUNCH("moments", obb_moment_kernel<kRegions>, runs, run_block, labels, ws.stats, ws.recs, H, W, min_pixels, max_boxes);
+  FIT_LAUNCH("extents", obb_extent_kernel<kRegions>, runs, run_block, labels, ws.stats, ws.recs, H, W, min_pixels, max_boxes);
+  FIT_LAUNCH("emit", obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), block, ws.recs, counts, pad_px, boxes, (long long*)moments, H, W,
+             max_boxes);
+  return 0;
+}
+
+#undef FIT_LAUNCH
 
 // ------------------------------------------------------------------------------------------------ c. IoU and ATS
 __device__ __forceinline__ double cross2(double ax, double ay, double bx, double by) { return ax * by - ay * bx; }
@@ -845,92 +851,25 @@ int dd_label_components(const float* maps, float threshold, int32_t* labels, int
 }
 
 int64_t dd_component_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
-  if (!shape_ok(batch, height, width)) {
-    dd_fail(DD_ERR_UNSUPPORTED, "component_boxes: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", kMaxBatch, kMaxSide, batch,
-            height, width);
-    return -1;
-  }
-  const long n = (long)batch * height * width;
-  return align16(n * (long)sizeof(int)) + n * (long)sizeof(Stats) + 2 * align16((long)batch * height * (long)sizeof(int));
+  return fit_ws_bytes("component_boxes", false, batch, height, width, 0);
 }
 
 int dd_component_boxes(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch,
                        int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
-  DD_REQUIRE(maps && boxes && counts && workspace, DD_ERR_BAD_ARG, "component_boxes: null pointer");
-  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "component_boxes: min_pixels and max_boxes must be positive");
-  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "component_boxes: workspace must be 16-byte aligned");
-  const int64_t need = dd_component_boxes_workspace_bytes(batch, height, width);
-  if (need < 0) return DD_ERR_UNSUPPORTED;
-  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "component_boxes: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-             (long long)need);
-  const long n = (long)batch * height * width;
-  char* ws = (char*)workspace;
-  int* labels = (int*)ws;
-  Stats* stats = (Stats*)(ws + align16(n * (long)sizeof(int)));
-  int* rowcnt = (int*)((char*)stats + n * (long)sizeof(Stats));
-  int* rowbase = (int*)((char*)rowcnt + align16((long)batch * height * (long)sizeof(int)));
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = label_launch(maps, threshold, labels, stats, batch, height, width, st);      // zeroes the roots' slots
-  if (rc) return rc;
-  hipLaunchKernelGGL(run_stats_kernel, dim3((width + 63) / 64, (height + 3) / 4, batch), dim3(64, 4), 0, st, labels, stats, height, width);
-  DD_LAUNCH_CHECK("component_boxes stats");
-  hipLaunchKernelGGL(row_count_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, height, width, min_pixels);
-  DD_LAUNCH_CHECK("component_boxes row counts");
-  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, rowcnt, rowbase, counts, height);
-  DD_LAUNCH_CHECK("component_boxes row scan");
-  hipLaunchKernelGGL(emit_boxes_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, rowbase, boxes, height, width,
-                     min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("component_boxes emit");
-  return 0;
+  const int rc = fit_check("component_boxes", false, maps, boxes, counts, min_pixels, max_boxes, 0.f, batch, height, width, workspace, workspace_bytes);
+  return rc ? rc : fit_launch<false>("component_boxes", false, maps, threshold, min_pixels, max_boxes, 0.f, boxes, counts, nullptr, batch, height, width,
+                                     workspace, (hipStream_t)stream);
 }
 
 int64_t dd_component_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes) {
-  if (!obb_shape_ok(batch, height, width, max_boxes)) {
-    dd_fail(DD_ERR_UNSUPPORTED, "component_obb: batch in [1,%d], height and width in [1,%d] (the second moments are exact in 64-bit integers up to "
-            "there), max_boxes in [1,%d] (got %d x %d x %d, max_boxes %d)", kMaxBatch, kObbMaxSide, kObbMaxBoxes, batch, height, width, max_boxes);
-    return -1;
-  }
-  return dd_component_boxes_workspace_bytes(batch, height, width) + (long)batch * max_boxes * (long)sizeof(Obb);
+  return fit_ws_bytes("component_obb", true, batch, height, width, max_boxes);
 }
 
 int dd_component_obb(const float* maps, float threshold, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts,
                      int64_t* moments, int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
-  DD_REQUIRE(maps && boxes && counts && workspace, DD_ERR_BAD_ARG, "component_obb: null pointer");
-  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "component_obb: min_pixels and max_boxes must be positive");
-  DD_REQUIRE(pad_px >= 0.f && pad_px <= (float)kObbMaxSide, DD_ERR_BAD_ARG, "component_obb: pad_px must lie in [0,%d]", kObbMaxSide);
-  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "component_obb: workspace must be 16-byte aligned");
-  const int64_t need = dd_component_obb_workspace_bytes(batch, height, width, max_boxes);
-  if (need < 0) return DD_ERR_UNSUPPORTED;
-  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "component_obb: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-             (long long)need);
-  const long n = (long)batch * height * width;
-  char* ws = (char*)workspace;
-  int* labels = (int*)ws;
-  Stats* stats = (Stats*)(ws + align16(n * (long)sizeof(int)));
-  int* rowcnt = (int*)((char*)stats + n * (long)sizeof(Stats));
-  int* rowbase = (int*)((char*)rowcnt + align16((long)batch * height * (long)sizeof(int)));
-  Obb* recs = (Obb*)((char*)rowbase + align16((long)batch * height * (long)sizeof(int)));
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = label_launch(maps, threshold, labels, stats, batch, height, width, st);
-  if (rc) return rc;
-  const dim3 runs((width + 63) / 64, (height + 3) / 4, batch);
-  hipLaunchKernelGGL(run_stats_kernel, runs, dim3(64, 4), 0, st, labels, stats, height, width);
-  DD_LAUNCH_CHECK("component_obb stats");
-  hipLaunchKernelGGL(row_count_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, height, width, min_pixels);
-  DD_LAUNCH_CHECK("component_obb row counts");
-  hipLaunchKernelGGL(row_scan_kernel, dim3(batch), dim3(kThreads), 0, st, rowcnt, rowbase, counts, height);
-  DD_LAUNCH_CHECK("component_obb row scan");
-  hipLaunchKernelGGL(obb_slot_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, stats, rowcnt, rowbase, recs, height, width, min_pixels,
-                     max_boxes);
-  DD_LAUNCH_CHECK("component_obb slots");
-  hipLaunchKernelGGL(obb_moment_kernel, runs, dim3(64, 4), 0, st, labels, stats, recs, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("component_obb moments");
-  hipLaunchKernelGGL(obb_extent_kernel, runs, dim3(64, 4), 0, st, labels, stats, recs, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("component_obb extents");
-  hipLaunchKernelGGL(obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, recs, counts, pad_px, boxes,
-                     (long long*)moments, height, width, max_boxes);
-  DD_LAUNCH_CHECK("component_obb emit");
-  return 0;
+  const int rc = fit_check("component_obb", true, maps, boxes, counts, min_pixels, max_boxes, pad_px, batch, height, width, workspace, workspace_bytes);
+  return rc ? rc : fit_launch<false>("component_obb", true, maps, threshold, min_pixels, max_boxes, pad_px, boxes, counts, moments, batch, height, width,
+                                     workspace, (hipStream_t)stream);
 }
 
 int64_t dd_split_components_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t split_px, int32_t grow_iters) {
@@ -969,68 +908,25 @@ int dd_split_components(const float* maps, float threshold, int32_t split_px, in
 }
 
 int64_t dd_labelled_boxes_workspace_bytes(int32_t batch, int32_t height, int32_t width) {
-  if (!shape_ok(batch, height, width)) {
-    dd_fail(DD_ERR_UNSUPPORTED, "labelled_boxes: batch in [1,%d], height and width in [1,%d] (got %d x %d x %d)", kMaxBatch, kMaxSide, batch,
-            height, width);
-    return -1;
-  }
-  return region_ws_bytes(batch, height, width);
+  return fit_ws_bytes("labelled_boxes", false, batch, height, width, 0);
 }
 
 int dd_labelled_boxes(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float* boxes, int32_t* counts, int32_t batch, int32_t height,
                       int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
-  DD_REQUIRE(labels && boxes && counts && workspace, DD_ERR_BAD_ARG, "labelled_boxes: null pointer");
-  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "labelled_boxes: min_pixels and max_boxes must be positive");
-  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "labelled_boxes: workspace must be 16-byte aligned");
-  const int64_t need = dd_labelled_boxes_workspace_bytes(batch, height, width);
-  if (need < 0) return DD_ERR_UNSUPPORTED;
-  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "labelled_boxes: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-             (long long)need);
-  const RegionWs ws = region_ws(workspace, batch, height, width);
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = region_count_launch(labels, ws, counts, min_pixels, batch, height, width, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(emit_region_boxes_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, (const Stats*)ws.stats, (const int*)ws.top,
-                     (const int*)ws.rowcnt, (const int*)ws.rowbase, boxes, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("labelled_boxes emit");
-  return 0;
+  const int rc = fit_check("labelled_boxes", false, labels, boxes, counts, min_pixels, max_boxes, 0.f, batch, height, width, workspace, workspace_bytes);
+  return rc ? rc : fit_launch<true>("labelled_boxes", false, labels, 0.f, min_pixels, max_boxes, 0.f, boxes, counts, nullptr, batch, height, width,
+                                    workspace, (hipStream_t)stream);
 }
 
 int64_t dd_labelled_obb_workspace_bytes(int32_t batch, int32_t height, int32_t width, int32_t max_boxes) {
-  if (!obb_shape_ok(batch, height, width, max_boxes)) {
-    dd_fail(DD_ERR_UNSUPPORTED, "labelled_obb: batch in [1,%d], height and width in [1,%d] (the second moments are exact in 64-bit integers up to "
-            "there), max_boxes in [1,%d] (got %d x %d x %d, max_boxes %d)", kMaxBatch, kObbMaxSide, kObbMaxBoxes, batch, height, width, max_boxes);
-    return -1;
-  }
-  return region_ws_bytes(batch, height, width) + (long)batch * max_boxes * (long)sizeof(Obb);
+  return fit_ws_bytes("labelled_obb", true, batch, height, width, max_boxes);
 }
 
 int dd_labelled_obb(const int32_t* labels, int32_t min_pixels, int32_t max_boxes, float pad_px, float* boxes, int32_t* counts, int64_t* moments,
                     int32_t batch, int32_t height, int32_t width, void* workspace, int64_t workspace_bytes, void* stream) {
-  DD_REQUIRE(labels && boxes && counts && workspace, DD_ERR_BAD_ARG, "labelled_obb: null pointer");
-  DD_REQUIRE(min_pixels >= 1 && max_boxes >= 1, DD_ERR_BAD_ARG, "labelled_obb: min_pixels and max_boxes must be positive");
-  DD_REQUIRE(pad_px >= 0.f && pad_px <= (float)kObbMaxSide, DD_ERR_BAD_ARG, "labelled_obb: pad_px must lie in [0,%d]", kObbMaxSide);
-  DD_REQUIRE((uintptr_t)workspace % 16 == 0, DD_ERR_BAD_ARG, "labelled_obb: workspace must be 16-byte aligned");
-  const int64_t need = dd_labelled_obb_workspace_bytes(batch, height, width, max_boxes);
-  if (need < 0) return DD_ERR_UNSUPPORTED;
-  DD_REQUIRE(workspace_bytes >= need, DD_ERR_WORKSPACE, "labelled_obb: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-             (long long)need);
-  const RegionWs ws = region_ws(workspace, batch, height, width);
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = region_count_launch(labels, ws, counts, min_pixels, batch, height, width, st);
-  if (rc) return rc;
-  const dim3 runs((width + 63) / 64, (height + 3) / 4, batch);
-  hipLaunchKernelGGL(obb_slot_kernel, dim3(height, batch), dim3(kThreads), 0, st, labels, ws.stats, (const int*)ws.rowcnt, (const int*)ws.rowbase,
-                     ws.recs, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("labelled_obb slots");
-  hipLaunchKernelGGL(obb_region_moment_kernel, runs, dim3(64, 4), 0, st, labels, (const Stats*)ws.stats, ws.recs, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("labelled_obb moments");
-  hipLaunchKernelGGL(obb_region_extent_kernel, runs, dim3(64, 4), 0, st, labels, (const Stats*)ws.stats, ws.recs, height, width, min_pixels, max_boxes);
-  DD_LAUNCH_CHECK("labelled_obb extents");
-  hipLaunchKernelGGL(obb_emit_kernel, dim3((max_boxes + kThreads - 1) / kThreads, batch), dim3(kThreads), 0, st, (const Obb*)ws.recs, (const int*)counts,
-                     pad_px, boxes, (long long*)moments, height, width, max_boxes);
-  DD_LAUNCH_CHECK("labelled_obb emit");
-  return 0;
+  const int rc = fit_check("labelled_obb", true, labels, boxes, counts, min_pixels, max_boxes, pad_px, batch, height, width, workspace, workspace_bytes);
+  return rc ? rc : fit_launch<true>("labelled_obb", true, labels, 0.f, min_pixels, max_boxes, pad_px, boxes, counts, moments, batch, height, width,
+                                    workspace, (hipStream_t)stream);
 }
 
 int64_t dd_box_iou_ats_workspace_bytes(const int32_t* offsets1, const int32_t* offsets2, int32_t batch) {

@@ -276,36 +276,44 @@ def split_components(maps, threshold=0.5, split_px=4, grow_iters=None):
     return labels
 
 
+def _fit_args(who, fit, want_moments):
+    if fit not in ("extent", "oriented"):
+        raise ValueError(f"{who}: fit must be 'extent' or 'oriented', got {fit!r}")
+    if want_moments and fit != "oriented":
+        raise ValueError(f"{who}: want_moments needs fit='oriented' (the extent fit forms no moments)")
+
+
+def _fit(who, entries, src, lead, min_pixels, max_boxes, fit, pad_px, want_moments):
+    """What ``component_boxes`` and ``labelled_boxes`` share: ``src`` [B,H,W] (maps or labels, already checked) through
+    ``entries`` = the (extent, oriented) pair of C entry points, whose arguments begin with ``lead`` (the source pointer, and the threshold)."""
+    min_pixels, max_boxes = int(min_pixels), int(max_boxes)
+    if min_pixels < 1 or max_boxes < 1:
+        raise _lib.HotpathError(f"{who}: min_pixels and max_boxes must be positive")
+    b, h, w = src.shape
+    lib, oriented = _lib.lib(), fit == "oriented"
+    entry = entries[oriented]
+    nbytes = getattr(lib, entry + "_workspace_bytes")(b, h, w, *((max_boxes,) if oriented else ()))
+    if b == 0 or nbytes < 0:
+        raise _lib.HotpathError(f"{who}: unsupported shape {tuple(src.shape)}: {lib.dd_last_error().decode()}")
+    boxes = torch.zeros((b, max_boxes, 2, 4), device=src.device, dtype=torch.float32)
+    counts = torch.empty((b,), device=src.device, dtype=torch.int32)
+    moments = torch.zeros((b, max_boxes, 6), device=src.device, dtype=torch.int64) if want_moments else None
+    ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
+    out = (float(pad_px), _p(boxes), _p(counts), _p(moments)) if oriented else (_p(boxes), _p(counts))
+    check(getattr(lib, entry)(*lead, min_pixels, max_boxes, *out, b, h, w, _p(ws), nbytes, _stream()), entry)
+    return (boxes, counts, moments) if want_moments else (boxes, counts)
+
+
 def labelled_boxes(labels, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False):
     """``component_boxes`` for regions given as an int32 label image [B,H,W] (``split_components``' or ``label_components``' output: the
     pixels of one label L form a region, and pixel L - 1 carries L).  Same survivors, order, counts, formats and roundings."""
-    if fit not in ("extent", "oriented"):
-        raise ValueError(f"labelled_boxes: fit must be 'extent' or 'oriented', got {fit!r}")
-    if want_moments and fit != "oriented":
-        raise ValueError("labelled_boxes: want_moments needs fit='oriented' (the extent fit forms no moments)")
+    _fit_args("labelled_boxes", fit, want_moments)
     if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
         raise _lib.HotpathError(f"labelled_boxes: expected int32 labels [B,H,W], got {getattr(labels, 'dtype', None)} "
                                 f"{tuple(getattr(labels, 'shape', ()))}")
     if not labels.is_cuda or not labels.is_contiguous():
         raise _lib.HotpathError("labelled_boxes: labels must be a contiguous GPU tensor (there is no CPU fallback)")
-    if int(min_pixels) < 1 or int(max_boxes) < 1:
-        raise _lib.HotpathError("labelled_boxes: min_pixels and max_boxes must be positive")
-    b, h, w = labels.shape
-    lib = _lib.lib()
-    nbytes = lib.dd_labelled_obb_workspace_bytes(b, h, w, int(max_boxes)) if fit == "oriented" else lib.dd_labelled_boxes_workspace_bytes(b, h, w)
-    if b == 0 or nbytes < 0:
-        raise _lib.HotpathError(f"labelled_boxes: unsupported shape {tuple(labels.shape)}: {lib.dd_last_error().decode()}")
-    boxes = torch.zeros((b, int(max_boxes), 2, 4), device=labels.device, dtype=torch.float32)
-    counts = torch.empty((b,), device=labels.device, dtype=torch.int32)
-    ws = torch.empty(nbytes, device=labels.device, dtype=torch.uint8)
-    if fit == "oriented":
-        moments = torch.zeros((b, int(max_boxes), 6), device=labels.device, dtype=torch.int64) if want_moments else None
-        check(lib.dd_labelled_obb(_p(labels), int(min_pixels), int(max_boxes), float(pad_px), _p(boxes), _p(counts), _p(moments), b, h, w,
-                                  _p(ws), nbytes, _stream()), "dd_labelled_obb")
-        return (boxes, counts, moments) if want_moments else (boxes, counts)
-    check(lib.dd_labelled_boxes(_p(labels), int(min_pixels), int(max_boxes), _p(boxes), _p(counts), b, h, w, _p(ws), nbytes, _stream()),
-          "dd_labelled_boxes")
-    return boxes, counts
+    return _fit("labelled_boxes", ("dd_labelled_boxes", "dd_labelled_obb"), labels, (_p(labels),), min_pixels, max_boxes, fit, pad_px, want_moments)
 
 
 def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False, split_px=0, grow_iters=None):
@@ -324,37 +332,17 @@ def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="exten
     ``split_px > 0``: the boxes are fitted to the regions of ``split_components(maps, threshold, split_px, grow_iters)`` instead of to the
     components (touching cars joined through a neck come apart; ``grow_iters=None`` = ``2 * split_px``).  ``split_px = 0``, the default,
     launches nothing new and changes no output."""
-    if fit not in ("extent", "oriented"):
-        raise ValueError(f"component_boxes: fit must be 'extent' or 'oriented', got {fit!r}")
-    if want_moments and fit != "oriented":
-        raise ValueError("component_boxes: want_moments needs fit='oriented' (the extent fit forms no moments)")
+    _fit_args("component_boxes", fit, want_moments)
     split_px, grow_iters = _split_args(split_px, grow_iters, "component_boxes")
     if split_px != 0:
         return labelled_boxes(split_components(maps, threshold, split_px, grow_iters), min_pixels, max_boxes, fit, pad_px, want_moments)
-    b, h, w = _maps(maps, "component_boxes")
-    if int(min_pixels) < 1 or int(max_boxes) < 1:
-        raise _lib.HotpathError("component_boxes: min_pixels and max_boxes must be positive")
-    boxes = torch.zeros((b, int(max_boxes), 2, 4), device=maps.device, dtype=torch.float32)
-    counts = torch.empty((b,), device=maps.device, dtype=torch.int32)
-    if fit == "oriented":
-        nbytes = _lib.lib().dd_component_obb_workspace_bytes(b, h, w, int(max_boxes))
-        if nbytes < 0:
-            raise _lib.HotpathError(f"component_boxes: unsupported shape {tuple(maps.shape)}: {_lib.lib().dd_last_error().decode()}")
-        moments = torch.zeros((b, int(max_boxes), 6), device=maps.device, dtype=torch.int64) if want_moments else None
-        ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
-        check(_lib.lib().dd_component_obb(_p(maps), float(threshold), int(min_pixels), int(max_boxes), float(pad_px), _p(boxes), _p(counts),
-                                          _p(moments), b, h, w, _p(ws), nbytes, _stream()), "dd_component_obb")
-        return (boxes, counts, moments) if want_moments else (boxes, counts)
-    nbytes = _lib.lib().dd_component_boxes_workspace_bytes(b, h, w)
-    ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
-    check(_lib.lib().dd_component_boxes(_p(maps), float(threshold), int(min_pixels), int(max_boxes), _p(boxes), _p(counts), b, h, w,
-                                        _p(ws), nbytes, _stream()), "dd_component_boxes")
-    return boxes, counts
+    _maps(maps, "component_boxes")
+    return _fit("component_boxes", ("dd_component_boxes", "dd_component_obb"), maps, (_p(maps), float(threshold)), min_pixels, max_boxes, fit, pad_px,
+                want_moments)
 
 
 def _box_list(box_sets, who, device):
     """Per-sample [n,2,4] tensors (all f64 or all f32) -> (flat device tensor [sum n, 8], dtype code, ctypes offsets)."""
-    import ctypes
     dtypes = {t.dtype for t in box_sets}
     if len(dtypes) != 1 or next(iter(dtypes)) not in (torch.float64, torch.float32):
         raise _lib.HotpathError(f"{who}: boxes must all be float64 or all float32")
@@ -362,7 +350,7 @@ def _box_list(box_sets, who, device):
         if t.dim() != 3 or tuple(t.shape[1:]) != (2, 4):
             raise _lib.HotpathError(f"{who}: expected [n,2,4] boxes, got {tuple(t.shape)}")
     counts = [int(t.shape[0]) for t in box_sets]
-    offsets = (ctypes.c_int32 * (len(box_sets) + 1))(0, *[sum(counts[:i + 1]) for i in range(len(box_sets))])
+    offsets = (C.c_int32 * (len(box_sets) + 1))(0, *[sum(counts[:i + 1]) for i in range(len(box_sets))])
     flat = torch.cat([t.reshape(-1, 8) for t in box_sets], dim=0).to(device).contiguous()
     return flat, 0 if flat.dtype == torch.float64 else 1, offsets
 
