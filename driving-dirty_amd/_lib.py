@@ -1,19 +1,42 @@
-"""ctypes binding of ``csrc/libdd_hotpath.so`` (C ABI: ``include/dd_hotpath.h``).
+"""ctypes binding of ``csrc/libdd_hotpath.so``, derived from its C ABI ``include/dd_hotpath.h``.
 
 There is no fallback: if the library is missing or a call fails, an exception is raised.
+
+``SIGNATURES`` {name: (restype, argtypes)} is parsed from the header at import (``parse_header``); nothing is declared twice.
+``call(name, *operands)`` is the one way the package enters a status-returning entry point, ``size(name, *args)`` the one way it
+asks a ``*_bytes`` / ``*_floats`` / ``*_elems`` query that answers a negative number for "refused".
+
+The boundary is also patched from OUTSIDE: bench.py's ``AbiTimer`` replaces entry points on the ``CDLL`` object by Python wrappers
+(``setattr(lib(), symbol, timed)``) whose predicates read the arguments, and its ``KernelTimer`` rebinds functions of ``ops``.
+What they rely on, and what ``call`` therefore keeps by construction:
+
+  * an entry point is looked up on the ``CDLL`` object at EVERY call, ``getattr(lib(), name)``; a function object is never cached
+    (a cached one would bypass the timers without a sound, and bench.py's roofline line would be computed from nothing);
+  * arguments reach the function positionally, in header order;
+  * descriptors go as ``ctypes.byref(struct)`` (the predicates read ``x[5]._obj.cin``);
+  * scalars go as plain Python numbers (the predicates compute ``x[4] >= 100_000_000`` and ``x[6] * x[7]``);
+  * ``ops.conv_fwd_bits``, ``ops.conv_wino_fwd_bits``, ``ops.conv_wino2_fwd_bits`` (``(x, packed, bias, desc)``) and
+    ``ops.conv_wino2_dgrad_w1`` stay module-level functions of ``ops`` that ``EncoderConvStack`` reaches through the module's
+    globals at call time; ``ops.WINOGRAD`` and ``ops.WINOGRAD_2D`` stay module attributes read at call time.
 """
 import ctypes as C
 import os
+import re
 
 import torch  # noqa: F401  -- FIRST: the library must bind to the HIP runtime torch has loaded (same soname
 #                              libamdhip64.so.7); loading ours first would put a second runtime in the process
 
-from .build import LIB
+from . import ddp as _ddp
+from .build import HEADER, LIB
 
 if os.environ.get("DD_HOTPATH_LIB"):      # another BUILD of the same library (tools/: A/B of two builds on one box); must exist, same ABI
     LIB = os.environ["DD_HOTPATH_LIB"]
 
 _i32, _i64, _f32, _p = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+
+
+class HotpathError(RuntimeError):
+    pass
 
 
 class ConvDesc(C.Structure):
@@ -35,211 +58,72 @@ class AdamTensor(C.Structure):
     _fields_ = [("p", _p), ("g", _p), ("m", _p), ("v", _p), ("n", _i64)]
 
 
-_DP = C.POINTER(ConvDesc)
-_GP = C.POINTER(GConvDesc)
+# ---- the header is the single source of the signatures ------------------------------------------------------------------------
+_SCALARS = {"int": _i32, "int32_t": _i32, "int64_t": _i64, "float": _f32}
+_STRUCTS = {"dd_conv_desc": ConvDesc, "dd_gconv_desc": GConvDesc, "dd_adam_tensor": AdamTensor}
+_POINTEES = {"void", "char", "unsigned char", "float", "double", "uint8_t", "uint16_t", "uint32_t", "uint64_t", "int32_t", "int64_t"}
+_RETURNS = {"int": _i32, "int32_t": _i32, "int64_t": _i64, "const char *": C.c_char_p}
+# what the header holds besides declarations: the extern "C" brackets, struct and enum definitions, preprocessor lines
+_NOT_DECLARATIONS = (r"#ifdef __cplusplus.*?#endif", r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", r"enum\s*\{.*?\}\s*;", r"#[^\n]*")
 
-# name -> (restype, argtypes); mirrors include/dd_hotpath.h one to one
-SIGNATURES = {
-    "dd_abi_version": (_i32, []),
-    "dd_last_error": (C.c_char_p, []),
-    "dd_clock_probe": (_i32, [_p, _i32, _i32, _p]),
-    "dd_set_cu_budget": (_i32, [_i32]),
-    "dd_set_adam_blocks_per_cu": (_i32, [_i32]),
-    "dd_set_adam_spare_cus": (_i32, [_i32]),
-    "dd_get_cu_budget": (_i32, []),
-    "dd_stitch6": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_stitch6_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
-    "dd_boxes_to_binary_map": (_i32, [_p, _i32, _p, _p, _i32, _p]),
-    "dd_stitch6_u8": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
-    "dd_stitch6_u8_ptrs": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_nchw_to_nhwc": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_subsample_nhwc4": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_subsample_nhwc4_u8_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_copy_channels": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_copy_channels_window": (_i32, [_p, _p] + [_i32] * 16 + [_p]),
-    "dd_deconv2x2_c32_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_deconv2x2_c32_fwd_slice": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_deconv2x2_c32_wgrad_workspace_bytes": (_i64, []),
-    "dd_deconv2x2_c32_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_ssconv_dgrad_supported": (_i32, [_i32, _i32, _i32]),
-    "dd_ssconv_dgrad": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_ssconv_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_conv1x1_c32_c3_nchw": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_conv1ch_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_conv1ch_wgrad_workspace_bytes": (_i64, []),
-    "dd_conv1ch_fwd_phase3": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_conv1ch_wgrad_phase3": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
-    "dd_phase3_scatter": (_i32, [_p, _p] + [_i32] * 8 + [_p]),
-    "dd_phase3_gather": (_i32, [_p, _p] + [_i32] * 8 + [_p]),
-    "dd_conv1ch_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
-    "dd_nhwc_to_nchw": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_conv_packed_floats": (_i64, [_DP, _i32]),
-    "dd_conv_pack": (_i32, [_p, _p, _DP, _i32, _p]),
-    "dd_conv_fwd": (_i32, [_p, _p, _p, _p, _p, _DP, _i32, _p]),
-    "dd_conv_fwd_relu_bits": (_i32, [_p, _p, _p, _p, _p, _DP, _p]),
-    "dd_conv_dgrad_relu_bits": (_i32, [_p, _p, _p, _p, _DP, _p]),
-    "dd_conv_stats_floats": (_i64, []),
-    "dd_conv_fwd_stats": (_i32, [_p, _p, _p, _p, _p, _p, _DP, _p]),
-    "dd_bn2d_finalize": (_i32, [_p, _i64, _p, _p, _p, _p, _f32, _f32, _i32, _p, _p, _p, _p]),
-    "dd_bn2d_stats": (_i32, [_p, _p, _i64, _p]),
-    "dd_bn2d_apply_relu": (_i32, [_p, _p, _p, _i64, _p]),
-    "dd_bn2d_workspace_bytes": (_i64, []),
-    "dd_bn2d_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p]),
-    "dd_conv_dgrad_bn": (_i32, [_p, _p, _p, _p, _p, _DP, _p]),
-    "dd_conv_wgrad_bn": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _DP, _p]),
-    "dd_pool4_bn_fwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_pool4_bn_bwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_conv_dgrad": (_i32, [_p, _p, _p, _p, _DP, _p]),
-    "dd_conv_wgrad_workspace_bytes": (_i64, [_DP]),
-    "dd_conv_wgrad": (_i32, [_p, _p, _p, _p, _p, _i64, _DP, _p]),
-    "dd_relu_bwd": (_i32, [_p, _p, _p, _i64, _p]),
-    "dd_relu_sign_bits": (_i32, [_p, _p, _i64, _p]),
-    "dd_relu_bwd_pad_bits": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_fwd": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_relu_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_relu_bwd_add": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_idx_elems": (_i64, [_i32, _i32, _i32, _i32]),
-    "dd_pool4_fwd_idx": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_idx_relu_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_mlp_tail_supported": (_i32, [_i32] * 4),
-    "dd_mlp_tail_fwd": (_i32, [_p] * 25 + [_i32] * 4 + [_f32] * 6 + [_i32, _p]),
-    "dd_mlp_tail_bwd": (_i32, [_p] * 28 + [_i32] * 4 + [_f32] * 4 + [_i32, _p]),
-    "dd_bn_relu_drop_fwd": (_i32, [_p] * 9 + [_i32, _i32, _f32, _f32, _f32, _i32, _p, _p]),
-    "dd_bn_relu_drop_bwd": (_i32, [_p] * 12 + [_i32, _i32, _f32, _f32, _i32, _p]),
-    "dd_loss_workspace_bytes": (_i64, [_i64]),
-    "dd_bce_logits": (_i32, [_p, _p, _p, _p, _p, _i64, _f32, _p, _p]),
-    "dd_bce_logits_u8": (_i32, [_p, _p, _p, _p, _p, _i64, _f32, _p, _p]),
-    "dd_bce_logits_u8_ptrs": (_i32, [_p, _p, _i32, _i64, _p, _p, _p, _f32, _p, _p]),
-    "dd_scale_by_device_scalar": (_i32, [_p, _p, _i64, _p]),
-    "dd_sigmoid": (_i32, [_p, _p, _i64, _p]),
-    "dd_sigmoid_bwd": (_i32, [_p, _p, _p, _i64, _p]),
-    "dd_mse": (_i32, [_p, _p, _p, _p, _i64, _f32, _p, _p]),
-    "dd_gconv_packed_floats": (_i64, [_GP]),
-    "dd_gconv_pack": (_i32, [_p, _p, _GP, _i64, _i64, _i64, _i32, _i32, _i32, _p]),
-    "dd_gconv_fwd": (_i32, [_p, _p, _p, _p, _p, _GP, _i32, _p]),
-    "dd_gconv_wgrad_workspace_bytes": (_i64, [_GP]),
-    "dd_gconv_wgrad": (_i32, [_p, _p, _p, _p, _GP, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_dconv_supported": (_i32, [_GP]),
-    "dd_dconv_packed_floats": (_i64, [_GP]),
-    "dd_dconv_pack": (_i32, [_p, _p, _GP, _i64, _i64, _i64, _i32, _i32, _i32, _p]),
-    "dd_dconv_fwd": (_i32, [_p, _p, _p, _p, _p, _GP, _i32, _p]),
-    "dd_dconv_colsum_supported": (_i32, [_p, _i32, _i32]),
-    "dd_dconv_colsum_workspace_bytes": (_i64, []),
-    "dd_dconv_fwd_colsum": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _p, _i64, _p]),
-    "dd_dconv_split_supported": (_i32, [_GP]),
-    "dd_dconv_split_input_bytes": (_i64, [_GP]),
-    "dd_dconv_split_packed_bytes": (_i64, [_GP]),
-    "dd_dconv_split_input": (_i32, [_p, _p, _GP, _p]),
-    "dd_dconv_split_pack": (_i32, [_p, _p, _GP, _i64, _i64, _i64, _i32, _i32, _i32, _p]),
-    "dd_dconv_fwd_split": (_i32, [_p, _p, _p, _p, _p, _p, _GP, _i32, _p]),
-    "dd_dconv_split_rows": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p]),
-    "dd_dconv_wgrad_split_supported": (_i32, [_i32, _i32, _i32, _i32]),
-    "dd_dconv_wgrad_split_workspace_bytes": (_i64, [_i32, _i32]),
-    "dd_dconv_wgrad_split": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_dconv_wgrad_supported": (_i32, [_i32] * 4),
-    "dd_dconv_wgrad_workspace_bytes": (_i64, [_i32] * 4),
-    "dd_dconv_wgrad": (_i32, [_p, _p, _p] + [_i32] * 14 + [_p, _i64, _p]),
-    "dd_channel_sum_workspace_bytes": (_i64, []),
-    "dd_channel_sum": (_i32, [_p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p]),
-    "dd_deconv2x2_c1_workspace_bytes": (_i64, [_i32]),
-    "dd_deconv2x2_c1_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_deconv2x2_c1_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
-    "dd_strip6_supported": (_i32, [_i32, _i32]),
-    "dd_strip6_fwd": (_i32, [_p, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_strip6_wgrad_workspace_bytes": (_i64, []),
-    "dd_strip6_wgrad": (_i32, [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_view_to_nhwc4": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_view_to_nhwc4_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_view_to_nhwc4_u8_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _i32, _p]),
-    "dd_add": (_i32, [_p, _p, _p, _i64, _p]),
-    "dd_bce_probs": (_i32, [_p, _p, _p, _p, _i64, _f32, _p, _p]),
-    "dd_linear_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "dd_linear_fwd": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_linear_dgrad": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_linear_sigmoid_gt": (_i32, [_p, _p, _p, _f32, _p, _i32, _i32, _i32, _p]),
-    "dd_linear_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_threat_score_workspace_bytes": (_i64, []),
-    "dd_threat_score": (_i32, [_p, _p, _p, _i64, _i32, _p, _p]),
-    "dd_ts_hist": (_i32, [_p, _p, _i32, _i64, _i32, _p, _p]),
-    "dd_label_components_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "dd_label_components": (_i32, [_p, _f32, _p, _i32, _i32, _i32, _p]),
-    "dd_component_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "dd_component_boxes": (_i32, [_p, _f32, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_component_obb_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
-    "dd_component_obb": (_i32, [_p, _f32, _i32, _i32, _f32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_split_components_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
-    "dd_split_components": (_i32, [_p, _f32, _i32, _i32, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_labelled_boxes_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "dd_labelled_boxes": (_i32, [_p, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_labelled_obb_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
-    "dd_labelled_obb": (_i32, [_p, _i32, _i32, _f32, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_box_iou_ats_workspace_bytes": (_i64, [_p, _p, _i32]),
-    "dd_box_iou_ats": (_i32, [_p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _p, _i64, _p]),
-    "dd_conv_wino_packed_floats": (_i64, [_p]),
-    "dd_conv_wino_pack": (_i32, [_p, _p, _p, _i32, _p]),
-    "dd_conv_wino_fwd_relu_bits": (_i32, [_p, _p, _p, _p, _p, _p, _p]),
-    "dd_conv_wino_dgrad_relu_bits": (_i32, [_p, _p, _p, _p, _p, _p]),
-    "dd_conv_wino2_packed_floats": (_i64, [_p]),
-    "dd_conv_wino2_pack": (_i32, [_p, _p, _p, _i32, _p]),
-    "dd_conv_wino2_fwd_relu_bits": (_i32, [_p, _p, _p, _p, _p, _p, _p]),
-    "dd_conv_wino2_dgrad_relu_bits": (_i32, [_p, _p, _p, _p, _p, _p]),
-    "dd_conv_wino2_dgrad_w1_workspace_bytes": (_i64, [_DP]),
-    "dd_conv_wino2_dgrad_w1": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _DP, _p]),
-    "dd_conv_wino2_wgrad_workspace_bytes": (_i64, [_p]),
-    "dd_conv_wino2_wgrad": (_i32, [_p, _p, _p, _p, _p, _i64, _p, _p]),
-    "dd_conv_wino2_wgrad_partials": (_i32, [_p, _p, _p, _i64, _DP, _p]),
-    "dd_conv_wino2_wgrad_finish": (_i32, [_p, _i64, _p, _p, _DP, _p]),
-    "dd_conv_wino_wgrad_workspace_bytes": (_i64, [_p]),
-    "dd_conv_wino_wgrad": (_i32, [_p, _p, _p, _p, _p, _i64, _p, _p]),
-    "dd_stitch6_bf16": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
-    "dd_stitch6_bf16_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
-    "dd_stitch6_bf16_u8_ptrs": (_i32, [_p, _p, _i32, _i32, _i32, _p]),
-    "dd_conv_bf16_packed_elems": (_i64, [_p]),
-    "dd_conv_bf16_pack": (_i32, [_p, _p, _i32, _p, _p]),
-    "dd_conv_bf16_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p]),
-    "dd_conv_bf16_dgrad": (_i32, [_p, _p, _p, _p, _p, _p]),
-    "dd_conv_bf16_wgrad_workspace_bytes": (_i64, [_p]),
-    "dd_conv_bf16_wgrad": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _p]),
-    "dd_pool4_bf16_fwd": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_relu_bf16_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_bf16_idx_elems": (_i64, [_i32, _i32, _i32, _i32]),
-    "dd_pool4_bf16_fwd_idx": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_pool4_idx_relu_bf16_bwd": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_f32_to_bf16": (_i32, [_p, _p, _i64, _p]),
-    "dd_bf16_to_f32": (_i32, [_p, _p, _i64, _p]),
-    "dd_stitch6_bf16_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_stitch6_bf16_ptrs_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_stitch6_bf16_u8_ptrs_masked": (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_split64": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_merge64": (_i32, [_p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_dc1_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_wgrad_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
-    "dd_dec_bf16_dc34_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_dc4_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_dec_bf16_dc3_dgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
-    "dd_dec_bf16_dc3_wgrad": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
-    "dd_adam_step": (_i32, [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
-    "dd_adam_step_rankb": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
-    "dd_column_sum": (_i32, [_p, _p, _i32, _i32, _p]),
-    "dd_adam_step_multi": (_i32, [C.POINTER(AdamTensor), _i32, _f32, _f32, _f32, _f32, _i32, _f32, _p]),
-    "dd_adam_step_dev": (_i32, [_p, _p, _p, _p, _i64, _f32, _f32, _f32, _f32, _i32, _p, _p]),
-    "dd_adam_step_rankb_dev": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _f32, _f32, _f32, _f32, _i32, _p, _p]),
-    "dd_adam_step_multi_dev": (_i32, [C.POINTER(AdamTensor), _i32, _f32, _f32, _f32, _f32, _i32, _p, _p]),
-    "dd_sqnorm_workspace_bytes": (_i64, [_i64]),
-    "dd_sqnorm": (_i32, [_p, _i64, _p, _p, _i64, _p]),
-    "dd_sqnorm_multi_workspace_bytes": (_i64, [C.POINTER(AdamTensor), _i32]),
-    "dd_sqnorm_multi": (_i32, [C.POINTER(AdamTensor), _i32, _p, _p, _i64, _p]),
-    "dd_rankb_sqnorm_workspace_bytes": (_i64, [_i32, _i32, _i32]),
-    "dd_rankb_sqnorm": (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _i64, _p]),
-    "dd_clip_scale": (_i32, [_p, _i32, _f32, _f32, _p, _p]),
-}
+
+def _ctype(spelling, decl):
+    """One parameter type of the header's vocabulary -> ctypes.  Scalars by name; ``const <struct>*`` -> POINTER of its Structure; a
+    pointer (or ``T* const*`` table) to a plain C type -> c_void_p.  Anything else is refused."""
+    t = " ".join(spelling.replace("*", " * ").split())
+    if t in _SCALARS:
+        return _SCALARS[t]
+    m = re.fullmatch(r"(const )?(\w+(?: \w+)?) \*( const \*)?", t)
+    if m and m.group(2) in _STRUCTS and m.group(1) and not m.group(3):
+        return C.POINTER(_STRUCTS[m.group(2)])
+    if m and m.group(2) in _POINTEES:
+        return _p
+    raise HotpathError(f"include/dd_hotpath.h: no ctypes mapping for the type '{spelling.strip()}' in: {decl}")
+
+
+def parse_header(text):
+    """Text of the header -> ({name: (restype, argtypes)}, frozenset of the names whose last parameter is called ``stream``).
+    Every statement that is left after comments, preprocessor lines, the struct and enum definitions are taken out must read
+    ``ret dd_name(params);`` in the types above: a declaration this cannot map raises HotpathError naming it."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    for pattern in _NOT_DECLARATIONS:
+        text = re.sub(pattern, " ", text, flags=re.S)
+    signatures, streamed = {}, set()
+    for decl in (" ".join(s.split()) for s in text.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(int|int32_t|int64_t|const char ?\*) ?(dd_\w+) ?\((.*)\)", decl)
+        if not m:
+            raise HotpathError(f"include/dd_hotpath.h: not a 'ret dd_name(params);' declaration: {decl}")
+        ret, name, params = " ".join(m.group(1).replace("*", " *").split()), m.group(2), m.group(3).strip()
+        if name in signatures:
+            raise HotpathError(f"include/dd_hotpath.h: {name} is declared twice")
+        argtypes, last = [], None
+        for param in ([] if params == "void" else params.split(",")):
+            pm = re.fullmatch(r"\s*(.*?[\s*])(\w+)\s*", param)
+            if not pm:
+                raise HotpathError(f"include/dd_hotpath.h: parameter '{param.strip()}' has no name in: {decl}")
+            argtypes.append(_ctype(pm.group(1), decl))
+            last = pm.group(2)
+        signatures[name] = (_RETURNS[ret], argtypes)
+        if last == "stream":
+            if argtypes[-1] is not _p or _RETURNS[ret] is not _i32:
+                raise HotpathError(f"include/dd_hotpath.h: a launch function returns int and ends in 'void* stream': {decl}")
+            streamed.add(name)
+    return signatures, frozenset(streamed)
+
+
+with open(HEADER) as _f:
+    SIGNATURES, STREAMED = parse_header(_f.read())
+# operands a caller supplies: to call() for the launch functions (the stream is appended) and the dd_set_* settings, to size() for the
+# int64 queries.  The yes/no queries and the getters are neither: their non-zero answer is no error code.
+CALL_OPERANDS = {name: len(args) - (name in STREAMED) for name, (res, args) in SIGNATURES.items()
+                 if name in STREAMED or (res is _i32 and name.startswith("dd_set_"))}
+SIZE_OPERANDS = {name: len(args) for name, (res, args) in SIGNATURES.items() if res is _i64}
 
 ABI_VERSION = 4      # include/dd_hotpath.h: DD_ABI_VERSION
 _lib = None
-
-
-class HotpathError(RuntimeError):
-    pass
 
 
 def lib():
@@ -263,3 +147,90 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise HotpathError(f"{what} failed (code {rc}): {lib().dd_last_error().decode()}")
+
+
+# ---- operands --------------------------------------------------------------------------------------------------------------
+def stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    """Device pointer of a kernel operand.  A parameter whose all-gather (sharded optimizer, ddp.GradSync) is still in flight
+    is waited for -- on the current stream -- the first time it is handed to a kernel.  For callers that build pointer tables or call
+    lib() themselves; call() does the same per tensor operand inside its own loop."""
+    if t is None:
+        return None
+    p = t.data_ptr()
+    if _ddp.PARAM_WAITS:
+        wait = _ddp.PARAM_WAITS.pop(p, None)
+        if wait is not None:
+            wait()
+    return C.c_void_p(p)
+
+
+_DTYPE_NAMES = {torch.float32: "fp32", torch.bfloat16: "bf16"}
+
+
+def dev(t, name, shape=None, dtype=torch.float32):
+    """Validate a kernel operand on the HOST before any launch (a faulting kernel can reset the GPU)."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise HotpathError(f"{name}: expected a contiguous {_DTYPE_NAMES.get(dtype, dtype)} device tensor, got "
+                           f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')} "
+                           f"contiguous={getattr(t, 'is_contiguous', lambda: '?')()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise HotpathError(f"{name}: shape {tuple(t.shape)} != expected {tuple(shape)}")
+    return t
+
+
+# The loop in call() is the host cost of every launch.  Measured against the idiom it replaces (check(lib().dd_x(_p(a), ...,
+# _stream()), "dd_x")): operands told by their class first, ``ptr`` inlined and the names below bound once keep it level with it;
+# through a helper and with attribute lookups per operand it cost 1.5 us more per call.
+_PLAIN = frozenset((int, float, bool, type(None)))      # operands that pass as they are
+_Tensor, _Structure, _byref, _void_p, _WAITS = torch.Tensor, C.Structure, C.byref, C.c_void_p, _ddp.PARAM_WAITS
+
+
+def _refuse(name, operands, declared):
+    if name not in declared:
+        raise HotpathError(f"{name}: not an entry point that " + ("call() serves (a launch function or a dd_set_* setting)"
+                                                                   if declared is CALL_OPERANDS else "size() serves (an int64_t query)"))
+    raise HotpathError(f"{name}: {len(operands)} operands given, the header declares {declared[name]}"
+                       + (" in front of the stream, which call() appends itself" if name in STREAMED else ""))
+
+
+def call(name, *operands):
+    """Enter a launch function (last parameter ``stream``: the current torch stream is appended) or a ``dd_set_*`` setting with
+    ``operands`` in header order: a tensor goes as its device pointer (as ``ptr`` gives it), a Structure as byref; None, numbers,
+    ctypes arrays and pointers as they are.  Another operand count than the header's, or any other function, is refused.  Raises
+    HotpathError with the name, the code and dd_last_error() on a non-zero return.  The function is looked up on the CDLL object NOW
+    (see the module docstring: never cache it)."""
+    if len(operands) != CALL_OPERANDS.get(name):
+        _refuse(name, operands, CALL_OPERANDS)
+    args = []
+    for a in operands:
+        if a.__class__ in _PLAIN:
+            args.append(a)
+        elif isinstance(a, _Tensor):
+            p = a.data_ptr()
+            if _WAITS:
+                wait = _WAITS.pop(p, None)
+                if wait is not None:
+                    wait()
+            args.append(_void_p(p))
+        else:
+            args.append(_byref(a) if isinstance(a, _Structure) else a)
+    if name in STREAMED:
+        args.append(stream())
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        check(rc, name)
+
+
+def size(name, *args):
+    """An ``int64_t`` query (``*_bytes`` / ``*_floats`` / ``*_elems``; descriptors go as they go to call()): its value, or HotpathError
+    with dd_last_error() when it answers a negative one."""
+    if len(args) != SIZE_OPERANDS.get(name):
+        _refuse(name, args, SIZE_OPERANDS)
+    n = getattr(lib(), name)(*[_byref(a) if isinstance(a, _Structure) else a for a in args])
+    if n < 0:
+        raise HotpathError(f"{name} refused (returned {n}): {lib().dd_last_error().decode()}")
+    return n

@@ -21,7 +21,8 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # per-file additions.  adam_rankb.hip: MFMA accumulators in ordinary vector registers (the kernel's whole budget is 72 registers, and the
 # default form keeps a second copy of the accumulators in the accumulation registers)
 EXTRA_FLAGS = {"adam_rankb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
-HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "adam_rankb_kernels.inc"), os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "dd_hotpath.h")]
+HEADER = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "dd_hotpath.h")      # the C ABI; _lib.py derives its ctypes table from it
+HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "adam_rankb_kernels.inc"), HEADER]
 
 
 def _obj(src):

@@ -15,23 +15,20 @@ channel: no cross-lane traffic); ``relu(u*scale + shift)`` is applied by the ker
 row loader, pool, ReLU mask of the data gradient, weight-gradient input), so the normalised activation is never
 written; the BN backward reductions use wavefront shuffles.
 """
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _lib, ops
-from ._lib import check
+from ._lib import call, size
 from .components import POOL, DenseBlock, _require_gpu
-from .ops import PACK_DGRAD_S1, PACK_DGRAD_S2, PACK_FWD, _p, _stream, conv_desc, conv_out, conv_pack
+from .ops import PACK_DGRAD_S1, PACK_DGRAD_S2, PACK_FWD, conv_desc, conv_out, conv_pack
 
 
 def _conv_stats(x, w, b, desc, in_aff):
     ho, wo = conv_out(desc.height, desc.stride), conv_out(desc.width, desc.stride)
     u = torch.empty((desc.batch, ho, wo, 32), device=x.device, dtype=torch.float32)
-    stats = torch.empty(_lib.lib().dd_conv_stats_floats(), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_fwd_stats(_p(x), _p(conv_pack(w, desc, PACK_FWD)), _p(b), _p(in_aff), _p(u), _p(stats),
-                                       C.byref(desc), _stream()), "dd_conv_fwd_stats")
+    stats = torch.empty(size("dd_conv_stats_floats"), device=x.device, dtype=torch.float32)
+    call("dd_conv_fwd_stats", x, conv_pack(w, desc, PACK_FWD), b, in_aff, u, stats, desc)
     return u, stats
 
 
@@ -41,8 +38,7 @@ def _finalize(stats, count, bn, training):
     mean = torch.empty(32, device=dev, dtype=torch.float32)
     inv = torch.empty(32, device=dev, dtype=torch.float32)
     momentum = 0.1 if bn.momentum is None else bn.momentum
-    check(_lib.lib().dd_bn2d_finalize(_p(stats), count, _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var),
-                                      momentum, bn.eps, int(training), _p(aff), _p(mean), _p(inv), _stream()), "dd_bn2d_finalize")
+    call("dd_bn2d_finalize", stats, count, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, int(training), aff, mean, inv)
     if training and bn.num_batches_tracked is not None:
         bn.num_batches_tracked += 1
     return aff, mean, inv
@@ -50,9 +46,8 @@ def _finalize(stats, count, bn, training):
 
 def _bn_bwd(g, u, gamma, mean, inv, training):
     du, dgamma, dbeta = torch.empty_like(u), torch.empty_like(gamma), torch.empty_like(gamma)
-    ws = torch.empty(_lib.lib().dd_bn2d_workspace_bytes(), device=u.device, dtype=torch.uint8)
-    check(_lib.lib().dd_bn2d_bwd(_p(g), _p(u), _p(gamma), _p(mean), _p(inv), _p(du), _p(dgamma), _p(dbeta), u.numel() // 32,
-                                 int(training), _p(ws), _stream()), "dd_bn2d_bwd")
+    ws = torch.empty(size("dd_bn2d_workspace_bytes"), device=u.device, dtype=torch.uint8)
+    call("dd_bn2d_bwd", g, u, gamma, mean, inv, du, dgamma, dbeta, u.numel() // 32, int(training), ws)
     return du, dgamma, dbeta
 
 
@@ -76,10 +71,10 @@ class EncoderV2ConvStack(torch.autograd.Function):
             ops.TRACE.update(v2=((u1, a1), (u2, a2), (u3, a3)))      # never written, the checker recomputes it with dd_bn2d_apply_relu
         if pool:
             pooled = torch.empty((b, (32 * ho * wo) // 4), device=x4.device, dtype=torch.float32)
-            check(_lib.lib().dd_pool4_bn_fwd(_p(u3), _p(a3), _p(pooled), b, ho, wo, _stream()), "dd_pool4_bn_fwd")
+            call("dd_pool4_bn_fwd", u3, a3, pooled, b, ho, wo)
             return pooled
         y3 = torch.empty_like(u3)
-        check(_lib.lib().dd_bn2d_apply_relu(_p(u3), _p(a3), _p(y3), u3.numel() // 32, _stream()), "dd_bn2d_apply_relu")
+        call("dd_bn2d_apply_relu", u3, a3, y3, u3.numel() // 32)
         return y3
 
     @staticmethod
@@ -89,28 +84,27 @@ class EncoderV2ConvStack(torch.autograd.Function):
         b, h, w, _ = x4.shape
         ho, wo = conv_out(h, 2), conv_out(w, 2)
         d1, d2, d3 = conv_desc(b, h, w, 3, 1), conv_desc(b, h, w, 32, 1), conv_desc(b, h, w, 32, 2)
-        lib = _lib.lib()
         grad = grad.contiguous()
         gh3 = torch.empty_like(u3)                       # dL/d(BN3 output), ReLU already applied
         if pool:
-            check(lib.dd_pool4_bn_bwd(_p(grad), _p(u3), _p(a3), _p(gh3), b, ho, wo, _stream()), "dd_pool4_bn_bwd")
+            call("dd_pool4_bn_bwd", grad, u3, a3, gh3, b, ho, wo)
         else:
             y3 = torch.empty_like(u3)
-            check(lib.dd_bn2d_apply_relu(_p(u3), _p(a3), _p(y3), u3.numel() // 32, _stream()), "dd_bn2d_apply_relu")
+            call("dd_bn2d_apply_relu", u3, a3, y3, u3.numel() // 32)
             gh3 = ops.relu_bwd(grad, y3)
         du3, dg3, dbe3 = _bn_bwd(gh3, u3, g3, m3, i3, training)
 
         def wgrad_bn(u_in, aff, dy, desc):
-            nbytes = lib.dd_conv_wgrad_workspace_bytes(C.byref(desc))
+            nbytes = size("dd_conv_wgrad_workspace_bytes", desc)
             ws = torch.empty(nbytes, device=dy.device, dtype=torch.uint8)
             dw = torch.empty((32, 32, 3, 3), device=dy.device, dtype=torch.float32)
             db = torch.empty(32, device=dy.device, dtype=torch.float32)
-            check(lib.dd_conv_wgrad_bn(_p(u_in), _p(aff), _p(dy), _p(dw), _p(db), _p(ws), nbytes, C.byref(desc), _stream()), "dd_conv_wgrad_bn")
+            call("dd_conv_wgrad_bn", u_in, aff, dy, dw, db, ws, nbytes, desc)
             return dw, db
 
         def dgrad_bn(dy, w, kind, u_in, aff, desc):
             dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
-            check(lib.dd_conv_dgrad_bn(_p(dy), _p(conv_pack(w, desc, kind)), _p(u_in), _p(aff), _p(dx), C.byref(desc), _stream()), "dd_conv_dgrad_bn")
+            call("dd_conv_dgrad_bn", dy, conv_pack(w, desc, kind), u_in, aff, dx, desc)
             return dx
 
         dw3, db3 = wgrad_bn(u2, a2, du3, d3)
@@ -173,14 +167,14 @@ class Encoder(nn.Module):
 
 # ------------------------------------------------------------------------------------------------ v2 decoder
 def _stats(u):
-    stats = torch.empty(_lib.lib().dd_conv_stats_floats(), device=u.device, dtype=torch.float32)
-    check(_lib.lib().dd_bn2d_stats(_p(u), _p(stats), u.numel() // 32, _stream()), "dd_bn2d_stats")
+    stats = torch.empty(size("dd_conv_stats_floats"), device=u.device, dtype=torch.float32)
+    call("dd_bn2d_stats", u, stats, u.numel() // 32)
     return stats
 
 
 def _apply_relu(u, aff):
     y = torch.empty_like(u)
-    check(_lib.lib().dd_bn2d_apply_relu(_p(u), _p(aff), _p(y), u.numel() // 32, _stream()), "dd_bn2d_apply_relu")
+    call("dd_bn2d_apply_relu", u, aff, y, u.numel() // 32)
     return y
 
 

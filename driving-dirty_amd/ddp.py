@@ -68,7 +68,8 @@ import torch.distributed as dist
 from . import lightning
 
 # data_ptr of a parameter -> callable that makes the CURRENT stream wait for the all-gather still writing into it (shard mode).
-# ops._p / gconv._p pop and call the entry the first time a kernel operand with that address is handed to the C ABI.
+# _lib.call (for every tensor operand, in its conversion loop) and _lib.ptr pop and call the entry the first time a kernel operand with
+# that address is handed to the C ABI.  _lib binds this dict once at import: mutate it, NEVER rebind it.
 PARAM_WAITS = {}
 
 
@@ -404,7 +405,7 @@ class GradSync:
     @staticmethod
     def _set_budget(cus):
         from . import _lib
-        _lib.check(_lib.lib().dd_set_cu_budget(cus), "dd_set_cu_budget")
+        _lib.call("dd_set_cu_budget", cus)
 
     def remove(self):
         self.wait_gathers()

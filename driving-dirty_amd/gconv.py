@@ -17,33 +17,11 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from . import ddp as _ddp
-from ._lib import GConvDesc, check
+from ._lib import GConvDesc, call, size
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_RELU_MASK, EPI_BIAS_SIGMOID = 0, 1, 2, 3, 4
 
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    """Device pointer of a kernel operand.  A parameter whose all-gather (sharded optimizer, ddp.GradSync) is still in flight
-    is waited for -- on the current stream -- the first time it is handed to a kernel."""
-    if t is None:
-        return None
-    ptr = t.data_ptr()
-    if _ddp.PARAM_WAITS:
-        wait = _ddp.PARAM_WAITS.pop(ptr, None)
-        if wait is not None:
-            wait()
-    return C.c_void_p(ptr)
-
-
-def _chk(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise _lib.HotpathError(f"{name}: expected a contiguous fp32 device tensor")
-    return t
+_stream, _p, _chk = _lib.stream, _lib.ptr, _lib.dev      # the operand helpers live in _lib; _p / _stream stay for heads.py and tools/
 
 
 def _pair(v):
@@ -83,16 +61,13 @@ def _desc(batch, src, dst, cin, cout, k, stride=(1, 1), dil=(1, 1), pad=(0, 0), 
 
 
 def _pack(w, d, w_off, sn, sc, flip, n_real, c_real):
-    n = _lib.lib().dd_gconv_packed_floats(C.byref(d))
-    if n <= 0:
-        raise _lib.HotpathError(f"gconv: {_lib.lib().dd_last_error().decode()}")
-    packed = torch.empty(n, device=w.device, dtype=torch.float32)
-    check(_lib.lib().dd_gconv_pack(_p(w), _p(packed), C.byref(d), w_off, sn, sc, int(flip), n_real, c_real, _stream()), "dd_gconv_pack")
+    packed = torch.empty(size("dd_gconv_packed_floats", d), device=w.device, dtype=torch.float32)
+    call("dd_gconv_pack", w, packed, d, w_off, sn, sc, int(flip), n_real, c_real)
     return packed
 
 
 def _fwd(x, packed, bias, mask, y, d, epi):
-    check(_lib.lib().dd_gconv_fwd(_p(x), _p(packed), _p(bias), _p(mask), _p(y), C.byref(d), epi, _stream()), "dd_gconv_fwd")
+    call("dd_gconv_fwd", x, packed, bias, mask, y, d, epi)
 
 
 # The dilated stride-1 layers (the box heads' up-convs) have their own phase-decomposed, LDS-staged kernel (csrc/dconv.hip);
@@ -139,7 +114,7 @@ def split_rows(view):
         raise _lib.HotpathError("split_rows: a whole-buffer View with a multiple of 16 channels")
     b, h, w, cs = view.buf.shape
     xs = torch.empty(b * h * (view.chans // 16) * w * 112, device=view.buf.device, dtype=torch.uint8)
-    check(_lib.lib().dd_dconv_split_rows(_p(_chk(view.buf, "x")), _p(xs), b * h, w, cs, view.coff, view.chans, _stream()), "dd_dconv_split_rows")
+    call("dd_dconv_split_rows", _chk(view.buf, "x"), xs, b * h, w, cs, view.coff, view.chans)
     return xs
 
 
@@ -173,41 +148,37 @@ def _conv(x, weight, bias, mask, y, d, epi, w_off, sn, sc, flip, n_real, c_real,
     lib = _lib.lib()
     if SPLIT_BF16 and lib.dd_dconv_split_supported(C.byref(d)) and (
             (d.pad_h > 0 and mask is None and epi in (EPI_NONE, EPI_BIAS, EPI_BIAS_RELU)) or (d.pad_h == 0 and epi in (EPI_NONE, EPI_RELU_MASK))):
-        packed = torch.empty(lib.dd_dconv_split_packed_bytes(C.byref(d)), device=x.device, dtype=torch.uint8)
+        packed = torch.empty(size("dd_dconv_split_packed_bytes", d), device=x.device, dtype=torch.uint8)
         if xs is None:
-            xs = torch.empty(lib.dd_dconv_split_input_bytes(C.byref(d)), device=x.device, dtype=torch.uint8)
-            check(lib.dd_dconv_split_input(_p(x), _p(xs), C.byref(d), _stream()), "dd_dconv_split_input")
-        check(lib.dd_dconv_split_pack(_p(weight), _p(packed), C.byref(d), w_off, sn, sc, int(flip), n_real, c_real, _stream()), "dd_dconv_split_pack")
+            xs = torch.empty(size("dd_dconv_split_input_bytes", d), device=x.device, dtype=torch.uint8)
+            call("dd_dconv_split_input", x, xs, d)
+        call("dd_dconv_split_pack", weight, packed, d, w_off, sn, sc, int(flip), n_real, c_real)
         ys = None
         if emit is not None and d.cout % 16 == 0 and d.out_coff == 0 and d.ooff_h == 0 and d.ooff_w == 0 and d.omem_h == d.out_h and d.omem_w == d.out_w:
             ys = torch.empty(d.batch * d.out_h * (d.cout // 16) * d.out_w * 112, device=x.device, dtype=torch.uint8)
             emit["ys"] = ys
-        check(lib.dd_dconv_fwd_split(_p(xs), _p(packed), _p(bias), _p(mask), _p(y), _p(ys), C.byref(d), epi, _stream()), "dd_dconv_fwd_split")
+        call("dd_dconv_fwd_split", xs, packed, bias, mask, y, ys, d, epi)
         return xs
     if _dconv_ok(d):
-        n = lib.dd_dconv_packed_floats(C.byref(d))
+        n = size("dd_dconv_packed_floats", d)
         packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-        check(lib.dd_dconv_pack(_p(weight), _p(packed), C.byref(d), w_off, sn, sc, int(flip), n_real, c_real, _stream()), "dd_dconv_pack")
+        call("dd_dconv_pack", weight, packed, d, w_off, sn, sc, int(flip), n_real, c_real)
         if (colsum is not None and bias is None and epi in (EPI_NONE, EPI_RELU_MASK)
                 and lib.dd_dconv_colsum_supported(C.byref(d), epi, int(mask is not None))):
             # the launch also leaves the per-channel sums of its output: the bias gradient of the layer below (csrc/dconv_m.hip)
-            nbytes = lib.dd_dconv_colsum_workspace_bytes()
+            nbytes = size("dd_dconv_colsum_workspace_bytes")
             ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-            check(lib.dd_dconv_fwd_colsum(_p(x), _p(packed), _p(mask), _p(y), _p(colsum), C.byref(d), epi, _p(ws), nbytes, _stream()),
-                  "dd_dconv_fwd_colsum")
+            call("dd_dconv_fwd_colsum", x, packed, mask, y, colsum, d, epi, ws, nbytes)
             return "colsum"
-        check(lib.dd_dconv_fwd(_p(x), _p(packed), _p(bias), _p(mask), _p(y), C.byref(d), epi, _stream()), "dd_dconv_fwd")
+        call("dd_dconv_fwd", x, packed, bias, mask, y, d, epi)
     else:
         _fwd(x, _pack(weight, d, w_off, sn, sc, flip, n_real, c_real), bias, mask, y, d, epi)
 
 
 def _wgrad(x, dy, dw, db, d, w_off, sn, sc, flip, n_real, c_real, accumulate):
-    nbytes = _lib.lib().dd_gconv_wgrad_workspace_bytes(C.byref(d))
-    if nbytes <= 0:
-        raise _lib.HotpathError(f"gconv_wgrad: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_gconv_wgrad_workspace_bytes", d)
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    check(_lib.lib().dd_gconv_wgrad(_p(x), _p(dy), _p(dw), _p(db), C.byref(d), w_off, sn, sc, int(flip), n_real, c_real,
-                                    int(accumulate), _p(ws), nbytes, _stream()), "dd_gconv_wgrad")
+    call("dd_gconv_wgrad", x, dy, dw, db, d, w_off, sn, sc, int(flip), n_real, c_real, int(accumulate), ws, nbytes)
 
 
 class Layer:
@@ -353,12 +324,10 @@ class Layer:
               and src.buf.shape[3] == 32 and src.buf.is_contiguous() and ddst.buf.is_contiguous() and src.buf.shape[2] >= 2
               and ddst.buf.shape[1] == 2 * src.buf.shape[1] and ddst.buf.shape[2] == 2 * src.buf.shape[2]):
             # ss_deconv / the decoder's dc3: the four phases in one launch (csrc/gconv.hip, deconv2x2_c32_wgrad_kernel)
-            lib = _lib.lib()
-            nbytes = lib.dd_deconv2x2_c32_wgrad_workspace_bytes()
+            nbytes = size("dd_deconv2x2_c32_wgrad_workspace_bytes")
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             _, ih, iw, _ = src.buf.shape
-            check(lib.dd_deconv2x2_c32_wgrad(_p(src.buf), _p(ddst.buf), _p(dw), _p(db) if db is not None else None, b, ih, iw,
-                                             ddst.buf.shape[3], ddst.coff, _p(ws), nbytes, _stream()), "dd_deconv2x2_c32_wgrad")
+            call("dd_deconv2x2_c32_wgrad", src.buf, ddst.buf, dw, db, b, ih, iw, ddst.buf.shape[3], ddst.coff, ws, nbytes)
         elif self.k2s2:
             ih, iw = src.buf.shape[1:3]
             for ph in range(4):
@@ -367,28 +336,25 @@ class Layer:
         elif self.split_wgrad_ok(src, ddst):
             # EXPERIMENT: both operands as three bf16 planes, six bf16 x bf16 products per fp32 product (csrc/dconv_split.hip); the
             # split images of x (from the forward) and of dL/dy (from the data gradient) are taken over when the caller holds them
-            lib = _lib.lib()
             xs = split_rows(src) if xs is None else xs
             gs = split_rows(ddst) if gs is None else gs
-            nbytes = lib.dd_dconv_wgrad_split_workspace_bytes(self.cin, self.cout)
+            nbytes = size("dd_dconv_wgrad_split_workspace_bytes", self.cin, self.cout)
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             _, ih, iw, _ = src.buf.shape
             _, gh, gw, _ = ddst.buf.shape
-            check(lib.dd_dconv_wgrad_split(_p(xs), _p(gs), _p(dw), b, ih, iw, self.cin, gh, gw, self.cout, 0, _p(ws), nbytes, _stream()),
-                  "dd_dconv_wgrad_split")
+            call("dd_dconv_wgrad_split", xs, gs, dw, b, ih, iw, self.cin, gh, gw, self.cout, 0, ws, nbytes)
             if want_bias:
                 channel_sum(ddst, db)
         elif (DCONV and self.k[0] == self.k[1] and self.dil[0] == self.dil[1] and self.pad == (0, 0) and src.chans == self.cin
               and ddst.chans == self.cout and _whole(src) and _whole(ddst)
               and _lib.lib().dd_dconv_wgrad_supported(self.k[0], self.dil[0], self.cin, self.cout)):
             # the box heads' dilated up-convs: LDS-staged weight-gradient kernel (csrc/dconv.hip)
-            lib = _lib.lib()
-            nbytes = lib.dd_dconv_wgrad_workspace_bytes(self.k[0], self.dil[0], self.cin, self.cout)
+            nbytes = size("dd_dconv_wgrad_workspace_bytes", self.k[0], self.dil[0], self.cin, self.cout)
             ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             _, ih, iw, ics = src.buf.shape
             _, gh, gw, gcs = ddst.buf.shape
-            check(lib.dd_dconv_wgrad(_p(src.buf), _p(ddst.buf), _p(dw), b, ih, iw, ics, src.coff, self.cin, gh, gw, gcs, ddst.coff, self.cout,
-                                     self.k[0], self.dil[0], 0, _p(ws), nbytes, _stream()), "dd_dconv_wgrad")
+            call("dd_dconv_wgrad", src.buf, ddst.buf, dw, b, ih, iw, ics, src.coff, self.cin, gh, gw, gcs, ddst.coff, self.cout, self.k[0],
+                 self.dil[0], 0, ws, nbytes)
             if want_bias:
                 channel_sum(ddst, db)
         elif self.cin <= 96 and self.cout % 4 == 0 and ddst.off_h == 0 and ddst.off_w == 0:
@@ -412,23 +378,20 @@ def copy_channels(src, dst):
     assert src.chans == dst.chans and src.buf.shape[0] == dst.buf.shape[0] and (src.h, src.w) == (dst.h, dst.w)
     whole = all(v.off_h == 0 and v.off_w == 0 and v.h == v.buf.shape[1] and v.w == v.buf.shape[2] for v in (src, dst))
     if not whole:
-        check(_lib.lib().dd_copy_channels_window(_p(_chk(src.buf, "src")), _p(_chk(dst.buf, "dst")), src.buf.shape[0], src.h, src.w, src.chans,
-                                                 src.buf.shape[1], src.buf.shape[2], src.off_h, src.off_w, src.buf.shape[3], src.coff,
-                                                 dst.buf.shape[1], dst.buf.shape[2], dst.off_h, dst.off_w, dst.buf.shape[3], dst.coff,
-                                                 _stream()), "dd_copy_channels_window")
+        call("dd_copy_channels_window", _chk(src.buf, "src"), _chk(dst.buf, "dst"), src.buf.shape[0], src.h, src.w, src.chans, src.buf.shape[1],
+             src.buf.shape[2], src.off_h, src.off_w, src.buf.shape[3], src.coff, dst.buf.shape[1], dst.buf.shape[2], dst.off_h, dst.off_w,
+             dst.buf.shape[3], dst.coff)
         return
     npix = src.buf.shape[0] * src.buf.shape[1] * src.buf.shape[2]
-    check(_lib.lib().dd_copy_channels(_p(_chk(src.buf, "src")), _p(_chk(dst.buf, "dst")), npix, src.chans, src.buf.shape[3], src.coff,
-                                      dst.buf.shape[3], dst.coff, _stream()), "dd_copy_channels")
+    call("dd_copy_channels", _chk(src.buf, "src"), _chk(dst.buf, "dst"), npix, src.chans, src.buf.shape[3], src.coff, dst.buf.shape[3], dst.coff)
 
 
 def channel_sum(view, out, accumulate=False):
     """out[c] = sum over all pixels of view.buf[..., view.coff + c] (dense buffers only)."""
     b, mh, mw, cs = view.buf.shape
     assert view.off_h == 0 and view.off_w == 0 and view.h == mh and view.w == mw
-    ws = torch.empty(_lib.lib().dd_channel_sum_workspace_bytes(), device=view.buf.device, dtype=torch.uint8)
-    check(_lib.lib().dd_channel_sum(_p(view.buf), _p(out), b * mh * mw, cs, view.coff, view.chans, int(accumulate), _p(ws),
-                                    _stream()), "dd_channel_sum")
+    ws = torch.empty(size("dd_channel_sum_workspace_bytes"), device=view.buf.device, dtype=torch.uint8)
+    call("dd_channel_sum", view.buf, out, b * mh * mw, cs, view.coff, view.chans, int(accumulate), ws)
 
 
 def view_to_nhwc4(views, view, transform):
@@ -440,7 +403,7 @@ def view_to_nhwc4(views, view, transform):
         table, b, h, w, dev, _keep = ops.u8_table(views, "view_to_nhwc4")
         oh, ow = (w, h) if transform in (1, 2) else (h, w)
         out = torch.empty((b, oh, ow, 4), device=dev, dtype=torch.float32)
-        check(_lib.lib().dd_view_to_nhwc4_u8_ptrs(table, _p(out), b, h, w, view, transform, _stream()), "dd_view_to_nhwc4_u8_ptrs")
+        call("dd_view_to_nhwc4_u8_ptrs", table, out, b, h, w, view, transform)
         return out
     if isinstance(views, (tuple, list)):
         b = len(views)
@@ -451,12 +414,12 @@ def view_to_nhwc4(views, view, transform):
         oh, ow = (w, h) if transform in (1, 2) else (h, w)
         out = torch.empty((b, oh, ow, 4), device=views[0].device, dtype=torch.float32)
         table = (C.c_void_p * b)(*[t.data_ptr() for t in views])
-        check(_lib.lib().dd_view_to_nhwc4_ptrs(table, _p(out), b, h, w, view, transform, _stream()), "dd_view_to_nhwc4_ptrs")
+        call("dd_view_to_nhwc4_ptrs", table, out, b, h, w, view, transform)
         return out
     b, _, _, h, w = views.shape
     oh, ow = (w, h) if transform in (1, 2) else (h, w)
     out = torch.empty((b, oh, ow, 4), device=views.device, dtype=torch.float32)
-    check(_lib.lib().dd_view_to_nhwc4(_p(_chk(views, "views")), _p(out), b, h, w, view, transform, _stream()), "dd_view_to_nhwc4")
+    call("dd_view_to_nhwc4", _chk(views, "views"), out, b, h, w, view, transform)
     return out
 
 
@@ -507,8 +470,8 @@ def strip6_fwd(views, weights, biases, want_bits=False):
     weights = [x.contiguous() for x in weights]
     mosaic = torch.empty((b, 3 * th, 2 * tw, 32), device=dev, dtype=torch.float32)
     bits = torch.empty((b, 3 * th, 2 * tw), device=dev, dtype=torch.int32) if want_bits else None
-    check(_lib.lib().dd_strip6_fwd(table, u8, _ptr6(weights, "weight", _STRIP_SHAPES), _ptr6(biases, "bias", [(32,)] * 6), _p(mosaic),
-                                   _p(bits) if want_bits else None, b, h, w, _stream()), "dd_strip6_fwd")
+    call("dd_strip6_fwd", table, u8, _ptr6(weights, "weight", _STRIP_SHAPES), _ptr6(biases, "bias", [(32,)] * 6), mosaic, bits if want_bits else None,
+         b, h, w)
     return (mosaic, bits) if want_bits else mosaic
 
 
@@ -522,13 +485,13 @@ def strip6_wgrad(views, g):
         raise _lib.HotpathError(f"strip6_wgrad: g {tuple(g.shape)} != {(b, 3 * th, 2 * tw, 32)}")
     dws = [torch.empty(s, device=dev, dtype=torch.float32) for s in _STRIP_SHAPES]
     dbs = [torch.empty(32, device=dev, dtype=torch.float32) for _ in range(6)]
-    nbytes = _lib.lib().dd_strip6_wgrad_workspace_bytes()
+    nbytes = size("dd_strip6_wgrad_workspace_bytes")
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    check(_lib.lib().dd_strip6_wgrad(table, u8, _p(g), _ptr6(dws, "dw"), _ptr6(dbs, "db"), b, h, w, _p(ws), nbytes, _stream()), "dd_strip6_wgrad")
+    call("dd_strip6_wgrad", table, u8, g, _ptr6(dws, "dw"), _ptr6(dbs, "db"), b, h, w, ws, nbytes)
     return dws, dbs
 
 
 def add(a, b):
     out = torch.empty_like(a)
-    check(_lib.lib().dd_add(_p(_chk(a, "a")), _p(_chk(b, "b")), _p(out), a.numel(), _stream()), "dd_add")
+    call("dd_add", _chk(a, "a"), _chk(b, "b"), out, a.numel())
     return out

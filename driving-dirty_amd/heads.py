@@ -14,8 +14,8 @@ import os
 import torch
 
 from . import _lib, ops
-from ._lib import check
-from .gconv import EPI_BIAS, EPI_BIAS_RELU, Layer, View, _p, _stream, add, copy_channels, view_to_nhwc4
+from ._lib import call, size
+from .gconv import EPI_BIAS, EPI_BIAS_RELU, Layer, View, add, copy_channels, view_to_nhwc4
 from . import gconv as gconv_mod
 from .gconv import split_rows as gconv_split_rows
 
@@ -84,7 +84,7 @@ class DecoderConvStack(torch.autograd.Function):
         if c != 32 or h < 4 or w < 4:
             return None
         d = ops.conv_desc(b, h, w, 32, 1)
-        return d if ops._lib.lib().dd_conv_wino2_packed_floats(ops.C.byref(d)) > 0 else None
+        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
 
     @staticmethod
     def _as_conv(w):
@@ -184,7 +184,7 @@ class SpatialMapFn(torch.autograd.Function):
         if c != 32 or not mosaic.is_contiguous() or mh < 4 or mw < 4:
             return None
         d = ops.conv_desc(b, mh, mw, 32, 1)
-        return d if ops._lib.lib().dd_conv_wino2_packed_floats(ops.C.byref(d)) > 0 else None
+        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
 
     @staticmethod
     def forward(ctx, views, *params):
@@ -316,7 +316,7 @@ class MergeFn(torch.autograd.Function):
         if ph < 4 or pw < 4:
             return None
         d = ops.conv_desc(9 * b, ph, pw, 32, 1)
-        return d if ops._lib.lib().dd_conv_wino2_packed_floats(ops.C.byref(d)) > 0 else None
+        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
 
     @staticmethod
     def _dense_from_phase3(p, oh, ow):
@@ -392,8 +392,7 @@ class MergeFn(torch.autograd.Function):
         ctx.split_mode = gconv_mod.SPLIT_BF16                # the backward runs in the precision mode of its forward (gconv.split_products)
         u = acts[-1]
         probs = _empty((b, 2 * u.shape[1], 2 * u.shape[2]), dev)
-        check(_lib.lib().dd_deconv2x2_c1_fwd(_p(u), _p(p_last[0]), _p(p_last[1]), _p(probs), b, u.shape[1], u.shape[2], 8,
-                                             _stream()), "dd_deconv2x2_c1_fwd")
+        call("dd_deconv2x2_c1_fwd", u, p_last[0], p_last[1], probs, b, u.shape[1], u.shape[2], 8)
         if TRACE is not None:
             TRACE.update(s1=s1, cat=cat, r1=cls._dense_from_phase3(r1, rh, rw) if ctx.wino_rm2 else r1, acts=acts)
         ctx.with_rm = with_rm
@@ -421,9 +420,8 @@ class MergeFn(torch.autograd.Function):
         # last layer: sigmoid' and the ReLU mask of u are applied inside
         gu = _empty(u.shape, dev)
         dw_last, db_last = torch.empty_like(w_last), _empty((1,), dev)
-        ws = torch.empty(_lib.lib().dd_deconv2x2_c1_workspace_bytes(8), device=dev, dtype=torch.uint8)
-        check(_lib.lib().dd_deconv2x2_c1_bwd(_p(u), _p(w_last), _p(probs), _p(gprobs.contiguous()), _p(gu), _p(dw_last), _p(db_last),
-                                             b, u.shape[1], u.shape[2], 8, _p(ws), _stream()), "dd_deconv2x2_c1_bwd")
+        ws = torch.empty(size("dd_deconv2x2_c1_workspace_bytes", 8), device=dev, dtype=torch.uint8)
+        call("dd_deconv2x2_c1_bwd", u, w_last, probs, gprobs.contiguous(), gu, dw_last, db_last, b, u.shape[1], u.shape[2], 8, ws)
         g = gu
         g_planes = None                              # split-product experiment: the bf16 planes of g, when the kernel that produced g wrote them
         db_from_above = None                         # this layer's bias gradient, when the data gradient above already summed dL/dy

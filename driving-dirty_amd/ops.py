@@ -12,38 +12,12 @@ import torch
 
 from . import _lib
 from . import ddp as _ddp
-from ._lib import ConvDesc, check
+from ._lib import ConvDesc, call, check, size  # noqa: F401  (check, C: tools/ and tests reach them as ops.check, ops.C)
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_RELU_MASK = 0, 1, 2, 3
 PACK_FWD, PACK_DGRAD_S1, PACK_DGRAD_S2 = 0, 1, 2
 
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    """Device pointer of a kernel operand.  A parameter whose all-gather (sharded optimizer, ddp.GradSync) is still in flight
-    is waited for -- on the current stream -- the first time it is handed to a kernel."""
-    if t is None:
-        return None
-    ptr = t.data_ptr()
-    if _ddp.PARAM_WAITS:
-        wait = _ddp.PARAM_WAITS.pop(ptr, None)
-        if wait is not None:
-            wait()
-    return C.c_void_p(ptr)
-
-
-def _dev(t, name, shape=None):
-    """Validate a kernel operand on the HOST before any launch (a faulting kernel can reset the GPU)."""
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-        raise _lib.HotpathError(f"{name}: expected a contiguous fp32 device tensor, got "
-                                f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')} "
-                                f"contiguous={getattr(t, 'is_contiguous', lambda: '?')()}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise _lib.HotpathError(f"{name}: shape {tuple(t.shape)} != expected {tuple(shape)}")
-    return t
+_stream, _p, _dev = _lib.stream, _lib.ptr, _lib.dev      # the operand helpers live in _lib; these names stay for tools/ and tests
 
 
 def conv_out(n, stride):
@@ -64,7 +38,7 @@ def stitch6(views, mask_slot=-1, want_nhwc4=True, want_nchw=False, want_target=F
     wide4 = torch.empty((b, h, 6 * w, 4), device=views.device, dtype=torch.float32) if want_nhwc4 else None
     wide = torch.empty((b, 3, h, 6 * w), device=views.device, dtype=torch.float32) if want_nchw else None
     tgt = torch.empty((b, 3, h, w), device=views.device, dtype=torch.float32) if want_target else None
-    check(_lib.lib().dd_stitch6(_p(views), _p(wide4), _p(wide), _p(tgt), b, h, w, int(mask_slot), _stream()), "dd_stitch6")
+    call("dd_stitch6", views, wide4, wide, tgt, b, h, w, int(mask_slot))
     return wide4, wide, tgt
 
 
@@ -79,7 +53,7 @@ def stitch6_samples(samples):
         raise _lib.HotpathError(f"stitch6_samples: expected samples of [6,3,H,W], got {tuple(samples[0].shape)}")
     table = (ctypes.c_void_p * b)(*[t.data_ptr() for t in samples])
     wide4 = torch.empty((b, h, 6 * w, 4), device=samples[0].device, dtype=torch.float32)
-    check(_lib.lib().dd_stitch6_ptrs(table, _p(wide4), b, h, w, _stream()), "dd_stitch6_ptrs")
+    call("dd_stitch6_ptrs", table, wide4, b, h, w)
     return wide4
 
 
@@ -104,8 +78,7 @@ def boxes_to_binary_map(box_sets, device=None):
     offsets = (ctypes.c_int32 * (b + 1))(0, *[sum(counts[:i + 1]) for i in range(b)])
     flat = torch.cat([t.reshape(-1, 8) for t in box_sets], dim=0).to(device).contiguous()
     maps = torch.empty((b, 800, 800), device=device, dtype=torch.float32)
-    check(_lib.lib().dd_boxes_to_binary_map(_p(flat) if flat.numel() else None, 0 if dtype == torch.float64 else 1, offsets,
-                                            _p(maps), b, _stream()), "dd_boxes_to_binary_map")
+    call("dd_boxes_to_binary_map", flat if flat.numel() else None, 0 if dtype == torch.float64 else 1, offsets, maps, b)
     return maps
 
 
@@ -115,7 +88,7 @@ def stitch6_u8(frames):
     if n != 6 or c != 3 or frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous():
         raise _lib.HotpathError(f"stitch6_u8: expected contiguous uint8 [B,6,H,W,3] on the GPU, got {tuple(frames.shape)} {frames.dtype}")
     out = torch.empty((b, h, 6 * w, 4), device=frames.device, dtype=torch.float32)
-    check(_lib.lib().dd_stitch6_u8(_p(frames), _p(out), b, h, w, _stream()), "dd_stitch6_u8")
+    call("dd_stitch6_u8", frames, out, b, h, w)
     return out
 
 
@@ -152,7 +125,7 @@ def stitch6_u8_samples(sample, mask_slot=-1, want_target=False):
     table, b, h, w, dev, _keep = u8_table(sample, "stitch6_u8_samples")
     wide4 = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.float32)
     tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
-    check(_lib.lib().dd_stitch6_u8_ptrs(table, _p(wide4), _p(tgt), b, h, w, int(mask_slot), _stream()), "dd_stitch6_u8_ptrs")
+    call("dd_stitch6_u8_ptrs", table, wide4, tgt, b, h, w, int(mask_slot))
     return (wide4, tgt) if want_target else wide4
 
 
@@ -185,8 +158,8 @@ def threat_score(a, b, round_b=False):
     _dev(a, "a")
     _dev(b, "b", a.shape)
     out = torch.empty((), device=a.device, dtype=torch.float32)
-    ws = torch.empty(_lib.lib().dd_threat_score_workspace_bytes(), device=a.device, dtype=torch.uint8)
-    check(_lib.lib().dd_threat_score(_p(a), _p(b), _p(out), a.numel(), int(round_b), _p(ws), _stream()), "dd_threat_score")
+    ws = torch.empty(size("dd_threat_score_workspace_bytes"), device=a.device, dtype=torch.uint8)
+    call("dd_threat_score", a, b, out, a.numel(), int(round_b), ws)
     return out
 
 
@@ -207,7 +180,7 @@ def ts_histogram(prob, target, bins=TS_BINS, out=None):
     elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and tuple(out.shape) == (2, bins + 1)):
         raise _lib.HotpathError(f"ts_histogram: out must be a contiguous int64 device tensor [2, {bins + 1}]")
     kind = 0 if target.dtype == torch.float32 else 1      # DD_TARGET_F32 / DD_TARGET_U8
-    check(_lib.lib().dd_ts_hist(_p(prob), _p(target), kind, prob.numel(), int(bins), _p(out), _stream()), "dd_ts_hist")
+    call("dd_ts_hist", prob, target, kind, prob.numel(), int(bins), out)
     return out
 
 
@@ -245,7 +218,7 @@ def label_components(maps, threshold=0.5):
     1 + the raster-order index (inside its sample) of the component's first pixel.  Canonical and deterministic."""
     b, h, w = _maps(maps, "label_components")
     labels = torch.empty((b, h, w), device=maps.device, dtype=torch.int32)
-    check(_lib.lib().dd_label_components(_p(maps), float(threshold), _p(labels), b, h, w, _stream()), "dd_label_components")
+    call("dd_label_components", maps, float(threshold), labels, b, h, w)
     return labels
 
 
@@ -266,13 +239,10 @@ def split_components(maps, threshold=0.5, split_px=4, grow_iters=None):
     some pixel of its region, not necessarily the first.  ``split_px`` in [1,8], ``grow_iters`` in [0,16].  Integer only: deterministic."""
     b, h, w = _maps(maps, "split_components")
     split_px, grow_iters = _split_args(split_px, grow_iters, "split_components")
-    nbytes = _lib.lib().dd_split_components_workspace_bytes(b, h, w, split_px, grow_iters)
-    if nbytes < 0:
-        raise _lib.HotpathError(f"split_components: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_split_components_workspace_bytes", b, h, w, split_px, grow_iters)
     labels = torch.empty((b, h, w), device=maps.device, dtype=torch.int32)
     ws = torch.empty(nbytes, device=maps.device, dtype=torch.uint8)
-    check(_lib.lib().dd_split_components(_p(maps), float(threshold), split_px, grow_iters, _p(labels), b, h, w, _p(ws), nbytes, _stream()),
-          "dd_split_components")
+    call("dd_split_components", maps, float(threshold), split_px, grow_iters, labels, b, h, w, ws, nbytes)
     return labels
 
 
@@ -285,22 +255,23 @@ def _fit_args(who, fit, want_moments):
 
 def _fit(who, entries, src, lead, min_pixels, max_boxes, fit, pad_px, want_moments):
     """What ``component_boxes`` and ``labelled_boxes`` share: ``src`` [B,H,W] (maps or labels, already checked) through
-    ``entries`` = the (extent, oriented) pair of C entry points, whose arguments begin with ``lead`` (the source pointer, and the threshold)."""
+    ``entries`` = the (extent, oriented) pair of C entry points, whose arguments begin with ``lead`` (the source, and the threshold)."""
     min_pixels, max_boxes = int(min_pixels), int(max_boxes)
     if min_pixels < 1 or max_boxes < 1:
         raise _lib.HotpathError(f"{who}: min_pixels and max_boxes must be positive")
     b, h, w = src.shape
-    lib, oriented = _lib.lib(), fit == "oriented"
+    oriented = fit == "oriented"
     entry = entries[oriented]
-    nbytes = getattr(lib, entry + "_workspace_bytes")(b, h, w, *((max_boxes,) if oriented else ()))
+    # not size(): the refusal keeps this function's own message (who, and the shape that was refused)
+    nbytes = getattr(_lib.lib(), entry + "_workspace_bytes")(b, h, w, *((max_boxes,) if oriented else ()))
     if b == 0 or nbytes < 0:
-        raise _lib.HotpathError(f"{who}: unsupported shape {tuple(src.shape)}: {lib.dd_last_error().decode()}")
+        raise _lib.HotpathError(f"{who}: unsupported shape {tuple(src.shape)}: {_lib.lib().dd_last_error().decode()}")
     boxes = torch.zeros((b, max_boxes, 2, 4), device=src.device, dtype=torch.float32)
     counts = torch.empty((b,), device=src.device, dtype=torch.int32)
     moments = torch.zeros((b, max_boxes, 6), device=src.device, dtype=torch.int64) if want_moments else None
     ws = torch.empty(nbytes, device=src.device, dtype=torch.uint8)
-    out = (float(pad_px), _p(boxes), _p(counts), _p(moments)) if oriented else (_p(boxes), _p(counts))
-    check(getattr(lib, entry)(*lead, min_pixels, max_boxes, *out, b, h, w, _p(ws), nbytes, _stream()), entry)
+    out = (float(pad_px), boxes, counts, moments) if oriented else (boxes, counts)
+    call(entry, *lead, min_pixels, max_boxes, *out, b, h, w, ws, nbytes)
     return (boxes, counts, moments) if want_moments else (boxes, counts)
 
 
@@ -313,7 +284,7 @@ def labelled_boxes(labels, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5
                                 f"{tuple(getattr(labels, 'shape', ()))}")
     if not labels.is_cuda or not labels.is_contiguous():
         raise _lib.HotpathError("labelled_boxes: labels must be a contiguous GPU tensor (there is no CPU fallback)")
-    return _fit("labelled_boxes", ("dd_labelled_boxes", "dd_labelled_obb"), labels, (_p(labels),), min_pixels, max_boxes, fit, pad_px, want_moments)
+    return _fit("labelled_boxes", ("dd_labelled_boxes", "dd_labelled_obb"), labels, (labels,), min_pixels, max_boxes, fit, pad_px, want_moments)
 
 
 def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, want_moments=False, split_px=0, grow_iters=None):
@@ -337,7 +308,7 @@ def component_boxes(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="exten
     if split_px != 0:
         return labelled_boxes(split_components(maps, threshold, split_px, grow_iters), min_pixels, max_boxes, fit, pad_px, want_moments)
     _maps(maps, "component_boxes")
-    return _fit("component_boxes", ("dd_component_boxes", "dd_component_obb"), maps, (_p(maps), float(threshold)), min_pixels, max_boxes, fit, pad_px,
+    return _fit("component_boxes", ("dd_component_boxes", "dd_component_obb"), maps, (maps, float(threshold)), min_pixels, max_boxes, fit, pad_px,
                 want_moments)
 
 
@@ -364,15 +335,13 @@ def _iou_ats(box_sets1, box_sets2, want_iou, who):
         raise _lib.HotpathError(f"{who}: no box tensor is on a GPU (there is no CPU fallback)")
     flat1, dt1, off1 = _box_list(box_sets1, who, device)
     flat2, dt2, off2 = _box_list(box_sets2, who, device)
-    nbytes = _lib.lib().dd_box_iou_ats_workspace_bytes(off1, off2, b)
-    if nbytes < 0:
-        raise _lib.HotpathError(f"{who}: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_box_iou_ats_workspace_bytes", off1, off2, b)
     ats = torch.empty((b,), device=device, dtype=torch.float32)
     pairs = sum(int(s.shape[0]) * int(t.shape[0]) for s, t in zip(box_sets1, box_sets2))
     iou = torch.empty((max(pairs, 1),), device=device, dtype=torch.float32) if want_iou else None
     ws = None if want_iou else torch.empty(nbytes, device=device, dtype=torch.uint8)
-    check(_lib.lib().dd_box_iou_ats(_p(flat1) if flat1.numel() else None, dt1, off1, _p(flat2) if flat2.numel() else None, dt2, off2,
-                                    _p(iou), _p(ats), b, _p(ws), 0 if want_iou else nbytes, _stream()), "dd_box_iou_ats")
+    call("dd_box_iou_ats", flat1 if flat1.numel() else None, dt1, off1, flat2 if flat2.numel() else None, dt2, off2, iou, ats, b, ws,
+         0 if want_iou else nbytes)
     return iou, ats
 
 
@@ -395,7 +364,7 @@ def nchw_to_nhwc(x, c_store):
     b, c, h, w = x.shape
     _dev(x, "x")
     out = torch.empty((b, h, w, c_store), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_nchw_to_nhwc(_p(x), _p(out), b, c, h, w, c_store, _stream()), "dd_nchw_to_nhwc")
+    call("dd_nchw_to_nhwc", x, out, b, c, h, w, c_store)
     return out
 
 
@@ -405,7 +374,7 @@ def subsample_nhwc4(x, stride, offset, oh, ow):
     b, h, w = x.shape[0], x.shape[-2], x.shape[-1]
     assert x.numel() == b * h * w, "subsample_nhwc4: one channel"
     out = torch.empty((b, oh, ow, 4), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_subsample_nhwc4(_p(x.contiguous()), _p(out), b, h, w, oh, ow, stride, offset, _stream()), "dd_subsample_nhwc4")
+    call("dd_subsample_nhwc4", x.contiguous(), out, b, h, w, oh, ow, stride, offset)
     return out
 
 
@@ -421,7 +390,7 @@ def subsample_masks_nhwc4(masks, stride, offset, oh, ow):
             raise _lib.HotpathError("subsample_masks_nhwc4: expected contiguous bool / uint8 device masks of one size")
     out = torch.empty((b, oh, ow, 4), device=masks[0].device, dtype=torch.float32)
     table = (ctypes.c_void_p * b)(*[t.data_ptr() for t in masks])
-    check(_lib.lib().dd_subsample_nhwc4_u8_ptrs(table, _p(out), b, h, w, oh, ow, stride, offset, _stream()), "dd_subsample_nhwc4_u8_ptrs")
+    call("dd_subsample_nhwc4_u8_ptrs", table, out, b, h, w, oh, ow, stride, offset)
     return out
 
 
@@ -430,7 +399,7 @@ def deconv2x2_c32_fwd(x, wt, bias, relu=True):
     b, h, w, c = x.shape
     assert c == 32 and tuple(wt.shape) == (32, 32, 2, 2) and x.is_contiguous() and wt.is_contiguous()
     out = torch.empty((b, 2 * h, 2 * w, 32), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_deconv2x2_c32_fwd(_p(x), _p(wt), _p(bias), _p(out), b, h, w, int(relu), _stream()), "dd_deconv2x2_c32_fwd")
+    call("dd_deconv2x2_c32_fwd", x, wt, bias, out, b, h, w, int(relu))
     return out
 
 
@@ -439,8 +408,7 @@ def deconv2x2_c32_fwd_into(x, wt, bias, out, coff, relu=True):
     b, h, w, c = x.shape
     assert c == 32 and tuple(wt.shape) == (32, 32, 2, 2) and x.is_contiguous() and wt.is_contiguous()
     assert out.is_contiguous() and tuple(out.shape[:3]) == (b, 2 * h, 2 * w) and 0 <= coff and coff + 32 <= out.shape[3]
-    check(_lib.lib().dd_deconv2x2_c32_fwd_slice(_p(x), _p(wt), _p(bias), _p(out), b, h, w, int(relu), out.shape[3], coff, _stream()),
-          "dd_deconv2x2_c32_fwd_slice")
+    call("dd_deconv2x2_c32_fwd_slice", x, wt, bias, out, b, h, w, int(relu), out.shape[3], coff)
 
 
 def ssconv_dgrad_ok(g, dx):
@@ -453,14 +421,14 @@ def ssconv_dgrad(g, wt, dx):
     """g [B,h,gw,32], wt [32,32,1,24] (Conv2d weight) -> dx [B,h,xw,32] = dL/d(input) of Conv2d(32,32,(1,24),stride (1,7))."""
     assert tuple(wt.shape) == (32, 32, 1, 24) and wt.is_contiguous() and ssconv_dgrad_ok(g, dx)
     b, h, gw, _ = g.shape
-    check(_lib.lib().dd_ssconv_dgrad(_p(g), _p(wt), _p(dx), b, h, gw, dx.shape[2], _stream()), "dd_ssconv_dgrad")
+    call("dd_ssconv_dgrad", g, wt, dx, b, h, gw, dx.shape[2])
 
 
 def ssconv_fwd(x, wt, bias, y, relu=True):
     """x [B,h,xw,32], wt [32,32,1,24], bias [32] or None -> y [B,h,gw,32] = (relu)(Conv2d(32,32,(1,24),stride (1,7))(x)), one launch."""
     assert tuple(wt.shape) == (32, 32, 1, 24) and wt.is_contiguous() and ssconv_dgrad_ok(y, x)
     b, h, xw, _ = x.shape
-    check(_lib.lib().dd_ssconv_fwd(_p(x), _p(wt), _p(bias), _p(y), b, h, xw, y.shape[2], int(relu), _stream()), "dd_ssconv_fwd")
+    call("dd_ssconv_fwd", x, wt, bias, y, b, h, xw, y.shape[2], int(relu))
 
 
 def conv1x1_c32_c3_nchw(x, wt, bias):
@@ -468,7 +436,7 @@ def conv1x1_c32_c3_nchw(x, wt, bias):
     b, h, w, c = x.shape
     assert c == 32 and tuple(wt.shape) == (32, 3, 1, 1) and x.is_contiguous() and wt.is_contiguous()
     out = torch.empty((b, 3, h, w), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv1x1_c32_c3_nchw(_p(x), _p(wt), _p(bias), _p(out), b, h, w, _stream()), "dd_conv1x1_c32_c3_nchw")
+    call("dd_conv1x1_c32_c3_nchw", x, wt, bias, out, b, h, w)
     return out
 
 
@@ -477,7 +445,7 @@ def conv1ch_fwd(taps4, w, bias, relu=True):
     b, sh, sw, _ = taps4.shape
     assert tuple(w.shape) == (32, 1, 7, 7) and w.is_contiguous()
     y = torch.empty((b, sh - 6, sw - 6, 32), device=taps4.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv1ch_fwd(_p(taps4), _p(w), _p(bias), _p(y), b, sh, sw, int(relu), _stream()), "dd_conv1ch_fwd")
+    call("dd_conv1ch_fwd", taps4, w, bias, y, b, sh, sw, int(relu))
     return y
 
 
@@ -487,8 +455,8 @@ def conv1ch_wgrad(taps4, g):
     assert tuple(g.shape) == (b, sh - 6, sw - 6, 32) and g.is_contiguous()
     dw = torch.empty((32, 1, 7, 7), device=g.device, dtype=torch.float32)
     db = torch.empty(32, device=g.device, dtype=torch.float32)
-    ws = torch.empty(_lib.lib().dd_conv1ch_wgrad_workspace_bytes(), device=g.device, dtype=torch.uint8)
-    check(_lib.lib().dd_conv1ch_wgrad(_p(taps4), _p(g), _p(dw), _p(db), b, sh, sw, _p(ws), _stream()), "dd_conv1ch_wgrad")
+    ws = torch.empty(size("dd_conv1ch_wgrad_workspace_bytes"), device=g.device, dtype=torch.uint8)
+    call("dd_conv1ch_wgrad", taps4, g, dw, db, b, sh, sw, ws)
     return dw, db
 
 
@@ -500,7 +468,7 @@ def conv1ch_fwd_phase3(taps4, w, bias, relu=True):
     ph, pw = (sh - 6 + 2) // 3, (sw - 6 + 2) // 3
     y = torch.empty((9 * b, ph, pw, 32), device=taps4.device, dtype=torch.float32)
     bits = torch.empty((9 * b, ph, pw), device=taps4.device, dtype=torch.int32)
-    check(_lib.lib().dd_conv1ch_fwd_phase3(_p(taps4), _p(w), _p(bias), _p(y), _p(bits), b, sh, sw, int(relu), _stream()), "dd_conv1ch_fwd_phase3")
+    call("dd_conv1ch_fwd_phase3", taps4, w, bias, y, bits, b, sh, sw, int(relu))
     return y, bits
 
 
@@ -511,8 +479,8 @@ def conv1ch_wgrad_phase3(taps4, g_phase):
     assert tuple(g_phase.shape) == (9 * b, ph, pw, 32) and g_phase.is_contiguous()
     dw = torch.empty((32, 1, 7, 7), device=g_phase.device, dtype=torch.float32)
     db = torch.empty(32, device=g_phase.device, dtype=torch.float32)
-    ws = torch.empty(_lib.lib().dd_conv1ch_wgrad_workspace_bytes(), device=g_phase.device, dtype=torch.uint8)
-    check(_lib.lib().dd_conv1ch_wgrad_phase3(_p(taps4), _p(g_phase), _p(dw), _p(db), b, sh, sw, _p(ws), _stream()), "dd_conv1ch_wgrad_phase3")
+    ws = torch.empty(size("dd_conv1ch_wgrad_workspace_bytes"), device=g_phase.device, dtype=torch.uint8)
+    call("dd_conv1ch_wgrad_phase3", taps4, g_phase, dw, db, b, sh, sw, ws)
     return dw, db
 
 
@@ -522,8 +490,7 @@ def phase3_scatter(src_phase, dst, coff, off):
     _dev(dst, "dst")
     b, oh, ow, cs = dst.shape
     assert src_phase.shape[0] == 9 * b and src_phase.shape[3] == 32
-    check(_lib.lib().dd_phase3_scatter(_p(src_phase), _p(dst), b, oh, ow, src_phase.shape[1], src_phase.shape[2], off, cs, coff, _stream()),
-          "dd_phase3_scatter")
+    call("dd_phase3_scatter", src_phase, dst, b, oh, ow, src_phase.shape[1], src_phase.shape[2], off, cs, coff)
 
 
 def phase3_gather(src, coff, ph, pw, off):
@@ -531,7 +498,7 @@ def phase3_gather(src, coff, ph, pw, off):
     _dev(src, "src")
     b, oh, ow, cs = src.shape
     out = torch.empty((9 * b, ph, pw, 32), device=src.device, dtype=torch.float32)
-    check(_lib.lib().dd_phase3_gather(_p(src), _p(out), b, oh, ow, ph, pw, off, cs, coff, _stream()), "dd_phase3_gather")
+    call("dd_phase3_gather", src, out, b, oh, ow, ph, pw, off, cs, coff)
     return out
 
 
@@ -539,7 +506,7 @@ def nhwc_to_nchw(x, c):
     b, h, w, cs = x.shape
     _dev(x, "x")
     out = torch.empty((b, c, h, w), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_nhwc_to_nchw(_p(x), _p(out), b, c, h, w, cs, _stream()), "dd_nhwc_to_nchw")
+    call("dd_nhwc_to_nchw", x, out, b, c, h, w, cs)
     return out
 
 
@@ -559,11 +526,9 @@ class ToNHWC(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------ conv primitives
 def conv_pack(weight, desc, kind):
     _dev(weight, "weight", (32, desc.cin_real, 3, 3))
-    n = _lib.lib().dd_conv_packed_floats(C.byref(desc), kind)
-    if n <= 0:
-        raise _lib.HotpathError(f"conv_pack: {_lib.lib().dd_last_error().decode()}")
+    n = size("dd_conv_packed_floats", desc, kind)
     packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_pack(_p(weight), _p(packed), C.byref(desc), kind, _stream()), "dd_conv_pack")
+    call("dd_conv_pack", weight, packed, desc, kind)
     return packed
 
 
@@ -575,7 +540,7 @@ def conv_fwd(x, packed, bias, desc, epilogue=EPI_BIAS_RELU, mask=None):
     if mask is not None:
         _dev(mask, "mask", (desc.batch, ho, wo, 32))
     y = torch.empty((desc.batch, ho, wo, 32), device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_fwd(_p(x), _p(packed), _p(bias), _p(mask), _p(y), C.byref(desc), epilogue, _stream()), "dd_conv_fwd")
+    call("dd_conv_fwd", x, packed, bias, mask, y, desc, epilogue)
     return y
 
 
@@ -586,7 +551,7 @@ def conv_fwd_bits(x, packed, bias, desc):
     _dev(bias, "bias", (32,))
     y = torch.empty((desc.batch, ho, wo, 32), device=x.device, dtype=torch.float32)
     bits = torch.empty((desc.batch, ho, wo), device=x.device, dtype=torch.int32)
-    check(_lib.lib().dd_conv_fwd_relu_bits(_p(x), _p(packed), _p(bias), _p(y), _p(bits), C.byref(desc), _stream()), "dd_conv_fwd_relu_bits")
+    call("dd_conv_fwd_relu_bits", x, packed, bias, y, bits, desc)
     return y, bits
 
 
@@ -597,64 +562,81 @@ WINOGRAD = True
 WINOGRAD_2D = True      # forward / data gradient of c2 by F(2x2,3x3) instead of F(2,3) along x (16 instead of 24 multiplies per tile)
 
 
-def conv_wino_pack(weight, desc, kind):
+def _relu_bits(bits, desc, who):
+    """The ReLU sign words a data gradient masks with: one int32 per pixel of the layer's input."""
+    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
+        raise _lib.HotpathError(f"{who}: relu_bits must be a contiguous int32 [B,H,W] device tensor")
+    return bits
+
+
+# The two Winograd families of c2 -- "dd_conv_wino" (F(2,3) along x) and "dd_conv_wino2" (F(2x2,3x3)) -- have the same entry points
+# with the same contracts: one body each, the public names below pick the family.
+def _wino_pack(family, weight, desc, kind):
     _dev(weight, "weight", (32, 32, 3, 3))
-    n = _lib.lib().dd_conv_wino_packed_floats(C.byref(desc))
-    if n <= 0:
-        raise _lib.HotpathError(f"conv_wino_pack: {_lib.lib().dd_last_error().decode()}")
-    packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino_pack(_p(weight), _p(packed), C.byref(desc), kind, _stream()), "dd_conv_wino_pack")
+    packed = torch.empty(size(family + "_packed_floats", desc), device=weight.device, dtype=torch.float32)
+    call(family + "_pack", weight, packed, desc, kind)
     return packed
+
+
+def _wino_fwd_bits(family, x, packed, bias, desc):
+    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
+    _dev(bias, "bias", (32,))
+    y = torch.empty((desc.batch, desc.height, desc.width, 32), device=x.device, dtype=torch.float32)
+    bits = torch.empty((desc.batch, desc.height, desc.width), device=x.device, dtype=torch.int32)
+    call(family + "_fwd_relu_bits", x, packed, bias, y, bits, desc)
+    return y, bits
+
+
+def _wino_dgrad_bits(family, dy, packed, bits, desc):
+    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
+    _relu_bits(bits, desc, family[3:] + "_dgrad_bits")
+    dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
+    call(family + "_dgrad_relu_bits", dy, packed, bits, dx, desc)
+    return dx
+
+
+def _wino_wgrad_buffers(family, x, dy, desc):
+    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
+    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
+    nbytes = size(family + "_wgrad_workspace_bytes", desc)
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    dw = torch.empty((32, 32, 3, 3), device=x.device, dtype=torch.float32)
+    db = torch.empty(32, device=x.device, dtype=torch.float32)
+    return ws, nbytes, dw, db
+
+
+def _wino_wgrad(family, x, dy, desc):
+    ws, nbytes, dw, db = _wino_wgrad_buffers(family, x, dy, desc)
+    call(family + "_wgrad", x, dy, dw, db, ws, nbytes, desc)
+    return dw, db
+
+
+def conv_wino_pack(weight, desc, kind):
+    return _wino_pack("dd_conv_wino", weight, desc, kind)
 
 
 def conv_wino_fwd_bits(x, packed, bias, desc):
-    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
-    _dev(bias, "bias", (32,))
-    y = torch.empty((desc.batch, desc.height, desc.width, 32), device=x.device, dtype=torch.float32)
-    bits = torch.empty((desc.batch, desc.height, desc.width), device=x.device, dtype=torch.int32)
-    check(_lib.lib().dd_conv_wino_fwd_relu_bits(_p(x), _p(packed), _p(bias), _p(y), _p(bits), C.byref(desc), _stream()),
-          "dd_conv_wino_fwd_relu_bits")
-    return y, bits
+    return _wino_fwd_bits("dd_conv_wino", x, packed, bias, desc)
 
 
 def conv_wino_dgrad_bits(dy, packed, bits, desc):
-    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
-    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
-        raise _lib.HotpathError("conv_wino_dgrad_bits: relu_bits must be a contiguous int32 [B,H,W] device tensor")
-    dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino_dgrad_relu_bits(_p(dy), _p(packed), _p(bits), _p(dx), C.byref(desc), _stream()),
-          "dd_conv_wino_dgrad_relu_bits")
-    return dx
+    return _wino_dgrad_bits("dd_conv_wino", dy, packed, bits, desc)
+
+
+def conv_wino_wgrad(x, dy, desc):
+    return _wino_wgrad("dd_conv_wino", x, dy, desc)
 
 
 def conv_wino2_pack(weight, desc, kind):
-    _dev(weight, "weight", (32, 32, 3, 3))
-    n = _lib.lib().dd_conv_wino2_packed_floats(C.byref(desc))
-    if n <= 0:
-        raise _lib.HotpathError(f"conv_wino2_pack: {_lib.lib().dd_last_error().decode()}")
-    packed = torch.empty(n, device=weight.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino2_pack(_p(weight), _p(packed), C.byref(desc), kind, _stream()), "dd_conv_wino2_pack")
-    return packed
+    return _wino_pack("dd_conv_wino2", weight, desc, kind)
 
 
 def conv_wino2_fwd_bits(x, packed, bias, desc):
-    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
-    _dev(bias, "bias", (32,))
-    y = torch.empty((desc.batch, desc.height, desc.width, 32), device=x.device, dtype=torch.float32)
-    bits = torch.empty((desc.batch, desc.height, desc.width), device=x.device, dtype=torch.int32)
-    check(_lib.lib().dd_conv_wino2_fwd_relu_bits(_p(x), _p(packed), _p(bias), _p(y), _p(bits), C.byref(desc), _stream()),
-          "dd_conv_wino2_fwd_relu_bits")
-    return y, bits
+    return _wino_fwd_bits("dd_conv_wino2", x, packed, bias, desc)
 
 
 def conv_wino2_dgrad_bits(dy, packed, bits, desc):
-    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
-    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
-        raise _lib.HotpathError("conv_wino2_dgrad_bits: relu_bits must be a contiguous int32 [B,H,W] device tensor")
-    dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino2_dgrad_relu_bits(_p(dy), _p(packed), _p(bits), _p(dx), C.byref(desc), _stream()),
-          "dd_conv_wino2_dgrad_relu_bits")
-    return dx
+    return _wino_dgrad_bits("dd_conv_wino2", dy, packed, bits, desc)
 
 
 def conv_wino2_dgrad_w1(dy, packed, bits, x4, desc):
@@ -662,62 +644,38 @@ def conv_wino2_dgrad_w1(dy, packed, bits, x4, desc):
     (dd_conv_wino2_dgrad_w1: g1 is never written to or re-read from HBM)."""
     _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
     _dev(x4, "x4", (desc.batch, desc.height, desc.width, 4))
-    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
-        raise _lib.HotpathError("conv_wino2_dgrad_w1: relu_bits must be a contiguous int32 [B,H,W] device tensor")
-    n = _lib.lib().dd_conv_wino2_dgrad_w1_workspace_bytes(C.byref(desc))
+    _relu_bits(bits, desc, "conv_wino2_dgrad_w1")
+    n = size("dd_conv_wino2_dgrad_w1_workspace_bytes", desc)
     ws = torch.empty(n, device=dy.device, dtype=torch.uint8)
     dw = torch.empty((32, 3, 3, 3), device=dy.device, dtype=torch.float32)
     db = torch.empty((32,), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino2_dgrad_w1(_p(dy), _p(packed), _p(bits), _p(x4), _p(dw), _p(db), _p(ws), n, C.byref(desc),
-                                            _stream()), "dd_conv_wino2_dgrad_w1")
+    call("dd_conv_wino2_dgrad_w1", dy, packed, bits, x4, dw, db, ws, n, desc)
     return dw, db
 
 
 def conv_wino2_wgrad(x, dy, desc, finish_stream=None):
-    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
-    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
-    nbytes = _lib.lib().dd_conv_wino2_wgrad_workspace_bytes(C.byref(desc))
-    if nbytes <= 0:
-        raise _lib.HotpathError(f"conv_wino2_wgrad: {_lib.lib().dd_last_error().decode()}")
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    dw = torch.empty((32, 32, 3, 3), device=x.device, dtype=torch.float32)
-    db = torch.empty(32, device=x.device, dtype=torch.float32)
     if finish_stream is None:
-        check(_lib.lib().dd_conv_wino2_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes, C.byref(desc), _stream()), "dd_conv_wino2_wgrad")
-        return dw, db
+        return _wino_wgrad("dd_conv_wino2", x, dy, desc)
     # the two reduce kernels go to `finish_stream` (beside whatever the caller launches next); the caller's stream has to
     # wait for the returned event before it reads dw / db
+    ws, nbytes, dw, db = _wino_wgrad_buffers("dd_conv_wino2", x, dy, desc)
     main = torch.cuda.current_stream()
-    check(_lib.lib().dd_conv_wino2_wgrad_partials(_p(x), _p(dy), _p(ws), nbytes, C.byref(desc), _stream()), "dd_conv_wino2_wgrad_partials")
+    call("dd_conv_wino2_wgrad_partials", x, dy, ws, nbytes, desc)
     finish_stream.wait_event(main.record_event())
     with torch.cuda.stream(finish_stream):
         for t in (ws, dw, db):
             t.record_stream(finish_stream)
-        check(_lib.lib().dd_conv_wino2_wgrad_finish(_p(ws), nbytes, _p(dw), _p(db), C.byref(desc), _stream()), "dd_conv_wino2_wgrad_finish")
+        call("dd_conv_wino2_wgrad_finish", ws, nbytes, dw, db, desc)
         done = finish_stream.record_event()
     return dw, db, done
-
-
-def conv_wino_wgrad(x, dy, desc):
-    _dev(x, "x", (desc.batch, desc.height, desc.width, 32))
-    _dev(dy, "dy", (desc.batch, desc.height, desc.width, 32))
-    nbytes = _lib.lib().dd_conv_wino_wgrad_workspace_bytes(C.byref(desc))
-    if nbytes <= 0:
-        raise _lib.HotpathError(f"conv_wino_wgrad: {_lib.lib().dd_last_error().decode()}")
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    dw = torch.empty((32, 32, 3, 3), device=x.device, dtype=torch.float32)
-    db = torch.empty(32, device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wino_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes, C.byref(desc), _stream()), "dd_conv_wino_wgrad")
-    return dw, db
 
 
 def conv_dgrad_bits(dy, packed_dgrad, bits, desc):
     ho, wo = conv_out(desc.height, desc.stride), conv_out(desc.width, desc.stride)
     _dev(dy, "dy", (desc.batch, ho, wo, 32))
-    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
-        raise _lib.HotpathError("conv_dgrad_bits: relu_bits must be a contiguous int32 [B,H,W] device tensor")
+    _relu_bits(bits, desc, "conv_dgrad_bits")
     dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_dgrad_relu_bits(_p(dy), _p(packed_dgrad), _p(bits), _p(dx), C.byref(desc), _stream()), "dd_conv_dgrad_relu_bits")
+    call("dd_conv_dgrad_relu_bits", dy, packed_dgrad, bits, dx, desc)
     return dx
 
 
@@ -727,7 +685,7 @@ def conv_dgrad(dy, packed_dgrad, relu_src, desc):
     if relu_src is not None:
         _dev(relu_src, "relu_src", (desc.batch, desc.height, desc.width, 32))
     dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_dgrad(_p(dy), _p(packed_dgrad), _p(relu_src), _p(dx), C.byref(desc), _stream()), "dd_conv_dgrad")
+    call("dd_conv_dgrad", dy, packed_dgrad, relu_src, dx, desc)
     return dx
 
 
@@ -735,11 +693,11 @@ def conv_wgrad(x, dy, desc):
     ho, wo = conv_out(desc.height, desc.stride), conv_out(desc.width, desc.stride)
     _dev(x, "x", (desc.batch, desc.height, desc.width, desc.cin_store))
     _dev(dy, "dy", (desc.batch, ho, wo, 32))
-    nbytes = _lib.lib().dd_conv_wgrad_workspace_bytes(C.byref(desc))
+    nbytes = size("dd_conv_wgrad_workspace_bytes", desc)
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
     dw = torch.empty((32, desc.cin_real, 3, 3), device=x.device, dtype=torch.float32)
     db = torch.empty(32, device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(ws), nbytes, C.byref(desc), _stream()), "dd_conv_wgrad")
+    call("dd_conv_wgrad", x, dy, dw, db, ws, nbytes, desc)
     return dw, db
 
 
@@ -747,7 +705,7 @@ def add(a, b):
     _dev(a, "a")
     _dev(b, "b", a.shape)
     out = torch.empty_like(a)
-    check(_lib.lib().dd_add(_p(a), _p(b), _p(out), a.numel(), _stream()), "dd_add")
+    call("dd_add", a, b, out, a.numel())
     return out
 
 
@@ -755,7 +713,7 @@ def relu_bwd(dy, y):
     _dev(dy, "dy", y.shape)
     _dev(y, "y")
     out = torch.empty_like(y)
-    check(_lib.lib().dd_relu_bwd(_p(dy), _p(y), _p(out), y.numel(), _stream()), "dd_relu_bwd")
+    call("dd_relu_bwd", dy, y, out, y.numel())
     return out
 
 
@@ -765,7 +723,7 @@ def relu_sign_bits(x):
     if x.dim() != 4 or x.shape[3] != 32:
         raise _lib.HotpathError(f"relu_sign_bits: expected [B,H,W,32], got {tuple(x.shape)}")
     bits = torch.empty(x.shape[:3], device=x.device, dtype=torch.int32)
-    check(_lib.lib().dd_relu_sign_bits(_p(x), _p(bits), bits.numel(), _stream()), "dd_relu_sign_bits")
+    call("dd_relu_sign_bits", x, bits, bits.numel())
     return bits
 
 
@@ -798,16 +756,59 @@ def relu_bwd_pad_bits(dy, bits_pad):
                                                         tuple(bits_pad.shape) == (b, h + 2, w + 2)):
         raise _lib.HotpathError(f"relu_bwd_pad_bits: dy {tuple(dy.shape)} needs 32 channels (a 4-aligned slice) and contiguous int32 sign words [B,H+2,W+2], got {tuple(bits_pad.shape)}")
     out = torch.empty((b, h + 2, w + 2, 32), device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_relu_bwd_pad_bits(_p(buf), _p(bits_pad), _p(out), b, h, w, buf.shape[3], coff, _stream()), "dd_relu_bwd_pad_bits")
+    call("dd_relu_bwd_pad_bits", buf, bits_pad, out, b, h, w, buf.shape[3], coff)
+    return out
+
+
+# The pool shims of both precisions share their bodies: the feature and its gradient are fp32 here and bf16 in ops_bf16 (pooled and
+# dpooled are fp32 in both).  A body takes the dtype TOGETHER with that dtype's entry points; the public names fix the pair.
+_POOL4_F32 = (torch.float32, {"fwd": "dd_pool4_fwd", "relu_bwd": "dd_pool4_relu_bwd", "idx_elems": "dd_pool4_idx_elems",
+                              "fwd_idx": "dd_pool4_fwd_idx", "idx_relu_bwd": "dd_pool4_idx_relu_bwd"})
+
+
+def _pool4_fwd(kind, feat):
+    dtype, entry = kind
+    b, h, w, c = feat.shape
+    _dev(feat, "feat", dtype=dtype)
+    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
+    call(entry["fwd"], feat, out, b, h, w, c)
+    return out
+
+
+def _pool4_fwd_idx(kind, feat):
+    dtype, entry = kind
+    b, h, w, c = feat.shape
+    _dev(feat, "feat", dtype=dtype)
+    n = size(entry["idx_elems"], b, h, w, c)
+    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
+    idx = torch.empty((n,), device=feat.device, dtype=torch.int16)
+    call(entry["fwd_idx"], feat, out, idx, b, h, w, c)
+    return out, idx
+
+
+def _pool4_idx_relu_bwd(kind, dpooled, idx, shape):
+    dtype, entry = kind
+    b, h, w, c = shape
+    _dev(dpooled, "dpooled", (b, (c * h * w) // 4))
+    if idx.dtype != torch.int16 or not idx.is_cuda or idx.numel() != b * (h * w // 4) * (c // 4):
+        raise _lib.HotpathError(f"{entry['idx_relu_bwd']}: bad routing codes {tuple(idx.shape)} {idx.dtype}")
+    out = torch.empty(shape, device=dpooled.device, dtype=dtype)
+    call(entry["idx_relu_bwd"], dpooled, idx, out, b, h, w, c)
+    return out
+
+
+def _pool4_relu_bwd(kind, dpooled, feat):
+    dtype, entry = kind
+    b, h, w, c = feat.shape
+    _dev(dpooled, "dpooled", (b, (c * h * w) // 4))
+    _dev(feat, "feat", dtype=dtype)
+    out = torch.empty_like(feat)
+    call(entry["relu_bwd"], dpooled, feat, out, b, h, w, c)
     return out
 
 
 def pool4_fwd(feat):
-    b, h, w, c = feat.shape
-    _dev(feat, "feat")
-    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
-    check(_lib.lib().dd_pool4_fwd(_p(feat), _p(out), b, h, w, c, _stream()), "dd_pool4_fwd")
-    return out
+    return _pool4_fwd(_POOL4_F32, feat)
 
 
 def pool4_has_idx(h, w, c):
@@ -817,25 +818,15 @@ def pool4_has_idx(h, w, c):
 
 def pool4_fwd_idx(feat):
     """pooled, codes: max_pool1d(4) + the backward's routing (dd_pool4_fwd_idx)."""
-    b, h, w, c = feat.shape
-    _dev(feat, "feat")
-    n = _lib.lib().dd_pool4_idx_elems(b, h, w, c)
-    if n < 0:
-        raise _lib.HotpathError(_lib.lib().dd_last_error().decode())
-    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
-    idx = torch.empty((n,), device=feat.device, dtype=torch.int16)
-    check(_lib.lib().dd_pool4_fwd_idx(_p(feat), _p(out), _p(idx), b, h, w, c, _stream()), "dd_pool4_fwd_idx")
-    return out, idx
+    return _pool4_fwd_idx(_POOL4_F32, feat)
 
 
 def pool4_idx_relu_bwd(dpooled, idx, shape):
-    b, h, w, c = shape
-    _dev(dpooled, "dpooled", (b, (c * h * w) // 4))
-    if idx.dtype != torch.int16 or not idx.is_cuda or idx.numel() != b * (h * w // 4) * (c // 4):
-        raise _lib.HotpathError(f"pool4_idx_relu_bwd: bad routing codes {tuple(idx.shape)} {idx.dtype}")
-    out = torch.empty(shape, device=dpooled.device, dtype=torch.float32)
-    check(_lib.lib().dd_pool4_idx_relu_bwd(_p(dpooled), _p(idx), _p(out), b, h, w, c, _stream()), "dd_pool4_idx_relu_bwd")
-    return out
+    return _pool4_idx_relu_bwd(_POOL4_F32, dpooled, idx, shape)
+
+
+def pool4_relu_bwd(dpooled, feat):
+    return _pool4_relu_bwd(_POOL4_F32, dpooled, feat)
 
 
 def pool4_relu_bwd_add(dpooled, feat, gfeat):
@@ -845,16 +836,7 @@ def pool4_relu_bwd_add(dpooled, feat, gfeat):
     _dev(feat, "feat")
     _dev(gfeat, "gfeat", feat.shape)
     out = torch.empty_like(feat)
-    check(_lib.lib().dd_pool4_relu_bwd_add(_p(dpooled), _p(feat), _p(gfeat), _p(out), b, h, w, c, _stream()), "dd_pool4_relu_bwd_add")
-    return out
-
-
-def pool4_relu_bwd(dpooled, feat):
-    b, h, w, c = feat.shape
-    _dev(dpooled, "dpooled", (b, (c * h * w) // 4))
-    _dev(feat, "feat")
-    out = torch.empty_like(feat)
-    check(_lib.lib().dd_pool4_relu_bwd(_p(dpooled), _p(feat), _p(out), b, h, w, c, _stream()), "dd_pool4_relu_bwd")
+    call("dd_pool4_relu_bwd_add", dpooled, feat, gfeat, out, b, h, w, c)
     return out
 
 
@@ -1046,7 +1028,7 @@ def encoder_conv_stack(x4, c1, c2, c3, pool, rows_per_task=0):
 
 # ------------------------------------------------------------------------------------------------ skinny GEMMs
 def _linear_ws(m, n, k, device):
-    nbytes = _lib.lib().dd_linear_workspace_bytes(m, n, k)
+    nbytes = size("dd_linear_workspace_bytes", m, n, k)
     return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
 
 
@@ -1069,7 +1051,7 @@ class Linear(torch.autograd.Function):
             _dev(bias, "bias", (n,))
         y = torch.empty((m, n), device=x.device, dtype=torch.float32)
         ws, nbytes = _linear_ws(m, n, k, x.device)
-        check(_lib.lib().dd_linear_fwd(_p(x), _p(weight), _p(bias), _p(y), m, n, k, _p(ws), nbytes, _stream()), "dd_linear_fwd")
+        call("dd_linear_fwd", x, weight, bias, y, m, n, k, ws, nbytes)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y
@@ -1084,7 +1066,7 @@ class Linear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             ws, nbytes = _linear_ws(m, n, k, x.device)
-            check(_lib.lib().dd_linear_dgrad(_p(dy), _p(weight), _p(dx), m, n, k, _p(ws), nbytes, _stream()), "dd_linear_dgrad")
+            call("dd_linear_dgrad", dy, weight, dx, m, n, k, ws, nbytes)
         sync = _ddp.FACTOR_SYNC.get(weight.data_ptr()) if _ddp.FACTOR_SYNC else None
         fused = RANKB.get(weight.data_ptr()) if RANKB else None
         taken = 0
@@ -1100,7 +1082,7 @@ class Linear(torch.autograd.Function):
         elif ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw = torch.empty_like(weight)
             db = torch.empty(n, device=x.device, dtype=torch.float32) if ctx.has_bias else None
-            check(_lib.lib().dd_linear_wgrad(_p(dy), _p(x), _p(dw), _p(db), m, n, k, _stream()), "dd_linear_wgrad")
+            call("dd_linear_wgrad", dy, x, dw, db, m, n, k)
         return dx, dw, db
 
 
@@ -1127,7 +1109,7 @@ def linear_sigmoid_gt(x, weight, bias, tau):
     if bias is not None:
         _dev(bias.detach(), "bias", (n,))
     out = torch.empty((m, n), device=x.device, dtype=torch.uint8)
-    check(_lib.lib().dd_linear_sigmoid_gt(_p(x), _p(weight), _p(bias), float(tau), _p(out), m, n, k, _stream()), "dd_linear_sigmoid_gt")
+    call("dd_linear_sigmoid_gt", x, weight, bias, float(tau), out, m, n, k)
     return out.view(torch.bool)
 
 
@@ -1137,7 +1119,7 @@ def column_sum(dy):
     m, n = dy.shape
     _dev(dy, "dy")
     db = torch.empty(n, device=dy.device, dtype=torch.float32)
-    check(_lib.lib().dd_column_sum(_p(dy), _p(db), m, n, _stream()), "dd_column_sum")
+    call("dd_column_sum", dy, db, m, n)
     return db
 
 
@@ -1149,7 +1131,7 @@ def linear_wgrad(dy, x, dw):
     _dev(dy, "dy")
     _dev(x, "x", (m, k))
     _dev(dw, "dw", (n, k))
-    check(_lib.lib().dd_linear_wgrad(_p(dy), _p(x), _p(dw), None, m, n, k, _stream()), "dd_linear_wgrad")
+    call("dd_linear_wgrad", dy, x, dw, None, m, n, k)
 
 
 # ------------------------------------------------------------------------------------------------ dense block tail
@@ -1165,9 +1147,8 @@ class BnReluDrop(torch.autograd.Function):
         y = torch.empty_like(x)
         save_mean = torch.empty(feat, device=x.device, dtype=torch.float32)
         save_inv = torch.empty(feat, device=x.device, dtype=torch.float32)
-        check(_lib.lib().dd_bn_relu_drop_fwd(_p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(keep),
-                                             _p(y), _p(save_mean), _p(save_inv), rows, feat, eps, momentum, scale,
-                                             int(training), _p(num_batches_tracked), _stream()), "dd_bn_relu_drop_fwd")
+        call("dd_bn_relu_drop_fwd", x, gamma, beta, running_mean, running_var, keep, y, save_mean, save_inv, rows, feat, eps, momentum, scale,
+             int(training), num_batches_tracked)
         if TRACE is not None:
             TRACE.setdefault("dense", []).append(y)
         ctx.save_for_backward(x, y, gamma, keep, save_mean, save_inv, running_mean, running_var)
@@ -1183,9 +1164,8 @@ class BnReluDrop(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma = torch.empty_like(gamma)
         dbeta = torch.empty_like(gamma)
-        check(_lib.lib().dd_bn_relu_drop_bwd(_p(dy), _p(x), _p(y), _p(gamma), _p(keep), _p(save_mean), _p(save_inv),
-                                             _p(running_mean), _p(running_var), _p(dx), _p(dgamma), _p(dbeta), rows, feat,
-                                             eps, scale, int(training), _stream()), "dd_bn_relu_drop_bwd")
+        call("dd_bn_relu_drop_bwd", dy, x, y, gamma, keep, save_mean, save_inv, running_mean, running_var, dx, dgamma, dbeta, rows, feat, eps, scale,
+             int(training))
         return dx, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
@@ -1222,11 +1202,9 @@ class EncoderTail(torch.autograd.Function):
         mean1, inv1, mean2, inv2 = new(h1), new(h1), new(h2), new(h2)
         mom = lambda bn: 0.1 if bn.momentum is None else bn.momentum
         nbt = lambda bn: bn.num_batches_tracked if (training and bn.num_batches_tracked is not None) else None
-        check(_lib.lib().dd_mlp_tail_fwd(_p(lin1), _p(gamma1), _p(beta1), _p(bn1.running_mean), _p(bn1.running_var), _p(nbt(bn1)),
-                                         _p(keep1), _p(w2), _p(bias2), _p(gamma2), _p(beta2), _p(bn2.running_mean),
-                                         _p(bn2.running_var), _p(nbt(bn2)), _p(keep2), _p(wz), _p(bz), _p(y1), _p(lin2), _p(y2),
-                                         _p(z), _p(mean1), _p(inv1), _p(mean2), _p(inv2), m, h1, h2, l, bn1.eps, bn2.eps,
-                                         mom(bn1), mom(bn2), scale1, scale2, int(training), _stream()), "dd_mlp_tail_fwd")
+        call("dd_mlp_tail_fwd", lin1, gamma1, beta1, bn1.running_mean, bn1.running_var, nbt(bn1), keep1, w2, bias2, gamma2, beta2, bn2.running_mean,
+             bn2.running_var, nbt(bn2), keep2, wz, bz, y1, lin2, y2, z, mean1, inv1, mean2, inv2, m, h1, h2, l, bn1.eps, bn2.eps, mom(bn1), mom(bn2),
+             scale1, scale2, int(training))
         if TRACE is not None:
             TRACE.setdefault("dense", []).extend([y1, y2])
         ctx.save_for_backward(lin1, y1, lin2, y2, gamma1, gamma2, keep1, keep2, w2, wz, mean1, inv1, mean2, inv2,
@@ -1246,10 +1224,8 @@ class EncoderTail(torch.autograd.Function):
         dw2, dwz = torch.empty_like(w2), torch.empty_like(wz)
         dbias2 = torch.empty(h2, device=dz.device, dtype=torch.float32)
         dbz = torch.empty(l, device=dz.device, dtype=torch.float32)
-        check(_lib.lib().dd_mlp_tail_bwd(_p(dz), _p(lin1), _p(y1), _p(lin2), _p(y2), _p(gamma1), _p(gamma2), _p(keep1), _p(keep2),
-                                         _p(w2), _p(wz), _p(mean1), _p(inv1), _p(mean2), _p(inv2), _p(rm1), _p(rv1), _p(rm2), _p(rv2),
-                                         _p(dlin1), _p(dg1), _p(db1), _p(dw2), _p(dbias2), _p(dg2), _p(db2), _p(dwz), _p(dbz),
-                                         m, h1, h2, l, eps1, eps2, scale1, scale2, int(training), _stream()), "dd_mlp_tail_bwd")
+        call("dd_mlp_tail_bwd", dz, lin1, y1, lin2, y2, gamma1, gamma2, keep1, keep2, w2, wz, mean1, inv1, mean2, inv2, rm1, rv1, rm2, rv2, dlin1,
+             dg1, db1, dw2, dbias2, dg2, db2, dwz, dbz, m, h1, h2, l, eps1, eps2, scale1, scale2, int(training))
         return dlin1, dg1, db1, dw2, dbias2, dg2, db2, dwz, dbz, None, None, None, None, None, None
 
 
@@ -1276,7 +1252,7 @@ def _stack_masks(target, shape):
 
 
 def _loss_ws(n, device):
-    return torch.empty(_lib.lib().dd_loss_workspace_bytes(n), device=device, dtype=torch.uint8)
+    return torch.empty(size("dd_loss_workspace_bytes", n), device=device, dtype=torch.uint8)
 
 
 def _scaled_loss_grad(ctx, dz, g):
@@ -1293,7 +1269,7 @@ def _scaled_loss_grad(ctx, dz, g):
         return dz * (g / prev)
     if (g.numel() == 1 and g.is_cuda and g.dtype == torch.float32 and dz.is_contiguous() and dz.dtype == torch.float32
             and dz.data_ptr() % 16 == 0 and not torch.is_grad_enabled()):
-        check(_lib.lib().dd_scale_by_device_scalar(_p(dz), _p(g), dz.numel(), _stream()), "dd_scale_by_device_scalar")
+        call("dd_scale_by_device_scalar", dz, g, dz.numel())
         ctx.applied_scale = g.detach()
         return dz
     return dz * g
@@ -1314,12 +1290,10 @@ class BceWithLogits(torch.autograd.Function):
         if target.dtype in (torch.bool, torch.uint8):      # the dataset's bool road masks, read as bytes
             if not target.is_cuda or not target.is_contiguous() or target.shape != logits.shape:
                 raise _lib.HotpathError(f"bce: target must be a contiguous GPU tensor of shape {tuple(logits.shape)}")
-            check(_lib.lib().dd_bce_logits_u8(_p(logits), _p(target), _p(loss), _p(dz), None, n, 1.0,
-                                              _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits_u8")
+            call("dd_bce_logits_u8", logits, target, loss, dz, None, n, 1.0, _loss_ws(n, logits.device))
         else:
             _dev(target, "target", logits.shape)
-            check(_lib.lib().dd_bce_logits(_p(logits), _p(target), _p(loss), _p(dz), None, n, 1.0,
-                                           _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits")
+            call("dd_bce_logits", logits, target, loss, dz, None, n, 1.0, _loss_ws(n, logits.device))
         ctx.save_for_backward(dz)
         return loss
 
@@ -1351,8 +1325,7 @@ class BceWithLogitsProbs(torch.autograd.Function):
                 target = _stack_masks(target, logits.shape)
         if isinstance(target, (tuple, list)):
             table = (C.c_void_p * b)(*[t.data_ptr() for t in target])
-            check(_lib.lib().dd_bce_logits_u8_ptrs(_p(logits), table, b, per, _p(loss), _p(dz), _p(probs), 1.0,
-                                                   _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits_u8_ptrs")
+            call("dd_bce_logits_u8_ptrs", logits, table, b, per, loss, dz, probs, 1.0, _loss_ws(n, logits.device))
             ctx.save_for_backward(dz)
             ctx.mark_non_differentiable(probs)
             ctx.set_materialize_grads(False)
@@ -1360,12 +1333,10 @@ class BceWithLogitsProbs(torch.autograd.Function):
         if not target.is_cuda or not target.is_contiguous() or target.shape != logits.shape:
             raise _lib.HotpathError(f"bce: target must be a contiguous GPU tensor of shape {tuple(logits.shape)}")
         if target.dtype in (torch.bool, torch.uint8):
-            check(_lib.lib().dd_bce_logits_u8(_p(logits), _p(target), _p(loss), _p(dz), _p(probs), n, 1.0,
-                                              _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits_u8")
+            call("dd_bce_logits_u8", logits, target, loss, dz, probs, n, 1.0, _loss_ws(n, logits.device))
         else:
             _dev(target, "target", logits.shape)
-            check(_lib.lib().dd_bce_logits(_p(logits), _p(target), _p(loss), _p(dz), _p(probs), n, 1.0,
-                                           _p(_loss_ws(n, logits.device)), _stream()), "dd_bce_logits")
+            call("dd_bce_logits", logits, target, loss, dz, probs, n, 1.0, _loss_ws(n, logits.device))
         ctx.save_for_backward(dz)
         ctx.mark_non_differentiable(probs)
         ctx.set_materialize_grads(False)      # no 82 MB of zeros for the probabilities' (unused) gradient slot
@@ -1389,7 +1360,7 @@ class MseLoss(torch.autograd.Function):
         n = pred.numel()
         loss = torch.empty((), device=pred.device, dtype=torch.float32)
         da = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        check(_lib.lib().dd_mse(_p(pred), _p(target), _p(loss), _p(da), n, 1.0, _p(_loss_ws(n, pred.device)), _stream()), "dd_mse")
+        call("dd_mse", pred, target, loss, da, n, 1.0, _loss_ws(n, pred.device))
         ctx.save_for_backward(da)
         return loss
 
@@ -1409,8 +1380,7 @@ class BceProbs(torch.autograd.Function):
         n = probs.numel()
         loss = torch.empty((), device=probs.device, dtype=torch.float32)
         dp = torch.empty_like(probs) if ctx.needs_input_grad[0] else None
-        check(_lib.lib().dd_bce_probs(_p(probs), _p(target), _p(loss), _p(dp), n, 1.0, _p(_loss_ws(n, probs.device)), _stream()),
-              "dd_bce_probs")
+        call("dd_bce_probs", probs, target, loss, dp, n, 1.0, _loss_ws(n, probs.device))
         ctx.save_for_backward(dp)
         return loss
 
@@ -1426,7 +1396,7 @@ def sigmoid(z):
     if z.numel() % 4:
         raise _lib.HotpathError("sigmoid: element count must be a multiple of 4")
     p = torch.empty_like(z)
-    check(_lib.lib().dd_sigmoid(_p(z), _p(p), z.numel(), _stream()), "dd_sigmoid")
+    call("dd_sigmoid", z, p, z.numel())
     return p
 
 
@@ -1446,7 +1416,7 @@ class Sigmoid(torch.autograd.Function):
         dp = dp.contiguous()
         _dev(dp, "dp", p.shape)
         dz = torch.empty_like(p)
-        check(_lib.lib().dd_sigmoid_bwd(_p(dp), _p(p), _p(dz), p.numel(), _stream()), "dd_sigmoid_bwd")
+        call("dd_sigmoid_bwd", dp, p, dz, p.numel())
         return dz
 
 
@@ -1455,8 +1425,7 @@ def sigmoid_and_loss(logits, target):
     n = logits.numel()
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     probs = torch.empty_like(logits)
-    check(_lib.lib().dd_bce_logits(_p(logits), _p(target), _p(loss), None, _p(probs), n, 1.0, _p(_loss_ws(n, logits.device)),
-                                   _stream()), "dd_bce_logits")
+    call("dd_bce_logits", logits, target, loss, None, probs, n, 1.0, _loss_ws(n, logits.device))
     return loss, probs
 
 
@@ -1488,11 +1457,9 @@ def adam_step_multi(tensors, lr, beta1, beta2, eps, step, grad_scale=1.0):
     table = _adam_table(tensors)
     scale, scale_dev = _scale_arg(grad_scale)
     if scale_dev is not None:
-        check(_lib.lib().dd_adam_step_multi_dev(table, len(tensors), lr, beta1, beta2, eps, int(step), _p(scale_dev), _stream()),
-              "dd_adam_step_multi_dev")
+        call("dd_adam_step_multi_dev", table, len(tensors), lr, beta1, beta2, eps, int(step), scale_dev)
         return
-    check(_lib.lib().dd_adam_step_multi(table, len(tensors), lr, beta1, beta2, eps, int(step), scale, _stream()),
-          "dd_adam_step_multi")
+    call("dd_adam_step_multi", table, len(tensors), lr, beta1, beta2, eps, int(step), scale)
 
 
 def adam_step_rankb(p, m, v, dy, x, bias, bias_m, bias_v, lr, beta1, beta2, eps, step, grad_scale=1.0):
@@ -1510,11 +1477,9 @@ def adam_step_rankb(p, m, v, dy, x, bias, bias_m, bias_v, lr, beta1, beta2, eps,
             _dev(t, name, (n,))
     scale, scale_dev = _scale_arg(grad_scale)
     if scale_dev is not None:
-        check(_lib.lib().dd_adam_step_rankb_dev(_p(p), _p(m), _p(v), _p(dy), _p(x), rows, n, k, _p(bias), _p(bias_m), _p(bias_v),
-                                                lr, beta1, beta2, eps, int(step), _p(scale_dev), _stream()), "dd_adam_step_rankb_dev")
+        call("dd_adam_step_rankb_dev", p, m, v, dy, x, rows, n, k, bias, bias_m, bias_v, lr, beta1, beta2, eps, int(step), scale_dev)
         return
-    check(_lib.lib().dd_adam_step_rankb(_p(p), _p(m), _p(v), _p(dy), _p(x), rows, n, k, _p(bias), _p(bias_m), _p(bias_v),
-                                        lr, beta1, beta2, eps, int(step), scale, _stream()), "dd_adam_step_rankb")
+    call("dd_adam_step_rankb", p, m, v, dy, x, rows, n, k, bias, bias_m, bias_v, lr, beta1, beta2, eps, int(step), scale)
 
 
 def adam_step_flat(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
@@ -1522,11 +1487,9 @@ def adam_step_flat(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
         _dev(t, name, p.shape)
     scale, scale_dev = _scale_arg(grad_scale)
     if scale_dev is not None:
-        check(_lib.lib().dd_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, int(step), _p(scale_dev),
-                                          _stream()), "dd_adam_step_dev")
+        call("dd_adam_step_dev", p, g, m, v, p.numel(), lr, beta1, beta2, eps, int(step), scale_dev)
         return
-    check(_lib.lib().dd_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, int(step), scale,
-                                  _stream()), "dd_adam_step")
+    call("dd_adam_step", p, g, m, v, p.numel(), lr, beta1, beta2, eps, int(step), scale)
 
 
 # ------------------------------------------------------------------------------------------------ gradient norm (clipping)
@@ -1551,11 +1514,9 @@ def _slot(out):
 def sqnorm(g, out):
     """``out`` (one fp64 device element) = sum of squares of the flat fp32 device tensor ``g``, accumulated in fp64 (dd_sqnorm)."""
     _dev(g, "g")
-    nbytes = _lib.lib().dd_sqnorm_workspace_bytes(g.numel())
-    if nbytes < 0:
-        raise _lib.HotpathError(f"dd_sqnorm_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_sqnorm_workspace_bytes", g.numel())
     ws = _norm_ws(nbytes, g.device)
-    check(_lib.lib().dd_sqnorm(_p(g), g.numel(), _p(_slot(out)), _p(ws), ws.numel(), _stream()), "dd_sqnorm")
+    call("dd_sqnorm", g, g.numel(), _slot(out), ws, ws.numel())
     return out
 
 
@@ -1567,11 +1528,9 @@ def sqnorm_multi(grads, out):
     for i, g in enumerate(grads):
         _dev(g, "g")
         table[i] = _lib.AdamTensor(None, _p(g), None, None, g.numel())
-    nbytes = _lib.lib().dd_sqnorm_multi_workspace_bytes(table, len(grads))
-    if nbytes < 0:
-        raise _lib.HotpathError(f"dd_sqnorm_multi_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_sqnorm_multi_workspace_bytes", table, len(grads))
     ws = _norm_ws(nbytes, grads[0].device)
-    check(_lib.lib().dd_sqnorm_multi(table, len(grads), _p(_slot(out)), _p(ws), ws.numel(), _stream()), "dd_sqnorm_multi")
+    call("dd_sqnorm_multi", table, len(grads), _slot(out), ws, ws.numel())
     return out
 
 
@@ -1582,12 +1541,9 @@ def rankb_sqnorm(dy, x, with_bias, out):
     k = x.shape[1]
     _dev(dy, "dy")
     _dev(x, "x", (rows, k))
-    nbytes = _lib.lib().dd_rankb_sqnorm_workspace_bytes(rows, n, k)
-    if nbytes < 0:
-        raise _lib.HotpathError(f"dd_rankb_sqnorm_workspace_bytes: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_rankb_sqnorm_workspace_bytes", rows, n, k)
     ws = _norm_ws(nbytes, dy.device)
-    check(_lib.lib().dd_rankb_sqnorm(_p(dy), _p(x), rows, n, k, 1 if with_bias else 0, _p(_slot(out)), _p(ws), ws.numel(), _stream()),
-          "dd_rankb_sqnorm")
+    call("dd_rankb_sqnorm", dy, x, rows, n, k, 1 if with_bias else 0, _slot(out), ws, ws.numel())
     return out
 
 
@@ -1596,5 +1552,5 @@ def clip_scale(sq, max_norm, grad_scale, out3):
     if not (isinstance(sq, torch.Tensor) and sq.is_cuda and sq.dtype == torch.float64 and sq.is_contiguous() and sq.numel() > 0):
         raise _lib.HotpathError("sq: expected a contiguous fp64 device tensor")
     _dev(out3, "out3", (3,))
-    check(_lib.lib().dd_clip_scale(_p(sq), sq.numel(), float(max_norm), float(grad_scale), _p(out3), _stream()), "dd_clip_scale")
+    call("dd_clip_scale", sq, sq.numel(), float(max_norm), float(grad_scale), out3)
     return out3

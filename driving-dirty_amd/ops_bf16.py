@@ -8,17 +8,12 @@ import ctypes as C
 import torch
 
 from . import _lib, ops
-from ._lib import check
-from .ops import PACK_DGRAD_S1, PACK_DGRAD_S2, PACK_FWD, _p, _stream, conv_desc, conv_out
+from ._lib import call, size
+from .ops import PACK_DGRAD_S1, PACK_DGRAD_S2, PACK_FWD, conv_desc, conv_out
 
 
 def _bf(t, name, shape=None):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()):
-        raise _lib.HotpathError(f"{name}: expected a contiguous bf16 device tensor, got {getattr(t, 'dtype', type(t))} "
-                                f"on {getattr(t, 'device', '?')}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise _lib.HotpathError(f"{name}: shape {tuple(t.shape)} != expected {tuple(shape)}")
-    return t
+    return _lib.dev(t, name, shape, torch.bfloat16)
 
 
 def stitch6_bf16(views):
@@ -28,7 +23,7 @@ def stitch6_bf16(views):
         raise _lib.HotpathError(f"stitch6_bf16: expected [B,6,3,H,W], got {tuple(views.shape)}")
     ops._dev(views, "views")
     out = torch.empty((b, h, 6 * w, 4), device=views.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_stitch6_bf16(_p(views), _p(out), b, h, w, _stream()), "dd_stitch6_bf16")
+    call("dd_stitch6_bf16", views, out, b, h, w)
     return out
 
 
@@ -42,7 +37,7 @@ def stitch6_bf16_samples(samples):
         ops._dev(t, "sample", (6, 3, h, w))
     table = (C.c_void_p * b)(*[t.data_ptr() for t in samples])
     out = torch.empty((b, h, 6 * w, 4), device=samples[0].device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_stitch6_bf16_ptrs(table, _p(out), b, h, w, _stream()), "dd_stitch6_bf16_ptrs")
+    call("dd_stitch6_bf16_ptrs", table, out, b, h, w)
     return out
 
 
@@ -51,7 +46,7 @@ def stitch6_bf16_u8(sample):
     the gather -- the values ``stitch6_bf16(frames.permute(..).float() / 255)`` gives."""
     table, b, h, w, dev, _keep = ops.u8_table(sample, "stitch6_bf16_u8")
     out = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.bfloat16)
-    check(_lib.lib().dd_stitch6_bf16_u8_ptrs(table, _p(out), b, h, w, _stream()), "dd_stitch6_bf16_u8_ptrs")
+    call("dd_stitch6_bf16_u8_ptrs", table, out, b, h, w)
     return out
 
 
@@ -60,7 +55,7 @@ def to_bf16(t):
     if t.numel() % 4:
         raise _lib.HotpathError("to_bf16: element count must be a multiple of 4")
     out = torch.empty(t.shape, device=t.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_f32_to_bf16(_p(t), _p(out), t.numel(), _stream()), "dd_f32_to_bf16")
+    call("dd_f32_to_bf16", t, out, t.numel())
     return out
 
 
@@ -69,17 +64,15 @@ def to_f32(t):
     if t.numel() % 4:
         raise _lib.HotpathError("to_f32: element count must be a multiple of 4")
     out = torch.empty(t.shape, device=t.device, dtype=torch.float32)
-    check(_lib.lib().dd_bf16_to_f32(_p(t), _p(out), t.numel(), _stream()), "dd_bf16_to_f32")
+    call("dd_bf16_to_f32", t, out, t.numel())
     return out
 
 
 def conv_pack(weight, desc, kind):
     ops._dev(weight, "weight", (32, desc.cin_real, 3, 3))
-    n = _lib.lib().dd_conv_bf16_packed_elems(C.byref(desc))
-    if n <= 0:
-        raise _lib.HotpathError(f"conv_bf16_pack: {_lib.lib().dd_last_error().decode()}")
+    n = size("dd_conv_bf16_packed_elems", desc)
     packed = torch.empty(n, device=weight.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_conv_bf16_pack(_p(weight), C.byref(desc), kind, _p(packed), _stream()), "dd_conv_bf16_pack")
+    call("dd_conv_bf16_pack", weight, desc, kind, packed)
     return packed
 
 
@@ -91,7 +84,7 @@ def conv_fwd(x, packed, bias, desc, want_bits=True):
     ops._dev(bias, "bias", (32,))
     y = torch.empty((desc.batch, ho, wo, 32), device=x.device, dtype=torch.bfloat16)
     bits = torch.empty((desc.batch, ho, wo), device=x.device, dtype=torch.int32) if want_bits else None
-    check(_lib.lib().dd_conv_bf16_fwd(_p(x), _p(packed), _p(bias), _p(y), _p(bits), C.byref(desc), _stream()), "dd_conv_bf16_fwd")
+    call("dd_conv_bf16_fwd", x, packed, bias, y, bits, desc)
     return y, bits
 
 
@@ -99,10 +92,9 @@ def conv_dgrad(dy, packed_dgrad, bits, desc):
     ho, wo = conv_out(desc.height, desc.stride), conv_out(desc.width, desc.stride)
     _bf(dy, "dy", (desc.batch, ho, wo, 32))
     _bf(packed_dgrad, "packed")
-    if not (bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and tuple(bits.shape) == (desc.batch, desc.height, desc.width)):
-        raise _lib.HotpathError("conv_bf16_dgrad: relu_bits must be a contiguous int32 [B,H,W] device tensor")
+    ops._relu_bits(bits, desc, "conv_bf16_dgrad")
     dx = torch.empty((desc.batch, desc.height, desc.width, 32), device=dy.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_conv_bf16_dgrad(_p(dy), _p(packed_dgrad), _p(bits), _p(dx), C.byref(desc), _stream()), "dd_conv_bf16_dgrad")
+    call("dd_conv_bf16_dgrad", dy, packed_dgrad, bits, dx, desc)
     return dx
 
 
@@ -110,31 +102,24 @@ def conv_wgrad(x, dy, desc):
     ho, wo = conv_out(desc.height, desc.stride), conv_out(desc.width, desc.stride)
     _bf(x, "x", (desc.batch, desc.height, desc.width, desc.cin_store))
     _bf(dy, "dy", (desc.batch, ho, wo, 32))
-    nbytes = _lib.lib().dd_conv_bf16_wgrad_workspace_bytes(C.byref(desc))
-    if nbytes <= 0:
-        raise _lib.HotpathError(f"conv_bf16_wgrad: {_lib.lib().dd_last_error().decode()}")
+    nbytes = size("dd_conv_bf16_wgrad_workspace_bytes", desc)
     ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
     dw = torch.empty((32, desc.cin_real, 3, 3), device=x.device, dtype=torch.float32)
     db = torch.empty(32, device=x.device, dtype=torch.float32)
-    check(_lib.lib().dd_conv_bf16_wgrad(_p(x), _p(dy), _p(dw), _p(db), C.byref(desc), _p(ws), nbytes, _stream()), "dd_conv_bf16_wgrad")
+    call("dd_conv_bf16_wgrad", x, dy, dw, db, desc, ws, nbytes)
     return dw, db
 
 
+_POOL4_BF16 = (torch.bfloat16, {"fwd": "dd_pool4_bf16_fwd", "relu_bwd": "dd_pool4_relu_bf16_bwd", "idx_elems": "dd_pool4_bf16_idx_elems",
+                                 "fwd_idx": "dd_pool4_bf16_fwd_idx", "idx_relu_bwd": "dd_pool4_idx_relu_bf16_bwd"})      # bodies: ops._pool4_*
+
+
 def pool4_fwd(feat):
-    b, h, w, c = feat.shape
-    _bf(feat, "feat")
-    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
-    check(_lib.lib().dd_pool4_bf16_fwd(_p(feat), _p(out), b, h, w, c, _stream()), "dd_pool4_bf16_fwd")
-    return out
+    return ops._pool4_fwd(_POOL4_BF16, feat)
 
 
 def pool4_relu_bwd(dpooled, feat):
-    b, h, w, c = feat.shape
-    ops._dev(dpooled, "dpooled", (b, (c * h * w) // 4))
-    _bf(feat, "feat")
-    out = torch.empty_like(feat)
-    check(_lib.lib().dd_pool4_relu_bf16_bwd(_p(dpooled), _p(feat), _p(out), b, h, w, c, _stream()), "dd_pool4_relu_bf16_bwd")
-    return out
+    return ops._pool4_relu_bwd(_POOL4_BF16, dpooled, feat)
 
 
 def pool4_has_idx(h, w, c):
@@ -144,25 +129,11 @@ def pool4_has_idx(h, w, c):
 
 def pool4_fwd_idx(feat):
     """pooled, codes: max_pool1d(4) + the backward's routing (dd_pool4_bf16_fwd_idx)."""
-    b, h, w, c = feat.shape
-    _bf(feat, "feat")
-    n = _lib.lib().dd_pool4_bf16_idx_elems(b, h, w, c)
-    if n < 0:
-        raise _lib.HotpathError(_lib.lib().dd_last_error().decode())
-    out = torch.empty((b, (c * h * w) // 4), device=feat.device, dtype=torch.float32)
-    idx = torch.empty(n, device=feat.device, dtype=torch.int16)
-    check(_lib.lib().dd_pool4_bf16_fwd_idx(_p(feat), _p(out), _p(idx), b, h, w, c, _stream()), "dd_pool4_bf16_fwd_idx")
-    return out, idx
+    return ops._pool4_fwd_idx(_POOL4_BF16, feat)
 
 
 def pool4_idx_relu_bwd(dpooled, idx, shape):
-    b, h, w, c = shape
-    ops._dev(dpooled, "dpooled", (b, (c * h * w) // 4))
-    if idx.dtype != torch.int16 or idx.numel() != b * (h * w // 4) * (c // 4) or not idx.is_cuda:
-        raise _lib.HotpathError(f"pool4_idx_relu_bwd (bf16): bad routing codes {tuple(idx.shape)} {idx.dtype}")
-    out = torch.empty(shape, device=dpooled.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_pool4_idx_relu_bf16_bwd(_p(dpooled), _p(idx), _p(out), b, h, w, c, _stream()), "dd_pool4_idx_relu_bf16_bwd")
-    return out
+    return ops._pool4_idx_relu_bwd(_POOL4_BF16, dpooled, idx, shape)
 
 
 class EncoderConvStackBf16(torch.autograd.Function):
@@ -251,7 +222,7 @@ def stitch6_bf16_masked(sample, mask_slot=-1, want_target=False):
     if ops.is_u8_frames(sample):
         table, b, h, w, dev, _keep = ops.u8_table(sample, "stitch6_bf16_u8_masked")
         out, tgt = _masked_out(b, h, w, dev, want_target)
-        check(_lib.lib().dd_stitch6_bf16_u8_ptrs_masked(table, _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_u8_ptrs_masked")
+        call("dd_stitch6_bf16_u8_ptrs_masked", table, out, tgt, b, h, w, slot)
     elif isinstance(sample, (tuple, list)):
         samples = [t.contiguous() for t in sample]
         if not samples:
@@ -264,7 +235,7 @@ def stitch6_bf16_masked(sample, mask_slot=-1, want_target=False):
         b = len(samples)
         table = (C.c_void_p * b)(*[t.data_ptr() for t in samples])
         out, tgt = _masked_out(b, h, w, samples[0].device, want_target)
-        check(_lib.lib().dd_stitch6_bf16_ptrs_masked(table, _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_ptrs_masked")
+        call("dd_stitch6_bf16_ptrs_masked", table, out, tgt, b, h, w, slot)
     else:
         if sample.dim() != 5 or sample.shape[1] != 6 or sample.shape[2] != 3:
             raise _lib.HotpathError(f"stitch6_bf16_masked: expected [B,6,3,H,W], got {tuple(sample.shape)}")
@@ -272,14 +243,12 @@ def stitch6_bf16_masked(sample, mask_slot=-1, want_target=False):
         ops._dev(views, "views")
         b, _, _, h, w = views.shape
         out, tgt = _masked_out(b, h, w, views.device, want_target)
-        check(_lib.lib().dd_stitch6_bf16_masked(_p(views), _p(out), _p(tgt), b, h, w, slot, _stream()), "dd_stitch6_bf16_masked")
+        call("dd_stitch6_bf16_masked", views, out, tgt, b, h, w, slot)
     return (out, tgt) if want_target else out
 
 
 def _dec_ws(layer, b, dh, dw, dev):
-    n = _lib.lib().dd_dec_bf16_wgrad_workspace_bytes(layer, b, dh, dw)
-    if n <= 0:
-        raise _lib.HotpathError(f"dec_bf16 wgrad: {_lib.lib().dd_last_error().decode()}")
+    n = size("dd_dec_bf16_wgrad_workspace_bytes", layer, b, dh, dw)
     return torch.empty(n, device=dev, dtype=torch.uint8), n
 
 
@@ -295,7 +264,7 @@ def dec_split64(h, dh, dw):
     ops._dev(h, "h", (b, 64 * dh * dw))
     lo = torch.empty((b, dh, dw, 32), device=h.device, dtype=torch.bfloat16)
     hi = torch.empty_like(lo)
-    check(_lib.lib().dd_dec_bf16_split64(_p(h), _p(lo), _p(hi), b, dh, dw, _stream()), "dd_dec_bf16_split64")
+    call("dd_dec_bf16_split64", h, lo, hi, b, dh, dw)
     return lo, hi
 
 
@@ -305,7 +274,7 @@ def dec_merge64(lo, hi):
     _bf(lo, "lo", (b, dh, dw, 32))
     _bf(hi, "hi", (b, dh, dw, 32))
     gh = torch.empty((b, 64 * dh * dw), device=lo.device, dtype=torch.float32)
-    check(_lib.lib().dd_dec_bf16_merge64(_p(lo), _p(hi), _p(gh), b, dh, dw, _stream()), "dd_dec_bf16_merge64")
+    call("dd_dec_bf16_merge64", lo, hi, gh, b, dh, dw)
     return gh
 
 
@@ -318,8 +287,7 @@ def dec_dc1_fwd(x_lo, x_hi, w1, b1):
     ops._dev(b1, "b1", (32,))
     a1 = torch.empty((b, dh, dw, 32), device=x_lo.device, dtype=torch.bfloat16)
     bits = torch.empty((b, dh, dw), device=x_lo.device, dtype=torch.int32)
-    check(_lib.lib().dd_dec_bf16_dc1_fwd(_p(x_lo), _p(x_hi), _p(w1), _p(b1), _p(a1), _p(bits), b, dh, dw, _stream()),
-          "dd_dec_bf16_dc1_fwd")
+    call("dd_dec_bf16_dc1_fwd", x_lo, x_hi, w1, b1, a1, bits, b, dh, dw)
     return a1, bits
 
 
@@ -353,8 +321,7 @@ def dec_dc34_fwd(a2, w3, b3, w4, b4):
     ops._dev(b4, "b4", (3,))
     a3 = torch.empty((b, 2 * dh, 2 * dw, 32), device=a2.device, dtype=torch.bfloat16)
     y = torch.empty((b, 3, 2 * dh, 2 * dw), device=a2.device, dtype=torch.float32)
-    check(_lib.lib().dd_dec_bf16_dc34_fwd(_p(a2), _p(w3), _p(b3), _p(w4), _p(b4), _p(a3), _p(y), b, dh, dw, _stream()),
-          "dd_dec_bf16_dc34_fwd")
+    call("dd_dec_bf16_dc34_fwd", a2, w3, b3, w4, b4, a3, y, b, dh, dw)
     return a3, y
 
 
@@ -370,8 +337,7 @@ def dec_dc4_bwd(gy, a3, w4):
     g3 = torch.empty_like(a3)
     dwt = torch.empty((32, 3, 1, 1), device=a3.device, dtype=torch.float32)
     db = torch.empty(3, device=a3.device, dtype=torch.float32)
-    check(_lib.lib().dd_dec_bf16_dc4_bwd(_p(gy), _p(a3), _p(w4), _p(g3), _p(dwt), _p(db), b, ho // 2, wo // 2, _p(ws), n, _stream()),
-          "dd_dec_bf16_dc4_bwd")
+    call("dd_dec_bf16_dc4_bwd", gy, a3, w4, g3, dwt, db, b, ho // 2, wo // 2, ws, n)
     return g3, dwt, db
 
 
@@ -384,7 +350,7 @@ def dec_dc3_dgrad(g3, w3, bits2):
     ops._dev(w3, "w3", (32, 32, 2, 2))
     _bits(bits2, (b, dh, dw), "dec_dc3_dgrad")
     g2 = torch.empty((b, dh, dw, 32), device=g3.device, dtype=torch.bfloat16)
-    check(_lib.lib().dd_dec_bf16_dc3_dgrad(_p(g3), _p(w3), _p(bits2), _p(g2), b, dh, dw, _stream()), "dd_dec_bf16_dc3_dgrad")
+    call("dd_dec_bf16_dc3_dgrad", g3, w3, bits2, g2, b, dh, dw)
     return g2
 
 
@@ -395,7 +361,7 @@ def dec_dc3_wgrad(a2, g3):
     ws, n = _dec_ws(3, b, dh, dw, a2.device)
     dwt = torch.empty((32, 32, 2, 2), device=a2.device, dtype=torch.float32)
     db = torch.empty(32, device=a2.device, dtype=torch.float32)
-    check(_lib.lib().dd_dec_bf16_dc3_wgrad(_p(a2), _p(g3), _p(dwt), _p(db), b, dh, dw, _p(ws), n, _stream()), "dd_dec_bf16_dc3_wgrad")
+    call("dd_dec_bf16_dc3_wgrad", a2, g3, dwt, db, b, dh, dw, ws, n)
     return dwt, db
 
 

@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from . import lightning, ops
+from . import _lib, lightning, ops
 
 
 class HipAdam(torch.optim.Optimizer):
@@ -178,11 +178,11 @@ class HipAdam(torch.optim.Optimizer):
             ev = torch.cuda.current_stream().record_event()
             with torch.no_grad(), torch.cuda.stream(self._side):
                 self._side.wait_event(ev)
-                ops.check(ops._lib.lib().dd_set_adam_spare_cus(self.EARLY_SPARE_CUS), "dd_set_adam_spare_cus")
+                _lib.call("dd_set_adam_spare_cus", self.EARLY_SPARE_CUS)
                 try:
                     self._take_rankb(p, self._group_of(p), self._scale)
                 finally:
-                    ops.check(ops._lib.lib().dd_set_adam_spare_cus(0), "dd_set_adam_spare_cus")
+                    _lib.call("dd_set_adam_spare_cus", 0)
             self._pending = [(q, g) for q, g in self._pending if q is not p]
         return 2 if bias is not None else 1
 
@@ -415,7 +415,7 @@ class HipAdam(torch.optim.Optimizer):
             raise RuntimeError("HipAdam: a clipped step (set_clip) runs its passes after the backward: no pass may start before every "
                                "gradient exists")
         self._side = torch.cuda.Stream()
-        ops.check(ops._lib.lib().dd_set_adam_blocks_per_cu(1), "dd_set_adam_blocks_per_cu")      # beside conv kernels: nothing queued ahead of them
+        _lib.call("dd_set_adam_blocks_per_cu", 1)      # beside conv kernels: nothing queued ahead of them
         self._scale = grad_scale
         if grad_sync is not None:
             self._sync = grad_sync

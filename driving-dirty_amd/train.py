@@ -79,7 +79,7 @@ class TrainStep:
         self.overlap = bool(adam_overlap)
         if not self.overlap and next(model.parameters()).is_cuda:
             from . import _lib
-            _lib.check(_lib.lib().dd_set_adam_blocks_per_cu(4), "dd_set_adam_blocks_per_cu")
+            _lib.call("dd_set_adam_blocks_per_cu", 4)
         if self.overlap:
             self.optimizer.overlap_with_backward(big_numel=big_numel, grad_scale=self.sync.grad_scale,
                                                  grad_sync=self.sync if (self.sync.active or self.sync.shard) else None)
