@@ -14,10 +14,12 @@ from . import ops
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 from .roadmap import predict_map
-from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, boxes_from_map, per_sample_inputs
+from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, box_loss_config, boxes_from_map, per_sample_inputs
 
 
 class JointRoadMapBBox(LightningModule):
+    box_loss = None      # spatial.box_loss_config(hparams): None = BCE on probabilities, as the reference's box model
+
     def __init__(self, hparams):
         super().__init__()
         self.hparams = hparams
@@ -32,6 +34,7 @@ class JointRoadMapBBox(LightningModule):
             if precision not in ("fp32", "fp32x3"):
                 raise ValueError(f"precision must be 'fp32' or 'fp32x3', got {precision!r}")
             self.box_merge.precision = precision
+        self.box_loss = box_loss_config(hparams)      # None: BCE on probabilities as the reference's box model (spatial_w_rm.py:131)
 
     def forward(self, x, rm):
         """x [B,6,3,256,306], rm [B,1,800,800] -> (roadmap logits [B,800,800], box probabilities [B,800,800]).  Both may also be
@@ -74,9 +77,14 @@ class JointRoadMapBBox(LightningModule):
             logits, boxes = self(sample, target_rm.unsqueeze(1))
             b = target_rm.size(0)
             loss_rm = ops.BceWithLogits.apply(logits.reshape(b, -1), target_rm.reshape(b, -1))
-        loss_bb = ops.BceProbs.apply(boxes.reshape(b, -1), target_bb.reshape(b, -1))
+        log = {}
+        if self.box_loss is not None:
+            loss_bb, log["bbox_bce"], log["bbox_soft_ts"] = ops.box_loss(boxes.reshape(b, -1), target_bb.reshape(b, -1).contiguous(),
+                                                                         return_parts=True, **self.box_loss)
+        else:
+            loss_bb = ops.BceProbs.apply(boxes.reshape(b, -1), target_bb.reshape(b, -1))
         loss = loss_rm + loss_bb
-        return {"loss": loss, "log": {"train_loss": loss, "roadmap_loss": loss_rm, "bbox_loss": loss_bb}}
+        return {"loss": loss, "log": {"train_loss": loss, "roadmap_loss": loss_rm, "bbox_loss": loss_bb, **log}}
 
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=self.hparams.learning_rate)

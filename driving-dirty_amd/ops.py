@@ -1390,6 +1390,84 @@ class BceProbs(torch.autograd.Function):
         return _scaled_loss_grad(ctx, dp, g), None
 
 
+POS_WEIGHT_AUTO = -1.0      # DD_POS_WEIGHT_AUTO
+
+
+def _box_loss_operands(probs, target, pos_weight):
+    """Host-side check of ``box_loss``'s operands -> (target as the kernels read it, DD_TARGET_*, pos_weight as the ABI takes it)."""
+    if not isinstance(probs, torch.Tensor) or probs.dim() != 2:
+        raise _lib.HotpathError(f"box_loss: probs must be [B, P], got {tuple(getattr(probs, 'shape', ()))}")
+    _dev(probs, "probs")
+    if not (isinstance(target, torch.Tensor) and target.is_cuda and target.is_contiguous() and target.shape == probs.shape
+            and target.dtype in (torch.float32, torch.uint8, torch.bool)):
+        raise _lib.HotpathError(f"box_loss: target must be a contiguous fp32 / uint8 / bool device tensor of shape {tuple(probs.shape)}, got "
+                                f"{getattr(target, 'dtype', type(target))} {tuple(getattr(target, 'shape', ()))}")
+    if pos_weight is None:
+        pos_weight = 1.0
+    elif isinstance(pos_weight, str):
+        if pos_weight != "auto":
+            raise _lib.HotpathError(f"box_loss: pos_weight must be None, a positive number or 'auto', got {pos_weight!r}")
+        pos_weight = POS_WEIGHT_AUTO
+    elif float(pos_weight) == POS_WEIGHT_AUTO:
+        raise _lib.HotpathError("box_loss: pos_weight must be positive (the per-sample weight is asked for as 'auto')")
+    return target, 0 if target.dtype == torch.float32 else 1, float(pos_weight)      # DD_TARGET_F32 / DD_TARGET_U8
+
+
+def box_loss_fwd(probs, target, pos_weight=None, bce_weight=1.0, ts_weight=0.0, ts_eps=1.0):
+    """dd_box_loss_fwd outside autograd -> (losses fp32 [3] = {L, L_bce, L_ts}, stats fp64 [B,5] = {T, S, I, A, C} per sample, coef fp32
+    [B,4]: the gradient coefficients ``box_loss_bwd`` takes).  One pass over the data for any weight; validation stops here."""
+    target, kind, pw = _box_loss_operands(probs, target, pos_weight)
+    b, per = probs.shape
+    losses = torch.empty(3, device=probs.device, dtype=torch.float32)
+    stats = torch.empty((b, 5), device=probs.device, dtype=torch.float64)
+    coef = torch.empty((b, 4), device=probs.device, dtype=torch.float32)
+    ws = torch.empty(size("dd_box_loss_workspace_bytes", b), device=probs.device, dtype=torch.uint8)
+    call("dd_box_loss_fwd", probs, target, kind, b, per, pw, float(bce_weight), float(ts_weight), float(ts_eps), losses, stats, coef, ws)
+    return losses, stats, coef
+
+
+def box_loss_bwd(probs, target, coef, grad_scale=1.0):
+    """dd_box_loss_bwd: d(loss)/d(probs) * grad_scale from the coefficients of ``box_loss_fwd`` on the same operands."""
+    target, kind, _ = _box_loss_operands(probs, target, None)
+    b, per = probs.shape
+    _dev(coef, "coef", (b, 4))
+    dprobs = torch.empty_like(probs)
+    call("dd_box_loss_bwd", probs, target, kind, b, per, coef, float(grad_scale), dprobs)
+    return dprobs
+
+
+class BoxLoss(torch.autograd.Function):
+    """Weighted BCE + soft threat score on probabilities (dd_box_loss_fwd / dd_box_loss_bwd; formulas in include/dd_hotpath.h) ->
+    (loss, L_bce, L_ts), the two components without a gradient.  The gradient is written with the forward, as the other losses do."""
+
+    @staticmethod
+    def forward(ctx, probs, target, pos_weight, bce_weight, ts_weight, ts_eps):
+        losses, _, coef = box_loss_fwd(probs, target, pos_weight, bce_weight, ts_weight, ts_eps)
+        ctx.save_for_backward(box_loss_bwd(probs, target, coef) if ctx.needs_input_grad[0] else None)
+        loss, bce, ts = losses.unbind(0)
+        ctx.mark_non_differentiable(bce, ts)
+        ctx.set_materialize_grads(False)
+        return loss, bce, ts
+
+    @staticmethod
+    def backward(ctx, g, _gb, _gt):
+        (dp,) = ctx.saved_tensors
+        if g is None or dp is None:
+            return (None,) * 6
+        return (_scaled_loss_grad(ctx, dp, g),) + (None,) * 5
+
+
+def box_loss(probs, target, pos_weight=None, bce_weight=1.0, ts_weight=0.0, ts_eps=1.0, return_parts=False):
+    """The class-balanced box-map loss ``bce_weight * L_bce + ts_weight * L_ts`` of probabilities ``probs`` [B, P] against ``target``
+    [B, P] (fp32 in [0,1], uint8 or bool): the 0-dim loss, differentiable in ``probs``.
+      * L_bce: mean binary cross-entropy with the positive elements weighted by ``pos_weight``: None (1), a positive number, or "auto" =
+        each sample's own (P - T_b) / max(T_b, 1), a constant of the step;
+      * L_ts: mean over the samples of 1 - (I_b + ts_eps) / (U_b + ts_eps), the soft threat score.
+    ``return_parts=True``: (loss, L_bce, L_ts), the components detached 0-dim tensors for logging."""
+    loss, bce, ts = BoxLoss.apply(probs, target, pos_weight, bce_weight, ts_weight, ts_eps)
+    return (loss, bce, ts) if return_parts else loss
+
+
 def sigmoid(z):
     """sigmoid(logits) outside autograd (the reference's second forward output, roadmap_bce_v2.py:81)."""
     _dev(z, "z")

@@ -129,6 +129,38 @@ def bb_coord_to_map(target, device=None, rasterizer=None):
     return ops.boxes_to_binary_map([t["bounding_box"] for t in target], device)
 
 
+def box_loss_config(hparams):
+    """The class-balanced box-map loss as the hparams ask for it: None when it is off (``box_pos_weight`` None, ``box_ts_weight`` 0,
+    ``box_bce_weight`` 1: the reference's loss, spatial_w_rm.py:128-131), else the keyword arguments of ``ops.box_loss``.
+    ``box_pos_weight``: None, a positive number (or a string that parses as one), or "auto" = each sample's own negatives / positives.
+    A value the kernels would refuse, or the loss together with ``mse_loss``, raises ValueError here, when the module is built."""
+    pos_weight = hparam(hparams, "box_pos_weight", None)
+    if isinstance(pos_weight, str) and pos_weight != "auto":
+        try:
+            pos_weight = float(pos_weight)
+        except ValueError:
+            raise ValueError(f"box_pos_weight must be a positive number or 'auto', got {pos_weight!r}") from None
+    if pos_weight is not None and pos_weight != "auto":
+        if isinstance(pos_weight, bool) or not isinstance(pos_weight, (int, float)) or not 0 < pos_weight < float("inf"):
+            raise ValueError(f"box_pos_weight must be a positive number or 'auto', got {pos_weight!r}")
+        pos_weight = float(pos_weight)
+    weights = {}
+    for name, default in (("box_bce_weight", 1.0), ("box_ts_weight", 0.0), ("box_ts_eps", 1.0)):
+        try:
+            weights[name] = float(hparam(hparams, name, default))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {hparam(hparams, name, default)!r}") from None
+        if not 0 <= weights[name] < float("inf"):
+            raise ValueError(f"{name} must be a finite number >= 0, got {weights[name]!r}")
+    if pos_weight is None and weights["box_ts_weight"] == 0 and weights["box_bce_weight"] == 1:
+        return None
+    if hparam(hparams, "mse_loss", False):
+        raise ValueError("box_pos_weight / box_bce_weight / box_ts_weight select a loss on probabilities and cannot be combined with mse_loss")
+    if weights["box_bce_weight"] == 0 and weights["box_ts_weight"] == 0:
+        raise ValueError("box_bce_weight and box_ts_weight are both 0: the loss would be constant")
+    return {"pos_weight": pos_weight, "bce_weight": weights["box_bce_weight"], "ts_weight": weights["box_ts_weight"], "ts_eps": weights["box_ts_eps"]}
+
+
 def compute_ats_bounding_boxes(boxes1, boxes2):
     """helper.py:33-72 for one sample, on the device: [n1,2,4] and [n2,2,4] corner tensors -> 0-dim average threat score
     (``iou_max`` over ``boxes1`` for each box of ``boxes2``).  An empty set scores 0 where the reference raises."""
@@ -155,6 +187,8 @@ class BBSpatialRoadMap(LightningModule):
     as one launch of the HIP rasteriser over the batch's ``'bounding_box'`` tensors; batches may instead carry a
     pre-rasterised ``'bb_map'`` [800,800] tensor in each target dict, or name their own ``hparams.rasterizer``."""
 
+    box_loss = None      # box_loss_config(hparams): None = the reference's loss
+
     def __init__(self, hparams):
         super().__init__()
         self.hparams = hparams
@@ -175,6 +209,7 @@ class BBSpatialRoadMap(LightningModule):
         self.box_merge = RoadMapBoxesMergingCNN()
         if hparam(hparams, "precision", None) is not None:
             self.box_merge.precision = "fp32x3" if precision == "fp32x3" else "fp32"
+        self.box_loss = box_loss_config(hparams)      # None: the reference's loss; a bad value fails here, not in the first step
 
     def wide_stitch_six_images(self, x):
         return ops.stitch6(x.contiguous(), want_nhwc4=False, want_nchw=True)[1]
@@ -193,6 +228,10 @@ class BBSpatialRoadMap(LightningModule):
         return bb_coord_to_map(target, device, hparam(self.hparams, "rasterizer", None))
 
     def _run_step(self, batch, batch_idx, step_name):
+        return self._run_step_parts(batch, batch_idx, step_name)[:3]
+
+    def _run_step_parts(self, batch, batch_idx, step_name):
+        """-> (loss, target, prediction, parts): parts is None with the reference's loss, (L_bce, L_ts) with ``box_loss_config``'s."""
         sample, target, road_image = batch
         if per_sample_inputs(sample, road_image):
             # the collate's tuples are read where they lie (pointer tables): no torch.stack of the 180 MB of views, no stack +
@@ -209,18 +248,24 @@ class BBSpatialRoadMap(LightningModule):
         batch_size = target_bb_img.size(0)
         target_bb_img = target_bb_img.reshape(batch_size, -1)
         pred_bb_img = pred_bb_img.reshape(batch_size, -1)
+        if self.box_loss is not None:
+            loss, bce, soft_ts = ops.box_loss(pred_bb_img, target_bb_img.contiguous(), return_parts=True, **self.box_loss)
+            return loss, target_bb_img, pred_bb_img, (bce, soft_ts)
         if hparam(self.hparams, "mse_loss", False):
             loss = ops.MseLoss.apply(pred_bb_img, target_bb_img)
         else:
             loss = ops.BceProbs.apply(pred_bb_img, target_bb_img)
-        return loss, target_bb_img, pred_bb_img
+        return loss, target_bb_img, pred_bb_img, None
 
     def training_step(self, batch, batch_idx):
         if self.current_epoch >= self.hparams.unfreeze_epoch_no and self.frozen:
             self.frozen = False
             self.ae.unfreeze()
-        train_loss, _, _ = self._run_step(batch, batch_idx, step_name="train")
-        return {"loss": train_loss, "log": {"train_loss": train_loss}}
+        train_loss, _, _, parts = self._run_step_parts(batch, batch_idx, step_name="train")
+        log = {"train_loss": train_loss}
+        if parts is not None:
+            log["bbox_bce"], log["bbox_soft_ts"] = parts
+        return {"loss": train_loss, "log": log}
 
     def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
         """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
@@ -231,8 +276,10 @@ class BBSpatialRoadMap(LightningModule):
             return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
     def validation_step(self, batch, batch_idx):
-        val_loss, target_bb_img, pred_bb_img = self._run_step(batch, batch_idx, step_name="valid")
+        val_loss, target_bb_img, pred_bb_img, parts = self._run_step_parts(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss}
+        if parts is not None:
+            out["val_bce"], out["val_soft_ts"] = parts
         if hparam(self.hparams, "box_metrics", False):
             # the task's own unit: boxes extracted from the predicted map against the targets' boxes, and the map-level threat score
             with torch.no_grad():
@@ -249,7 +296,7 @@ class BBSpatialRoadMap(LightningModule):
     def validation_epoch_end(self, outputs):
         avg_val_loss = torch.stack([x["val_loss"] for x in outputs]).mean()
         logs = {"avg_val_loss": avg_val_loss}
-        for k in ("val_ats", "val_ts"):          # present only under hparams.box_metrics
+        for k in ("val_ats", "val_ts", "val_bce", "val_soft_ts"):          # present only under hparams.box_metrics / the box-map loss
             if outputs and all(k in x for x in outputs):
                 logs["avg_" + k] = torch.stack([x[k] for x in outputs]).mean()
         return {"val_loss": avg_val_loss, "log": logs}
@@ -277,6 +324,13 @@ class BBSpatialRoadMap(LightningModule):
                             "(touching cars); 0 = off, at most 8")
         p.add_argument("--box_grow_iters", type=int, default=None,
                        help="box_metrics with --box_split_px: rounds the eroded cores grow back inside the map (default 2 * box_split_px, at most 16)")
+        p.add_argument("--box_pos_weight", type=str, default=None,
+                       help="box-map loss: weight of the positive (car) elements in the BCE: a positive number, or 'auto' = each sample's own "
+                            "negatives / positives; default: unweighted (the reference's loss)")
+        p.add_argument("--box_bce_weight", type=float, default=1.0, help="box-map loss: factor of the (weighted) BCE term")
+        p.add_argument("--box_ts_weight", type=float, default=0.0,
+                       help="box-map loss: factor of the soft threat-score term 1 - (I + eps) / (U + eps), per sample; 0 = off")
+        p.add_argument("--box_ts_eps", type=float, default=1.0, help="box-map loss: eps of the soft threat score (>= 0)")
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)

@@ -584,6 +584,37 @@ int dd_threat_score(const float* a, const float* b, float* out, int64_t n, int32
 enum { DD_TARGET_F32 = 0, DD_TARGET_U8 = 1 };
 int dd_ts_hist(const float* prob, const void* target, int32_t target_dtype, int64_t n, int32_t bins, int64_t* hist, void* stream);
 
+/* ---- class-balanced box-map loss: weighted BCE + soft threat score on probabilities ---------
+ * An alternative to dd_bce_probs for the box head's map (spatial_w_rm.py:128-131), whose target is a few percent positive.  probs is
+ * fp32 [batch][per_sample]; target the same shape, fp32 in [0,1] (DD_TARGET_F32) or one byte 0 / 1 per element (DD_TARGET_U8: uint8 /
+ * bool).  Per sample b, over its P = per_sample elements:
+ *   T = sum t,  S = sum p,  I = sum p t,  U = S + T - I,
+ *   A = sum t * -max(log p, -100),  C = sum (1 - t) * -max(log(1 - p), -100)          (the clamp of torch and dd_bce_probs)
+ *   w = pos_weight, or with pos_weight == DD_POS_WEIGHT_AUTO the sample's own (P - T) / max(T, 1): a sample's loss never depends on
+ *       the rest of the batch.  w is a constant of the step (no gradient through it), as pos_weight is in torch.
+ *   L_bce = 1 / (B P) * sum_b (w A + C)              = F.binary_cross_entropy(p, t, weight = 1 + (w - 1) t)
+ *   L_ts  = 1 / B * sum_b [1 - (I + eps) / (U + eps)]  the soft form of compute_ts_road_map (helper.py:74-77); eps = 0 on a sample
+ *                                                      with U = 0 is 0 / 0 and gives NaN, as the formula does
+ *   L     = bce_weight * L_bce + ts_weight * L_ts
+ *   dL/dp = -c0 t / p + c1 (1 - t) / (1 - p) - c2 t + c3 (1 - t),   the first term 0 where p = 0 and the second where p = 1 (the
+ *           clamped logs), with c0 = bce_weight w / (B P), c1 = bce_weight / (B P), c2 = ts_weight / (B (U + eps)),
+ *           c3 = ts_weight (I + eps) / (B (U + eps)^2).
+ * dd_box_loss_fwd: one pass over the data (five sums per sample, fp64 partials per workgroup in `workspace`, at least
+ * dd_box_loss_workspace_bytes(batch) bytes, 8-byte aligned) and one small launch that adds the partials in a fixed order and writes
+ * stats fp64 [batch][5] = {T, S, I, A, C}, coef fp32 [batch][4] = {c0, c1, c2, c3} (16-byte aligned) and loss_out fp32 [3] =
+ * {L, L_bce, L_ts}.  No atomics: two launches give the same bits.  Validation stops here.
+ * dd_box_loss_bwd: dprobs = dL/dp * grad_scale from probs, target and the coef of a forward call on the same operands.
+ * Any batch >= 1; per_sample a positive multiple of 4 (16-byte loads, nothing is read past the end), batch * per_sample <= 2^40.
+ * Refused before any device call: per_sample % 4 != 0 or an unknown dtype (DD_ERR_UNSUPPORTED); a NULL or misaligned buffer, a
+ * pos_weight <= 0 that is not DD_POS_WEIGHT_AUTO, eps < 0, a negative bce_weight or ts_weight, or a NaN among them (DD_ERR_BAD_ARG). */
+#define DD_POS_WEIGHT_AUTO (-1.0f)
+int64_t dd_box_loss_workspace_bytes(int32_t batch);
+int dd_box_loss_fwd(const float* probs, const void* target, int32_t target_dtype, int32_t batch, int64_t per_sample, float pos_weight,
+                    float bce_weight, float ts_weight, float ts_eps, float* loss_out, double* stats, float* coef, void* workspace,
+                    void* stream);
+int dd_box_loss_bwd(const float* probs, const void* target, int32_t target_dtype, int32_t batch, int64_t per_sample, const float* coef,
+                    float grad_scale, float* dprobs, void* stream);
+
 /* ---- box-level validation: map -> components -> boxes -> IoU -> average threat score ---------
  * The inverse direction of dd_boxes_to_binary_map, and compute_ats_bounding_boxes / compute_iou (src/utils/helper.py:33-83).
  *
