@@ -7,6 +7,8 @@
  *
  * Conventions
  *   - plain pointers to DEVICE memory, sizes as int32/int64, no torch types;
+ *   - every device pointer (operands and workspaces alike) is 16-byte aligned unless its entry point names a smaller
+ *     alignment; nothing is read or written outside the extent an entry point states for an operand;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - no allocation, no host synchronisation, no global state besides the thread-local
  *     error string; scratch memory is a caller-provided workspace sized by *_workspace_bytes;
@@ -221,7 +223,8 @@ int dd_pool4_relu_bwd(const float* dpooled, const float* feat, float* dfeat, int
 /* The same pooling with the backward's routing decided in the forward: `idx` receives one uint16 per thread-quad
  * (4 bits per window: index of the first maximum | (max > 0) << 2; dd_pool4_idx_elems of them, -1 when H*W or C
  * is not a multiple of 4), and dd_pool4_idx_relu_bwd scatters dpooled from those codes alone -- the 481 MB c3
- * feature (components.py:43) is neither kept for nor re-read by the backward. */
+ * feature (components.py:43) is neither kept for nor re-read by the backward.  idx: 2-byte aligned (C == 32 with a 4-byte
+ * aligned idx runs the tiled kernels; same codes, same results). */
 /* The joint roadmap + box model feeds the c3 feature to the pool AND to the box heads (joint_model: both losses on one encoder pass):
  * dfeat = (feat > 0) * (gfeat + routed dpooled) in ONE pass -- dd_relu_bwd(gfeat, feat) + dd_pool4_relu_bwd(dpooled, feat) + dd_add, same
  * arithmetic.  C == 32, H*W % 4 == 0, 16-byte aligned tensors. */
@@ -239,7 +242,10 @@ int dd_pool4_idx_relu_bwd(const float* dpooled, const uint16_t* idx, float* dfea
  * keep may be NULL (no dropout); scale = 1/(1-p).  save_mean/save_invstd [feat] are written in
  * training mode and consumed by the backward.  Running stats are updated in place with
  * `momentum` using the unbiased batch variance, as torch.nn.BatchNorm1d does; num_batches_tracked (device
- * int64, may be NULL) is incremented in training mode, as the module's forward does. */
+ * int64, may be NULL) is incremented in training mode, as the module's forward does.  Both entry points take any alignment a float
+ * can have (4 bytes); layers of 65536 features and more run several features per thread when every operand is 16-byte (forward) /
+ * 8-byte (backward) aligned: the sums over the rows run in the same order, but the updated running statistics may come out one
+ * rounding apart from the one-feature form's ((1 - momentum) * running + momentum * batch is contracted differently). */
 int dd_bn_relu_drop_fwd(const float* x, const float* gamma, const float* beta, float* running_mean,
                         float* running_var, const float* keep, float* y, float* save_mean,
                         float* save_invstd, int32_t rows, int32_t feat, float eps, float momentum,
@@ -290,7 +296,7 @@ int dd_bce_logits_u8(const float* logits, const unsigned char* target, float* lo
  * refused: the caller stacks the masks and calls dd_bce_logits_u8, which gives the same bits (ops.BceWithLogitsProbs does). */
 int dd_bce_logits_u8_ptrs(const float* logits, const unsigned char* const* target_ptrs, int32_t batch, int64_t per_sample,
                           float* loss_out, float* dlogits, float* probs, float grad_scale, void* workspace, void* stream);
-/* x[0..n) *= *scalar (a DEVICE float), skipped entirely on the device when *scalar == 1: the upstream gradient of the scalar
+/* x[0..n) *= *scalar (a DEVICE float, 4-byte aligned), skipped entirely on the device when *scalar == 1: the upstream gradient of the scalar
  * loss in `loss.backward()` (roadmap_bce_v2.py:106 / Lightning's backward) is 1, and the loss kernels above have already
  * written d(loss)/d(input); autograd's generic `grad * dz` would spend a full pass on multiplying by one. */
 int dd_scale_by_device_scalar(float* x, const float* scalar, int64_t n, void* stream);
@@ -415,7 +421,8 @@ int dd_dconv_wgrad(const float* x, const float* g, float* dw, int32_t batch, int
                    int32_t accumulate, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* out[c] (+)= sum over the npix pixels of buf[p, coff + c], c < cout <= 128 (bias gradient of a transposed conv whose
- * weight gradient is taken in the role-swapped form, see gconv.py). */
+ * weight gradient is taken in the role-swapped form, see gconv.py).  buf: any alignment a float can have (4 bytes); a 16-byte
+ * aligned buf with cstore % 4 == 0 streams 16-byte loads, which sums the pixels in another (fixed) order. */
 int64_t dd_channel_sum_workspace_bytes(void);
 int dd_channel_sum(const float* buf, float* out, int64_t npix, int32_t cstore, int32_t coff, int32_t cout, int32_t accumulate,
                    void* workspace, void* stream);
@@ -550,7 +557,9 @@ int dd_bce_probs(const float* probs, const float* target, float* loss_out, float
  *   dgrad dx[M,K] = dy[M,N] w[N,K]
  *   wgrad dw[N,K] = dy[M,N]^T x[M,K];  dbias[N] = sum_m dy[m,:]   (dbias may be NULL)
  * fwd/dgrad split the long contraction over workgroups and reduce the partial slabs in a fixed order
- * (deterministic); `workspace` must hold dd_linear_workspace_bytes(m, n, k) bytes. */
+ * (deterministic); `workspace` must hold dd_linear_workspace_bytes(m, n, k) bytes.  dd_linear_wgrad takes x and dw at any
+ * alignment a float can have (4 bytes): rows of K >= 512 go out as 16-byte stores when both are 16-byte aligned, through the
+ * scalar tiles otherwise. */
 int64_t dd_linear_workspace_bytes(int32_t m, int32_t n, int32_t k);
 int dd_linear_fwd(const float* x, const float* w, const float* bias, float* y, int32_t m, int32_t n, int32_t k,
                   void* workspace, int64_t workspace_bytes, void* stream);
