@@ -6,19 +6,32 @@ the encoder conv stack feeds both the latent path (pool -> dense blocks -> Linea
 roadmap_bce_v2.py:66-108) and the box path (SpatialMappingCNN + RoadMapBoxesMergingCNN -> BCE on probabilities,
 spatial_w_rm.py:67-131); the losses add, the two gradients of the shared c3 feature add inside the encoder's
 backward.  Parity is checked per head against the oracle (tests/test_gpu_heads.py).
+
+Camera-only use.  The box head reads a road map (``rm_conv_1``).  ``forward(x, rm)`` and the default training
+step hand it the ground truth, as the reference's box model does (spatial_w_rm.py:67-83); at test time there is none, and the
+model's own road-map head supplies it: ``predict`` / ``predict_boxes(x)`` / ``validation_step``'s ``val_ats`` and, with
+``hparams.box_rm_input = "predicted"``, the training step feed the head's thresholded map into the box branch
+(``_own_road_masks`` states the rule).  All of it runs on the entry points the two heads already use.
 """
+from argparse import ArgumentParser
+from collections import namedtuple
+
 import torch
 from torch import nn
 
 from . import ops
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
-from .roadmap import predict_map
-from .spatial import RoadMapBoxesMergingCNN, SpatialMappingCNN, bb_coord_to_map, box_loss_config, boxes_from_map, per_sample_inputs
+from .roadmap import CalibratedThreshold, eval_no_grad, predict_map, prediction_threshold, road_map_scores
+from .spatial import (RoadMapBoxesMergingCNN, SpatialMappingCNN, add_box_args, bb_coord_to_map, box_loss_config, boxes_from_map,
+                      decoded_box_ats, mean_logs, per_sample_inputs, require_bounding_boxes)
+
+Prediction = namedtuple("Prediction", ("road_map", "boxes"))      # torch.bool [B,800,800], tuple of B tensors [n_i,2,4]
 
 
-class JointRoadMapBBox(LightningModule):
+class JointRoadMapBBox(CalibratedThreshold, LightningModule):
     box_loss = None      # spatial.box_loss_config(hparams): None = BCE on probabilities, as the reference's box model
+    box_rm_input = "target"      # the road map the TRAINING step's box branch reads: "target" (ground truth) | "predicted" (the head's own)
 
     def __init__(self, hparams):
         super().__init__()
@@ -35,24 +48,78 @@ class JointRoadMapBBox(LightningModule):
                 raise ValueError(f"precision must be 'fp32' or 'fp32x3', got {precision!r}")
             self.box_merge.precision = precision
         self.box_loss = box_loss_config(hparams)      # None: BCE on probabilities as the reference's box model (spatial_w_rm.py:131)
+        self.box_rm_input = hparam(hparams, "box_rm_input", "target")
+        if self.box_rm_input not in ("target", "predicted"):
+            raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")
+
+    # ------------------------------------------------------------------------------------------------ the parts of one pass
+    def _features(self, x):
+        """x as ``forward`` takes it -> (conv feature [B,32,128,918] as an NCHW-shaped view, pooled vector for the encoder's tail,
+        SpatialMappingCNN's map [B,32,256,256]): everything both heads share or that reads the cameras, once."""
+        x = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
+        wide4 = ops.wide_image(x)                                     # fp32 views or uint8 frames, tensor or the collate's tuple
+        feat, pooled = self.ae.encoder.conv_feature_and_pooled(wide4)
+        return feat, pooled, self.space_map_cnn(x)
+
+    def _box_branch(self, feat, space_rep, rm):
+        """-> box probabilities [B,800,800].  ``rm``: [B,1,800,800] fp32, or a tuple of B bool / uint8 [800,800] masks."""
+        return self.box_merge(feat, space_rep, rm).squeeze(1)
+
+    def _road_logits(self, pooled):
+        """The encoder's dense tail and the road-map head -> logits [B,800,800]."""
+        z = self.ae.encoder._tail(pooled, (None, None))
+        return ops.linear(z, self.fc1.weight, self.fc1.bias).reshape(-1, 800, 800)
+
+    @staticmethod
+    def _own_road_masks(values, tau, logits=False):
+        """The road-map head's output as the masks the box branch reads: a tuple of B contiguous torch.bool [800,800] views, the form
+        ``heads.road_map_taps`` gathers from through ``ops.subsample_masks_nhwc4`` (any B: that entry point cuts its pointer table
+        into chunks of ``ops.PTR_TABLE_MAX`` itself, so nothing is chunked here).
+
+        THE RULE, stated once: a pixel is road where the head's PROBABILITY is ``> tau``, strictly, ``tau`` rounded to fp32.  The
+        probability is the dense head's one sigmoid (csrc/dd_device.h) of the fp32 logit: what ``ops.sigmoid`` returns, what the BCE
+        pass returns beside the loss, and what ``ops.linear_sigmoid_gt`` compares inside the head's kernel -- the same bits, so
+        ``predict``, ``validation_step`` and the self-fed training step draw the same map from the same logits.  ``values`` holds
+        probabilities; with ``logits=True`` it holds logits and goes through ``ops.sigmoid`` first (never compared against
+        ``logit(tau)``: that is a different rounding).  No gradient passes through the map."""
+        probs = ops.sigmoid(values.detach().contiguous()) if logits else values.detach()
+        return tuple((probs.reshape(-1, 800, 800) > float(tau)).unbind(0))
+
+    def _own_tau(self):
+        return prediction_threshold(self, None)      # the calibrated rm_threshold, else the reference's 0.5
 
     def forward(self, x, rm):
         """x [B,6,3,256,306], rm [B,1,800,800] -> (roadmap logits [B,800,800], box probabilities [B,800,800]).  Both may also be
         the collate's tuples (per-sample views, bool road masks), read through pointer tables."""
-        x = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
-        wide4 = ops.wide_image(x)                                     # fp32 views or uint8 frames, tensor or the collate's tuple
-        feat, pooled = self.ae.encoder.conv_feature_and_pooled(wide4)
+        feat, pooled, space_rep = self._features(x)
         # the box branch FIRST, the encoder's dense tail and the road-map head after it: autograd runs the newest nodes first, so
         # the two tensors that are 99.6 % of the data-parallel message (encoder fc1.fc1.weight 481 MB, head fc1.weight 164 MB) get
         # their gradients at the START of the backward and their reduction has the whole box-head backward (~40 ms) to hide under
         # instead of its last 5 (tools/step_phases.py); same arithmetic, same results
-        boxes = self.box_merge(feat, self.space_map_cnn(x), rm).squeeze(1)
-        z = self.ae.encoder._tail(pooled, (None, None))
-        logits = ops.linear(z, self.fc1.weight, self.fc1.bias).reshape(-1, 800, 800)
-        return logits, boxes
+        boxes = self._box_branch(feat, space_rep, rm)
+        return self._road_logits(pooled), boxes
 
-    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
-        """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4]."""
+    # ------------------------------------------------------------------------------------------------ prediction
+    def predict(self, x, threshold=None, box_threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+        """What the task asks for, from the six cameras alone: ``Prediction(road_map, boxes)``, torch.bool [B,800,800] and a tuple of
+        B tensors [n_i,2,4].  One encoder pass under ``no_grad`` in ``eval()`` mode (every submodule's mode is put back): the road
+        map from ``ops.linear_sigmoid_gt`` at ``threshold`` (None: the calibrated ``rm_threshold``, else 0.5), that map into the box
+        branch, the box map at ``box_threshold`` through ``boxes_from_map``.  ``x``: whatever ``forward`` takes.  The same kernels on
+        the same inputs as ``predict_road_map(x)`` followed by ``predict_boxes(x, masks)``, minus the second encoder conv pass."""
+        tau = prediction_threshold(self, threshold)
+        with eval_no_grad(self):
+            feat, pooled, space_rep = self._features(x)
+            z = self.ae.encoder._tail(pooled, (None, None))
+            road = ops.linear_sigmoid_gt(z, self.fc1.weight, self.fc1.bias, tau).reshape(-1, 800, 800)
+            probs = self._box_branch(feat, space_rep, tuple(road.unbind(0)))
+            boxes = boxes_from_map(probs, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
+        return Prediction(road, boxes)
+
+    def predict_boxes(self, x, rm=None, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+        """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4].  ``rm=None``: camera-only,
+        the boxes of ``predict`` (the head's own road map at its calibrated threshold); a given ``rm`` is used as it is."""
+        if rm is None:
+            return self.predict(x, None, threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters).boxes
         with torch.no_grad():
             return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
@@ -61,30 +128,110 @@ class JointRoadMapBBox(LightningModule):
         views = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
         return predict_map(self, lambda: self.ae.encoder.forward_nhwc4(ops.wide_image(views)), threshold)
 
-    def training_step(self, batch, batch_idx):
+    # ------------------------------------------------------------------------------------------------ the steps
+    def _run_step(self, batch, own_rm, want_probs):
+        """One pass over a batch -> a dict: both losses (``loss_rm``, ``loss_bb``, the class-balanced loss's ``parts`` or None), the
+        tensors validation scores (``logits``, ``boxes``, ``target_bb`` [b,800,800], ``probs`` when ``want_probs``) and what a second
+        box-branch call needs (``feat``, ``space_rep``).  ``own_rm``: the box branch reads the head's own map instead of the batch's."""
         sample, target, road_image = batch
-        if per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image) and len(road_image) <= ops.PTR_TABLE_MAX:
+        per_sample = (per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image)
+                      and len(road_image) <= ops.PTR_TABLE_MAX)
+        if per_sample:
             # roadmap_bce_v2.py:87 / spatial_w_rm.py:100-105 without the stacks: views and masks are read where the collate left them
-            dev = sample[0].device
-            b = len(sample)
-            target_bb = bb_coord_to_map(target, dev).to(dev).float()
-            logits, boxes = self(tuple(sample), tuple(road_image))
-            loss_rm, _ = ops.BceWithLogitsProbs.apply(logits.reshape(b, -1), tuple(road_image))
+            sample, rm, dev = tuple(sample), tuple(road_image), sample[0].device
         else:
             sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
             target_rm = torch.stack(tuple(road_image), dim=0).float()
-            target_bb = bb_coord_to_map(target, sample.device).to(sample.device).float()
-            logits, boxes = self(sample, target_rm.unsqueeze(1))
-            b = target_rm.size(0)
+            rm, dev = target_rm.unsqueeze(1), sample.device
+        b = len(road_image)
+        target_bb = bb_coord_to_map(target, dev).to(dev).float()
+        feat, pooled, space_rep = self._features(sample)
+        if own_rm:
+            logits = self._road_logits(pooled)
+            boxes = self._box_branch(feat, space_rep, self._own_road_masks(logits, self._own_tau(), logits=True))
+        else:
+            boxes = self._box_branch(feat, space_rep, rm)      # first: see forward
+            logits = self._road_logits(pooled)
+        probs = None
+        if per_sample:
+            loss_rm, probs = ops.BceWithLogitsProbs.apply(logits.reshape(b, -1), rm)
+        else:
             loss_rm = ops.BceWithLogits.apply(logits.reshape(b, -1), target_rm.reshape(b, -1))
-        log = {}
+            if want_probs:
+                probs = ops.sigmoid(logits.detach())
+        parts = None
         if self.box_loss is not None:
-            loss_bb, log["bbox_bce"], log["bbox_soft_ts"] = ops.box_loss(boxes.reshape(b, -1), target_bb.reshape(b, -1).contiguous(),
-                                                                         return_parts=True, **self.box_loss)
+            loss_bb, *parts = ops.box_loss(boxes.reshape(b, -1), target_bb.reshape(b, -1).contiguous(), return_parts=True, **self.box_loss)
         else:
             loss_bb = ops.BceProbs.apply(boxes.reshape(b, -1), target_bb.reshape(b, -1))
-        loss = loss_rm + loss_bb
-        return {"loss": loss, "log": {"train_loss": loss, "roadmap_loss": loss_rm, "bbox_loss": loss_bb, **log}}
+        return {"b": b, "loss_rm": loss_rm, "loss_bb": loss_bb, "parts": parts, "logits": logits, "boxes": boxes, "target_bb": target_bb,
+                "probs": None if probs is None else probs.detach().reshape(b, 800, 800), "feat": feat, "space_rep": space_rep}
+
+    def training_step(self, batch, batch_idx):
+        """``hparams.box_rm_input = "target"`` (the default): the box branch reads the batch's road map, the step the reference's two
+        models add up to.  ``"predicted"``: it reads the head's own map at ``rm_threshold`` (else 0.5), cut from the detached logits of
+        this very pass, so the box head trains on the input it gets at test time; the road-map loss still uses the ground truth and
+        no gradient of the box loss reaches the road-map head through the map.  The logits have to exist before the box branch
+        then, so the autograd order of the two branches SWAPS: the box head's backward runs first and the two big Linear gradients
+        (``forward`` says why they come first by default) finish late in the backward, with little left to hide their reduction
+        under in data-parallel training."""
+        s = self._run_step(batch, self.box_rm_input == "predicted", False)
+        log = {}
+        if s["parts"] is not None:
+            log["bbox_bce"], log["bbox_soft_ts"] = s["parts"]
+        loss = s["loss_rm"] + s["loss_bb"]
+        return {"loss": loss, "log": {"train_loss": loss, "roadmap_loss": s["loss_rm"], "bbox_loss": s["loss_bb"], **log}}
+
+    def validation_step(self, batch, batch_idx):
+        """One encoder pass, one road-map head pass.  Always: ``val_loss`` = ``val_roadmap_loss`` + ``val_bbox_loss`` (the training
+        step's losses; ``val_bce`` / ``val_soft_ts`` with the class-balanced box loss), the road map's ``val_ts`` / ``val_ts_rounded`` as
+        ``RoadMapBCE`` reports them, ``ts_hist`` under ``hparams.calibrate_threshold``.  Under ``hparams.box_metrics`` also
+        ``val_ats_gt_rm`` (boxes decoded from the box map computed WITH the ground-truth road map), ``val_ats`` (the honest one: a
+        second box-branch call fed the head's own map of this pass, at ``rm_threshold`` or 0.5) and ``val_box_ts`` (the rounded
+        map-level threat score of that camera-only box map)."""
+        sample, target, road_image = batch
+        s = self._run_step(batch, False, True)
+        out = {"val_loss": s["loss_rm"] + s["loss_bb"], "val_roadmap_loss": s["loss_rm"], "val_bbox_loss": s["loss_bb"]}
+        if s["parts"] is not None:
+            out["val_bce"], out["val_soft_ts"] = s["parts"]
+        target_rm = torch.stack(tuple(road_image), dim=0).float()
+        out.update(road_map_scores(target_rm, s["probs"]))
+        self._with_ts_hist(out, s["probs"], target_rm)
+        if hparam(self.hparams, "box_metrics", False):
+            with torch.no_grad():
+                require_bounding_boxes(target)
+                out["val_ats_gt_rm"] = decoded_box_ats(self.hparams, s["boxes"].detach().contiguous(), target)
+                own = self._box_branch(s["feat"], s["space_rep"], self._own_road_masks(s["probs"], self._own_tau())).contiguous()
+                out["val_ats"] = decoded_box_ats(self.hparams, own, target)
+                out["val_box_ts"] = ops.threat_score(s["target_bb"].contiguous(), own, round_b=True)
+        return out
+
+    def validation_epoch_end(self, outputs):
+        """The mean of every per-batch value as ``avg_*``; ``val_loss`` is the monitored value; under ``hparams.calibrate_threshold``
+        ``rm_threshold`` is set from the epoch's summed histogram, as in ``RoadMapBCE``."""
+        keys = ("val_loss", "val_roadmap_loss", "val_bbox_loss", "val_bce", "val_soft_ts", "val_ts", "val_ts_rounded", "val_ats_gt_rm",
+                "val_ats", "val_box_ts")
+        logs = mean_logs(outputs, keys)
+        self._calibrate(outputs, logs)
+        return {"val_loss": logs["avg_val_loss"], "log": logs}
 
     def configure_optimizers(self):
         return torch.optim.Adam(self.parameters(), lr=self.hparams.learning_rate)
+
+    @staticmethod
+    def add_model_specific_args(parent_parser):
+        p = ArgumentParser(parents=[parent_parser], add_help=False)
+        p.add_argument("--learning_rate", type=float, default=1e-3)
+        p.add_argument("--batch_size", type=int, default=16)
+        p.add_argument("--calibrate_threshold", action="store_true",
+                       help="validation also finds the road-map threshold with the best data-set threat score (rm_threshold)")
+        add_box_args(p)
+        p.add_argument("--box_rm_input", type=str, default="target", choices=("target", "predicted"),
+                       help="the road map the box head reads in TRAINING: the ground truth (the reference's step), or the road-map head's "
+                            "own thresholded map, as at test time")
+        p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
+        p.add_argument("--pretrained_path", type=str, default="")
+        p.add_argument("--output_img_freq", type=int, default=500)
+        p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "fp32x3"),
+                       help="fp32: the reference's arithmetic; fp32x3: the box head's dilated up-convs as six bf16 products per fp32 product")
+        return p

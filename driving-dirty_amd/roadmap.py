@@ -6,6 +6,7 @@ src/roadmap_model/roadmap_pretrain_ae.py (``roadmap_mse``).  Same constructor, `
 ``configure_optimizers`` and ``state_dict`` keys (``ae.encoder.*``, ``fc1.*``).
 """
 from argparse import ArgumentParser
+from contextlib import contextmanager
 
 import torch
 from torch import nn
@@ -16,21 +17,35 @@ from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 
 
-def predict_map(module, latent, threshold):
-    """``module``'s road-map head as a boolean map: ``latent()`` (the encoder) -> ``ops.linear_sigmoid_gt`` with ``module.fc1``, under
-    ``no_grad`` and in ``eval()`` mode; every submodule's mode is put back afterwards (a frozen extractor stays in eval inside a
-    training model).  ``threshold=None``: the calibrated ``rm_threshold`` where there is one, else the reference's 0.5."""
-    if threshold is None:
-        threshold = hparam(module.hparams, "rm_threshold", None)
-    tau = 0.5 if threshold is None else float(threshold)
+@contextmanager
+def eval_no_grad(module):
+    """``module`` in ``eval()`` mode under ``no_grad``; on exit every submodule's mode is what it was (a frozen extractor stays in eval
+    inside a training model)."""
     modes = [(m, m.training) for m in module.modules()]
     module.eval()
     try:
         with torch.no_grad():
-            y = ops.linear_sigmoid_gt(latent(), module.fc1.weight, module.fc1.bias, tau)
+            yield
     finally:
         for m, was in modes:
             m.training = was
+
+
+def prediction_threshold(module, threshold):
+    """The operating point of a prediction: ``threshold``, else the calibrated ``rm_threshold`` of ``module.hparams`` where there is
+    one, else the reference's 0.5."""
+    if threshold is None:
+        threshold = hparam(module.hparams, "rm_threshold", None)
+    return 0.5 if threshold is None else float(threshold)
+
+
+def predict_map(module, latent, threshold):
+    """``module``'s road-map head as a boolean map: ``latent()`` (the encoder) -> ``ops.linear_sigmoid_gt`` with ``module.fc1``, under
+    ``no_grad`` and in ``eval()`` mode; every submodule's mode is put back afterwards (a frozen extractor stays in eval inside a
+    training model).  ``threshold=None``: the calibrated ``rm_threshold`` where there is one, else the reference's 0.5."""
+    tau = prediction_threshold(module, threshold)
+    with eval_no_grad(module):
+        y = ops.linear_sigmoid_gt(latent(), module.fc1.weight, module.fc1.bias, tau)
     return y.reshape(y.size(0), 800, 800)
 
 
@@ -39,7 +54,45 @@ def compute_ts_road_map(road_map1, road_map2):
     return ops.threat_score(road_map1.contiguous(), road_map2.contiguous())
 
 
-class RoadMapBCE(LightningModule):
+def road_map_scores(target_rm, probs):
+    """{'val_ts', 'val_ts_rounded'} of a validation batch: the threat score of the probabilities and of the rounded probabilities
+    against the fp32 target (roadmap_bce_v2.py:117-118)."""
+    target_rm, probs = target_rm.contiguous(), probs.contiguous()
+    return {"val_ts": ops.threat_score(target_rm, probs), "val_ts_rounded": ops.threat_score(target_rm, probs, round_b=True)}
+
+
+class CalibratedThreshold:
+    """What a module with a road-map head needs to calibrate its operating point on validation data (hparams.calibrate_threshold)
+    and to carry it: the ``rm_threshold`` property, the per-batch histogram and the epoch's argmax.  Shared by the road-map modules
+    and the joint model."""
+
+    @property
+    def rm_threshold(self):
+        """The operating point ``validation_epoch_end`` calibrated (hparams.calibrate_threshold), a plain float, or None.  Kept in
+        ``hparams`` -- not a buffer, not in the state_dict -- so ``save_checkpoint`` / ``load_from_checkpoint`` carry it."""
+        return hparam(self.hparams, "rm_threshold", None)
+
+    @rm_threshold.setter
+    def rm_threshold(self, value):
+        self.hparams.rm_threshold = None if value is None else float(value)
+
+    def _with_ts_hist(self, out, probs, target_rm):
+        if hparam(self.hparams, "calibrate_threshold", False):
+            out["ts_hist"] = ops.ts_histogram(probs.detach().contiguous(), target_rm.contiguous())
+        return out
+
+    def _calibrate(self, outputs, logs):
+        """Under hparams.calibrate_threshold: ``rm_threshold`` <- the threshold with the best threat score of the DATA SET (the summed
+        histograms; the ``avg_*`` values are means of per-batch scores), and its figures into ``logs``."""
+        if hparam(self.hparams, "calibrate_threshold", False):
+            hist = torch.stack([x["ts_hist"] for x in outputs]).sum(0)
+            ts, best = ops.ts_curve(hist)
+            self.rm_threshold = best / ts.numel()
+            logs.update(best_threshold=self.rm_threshold, best_val_ts=float(ts[best]), val_ts_at_half=float(ts[ts.numel() // 2]))
+        return logs
+
+
+class RoadMapBCE(CalibratedThreshold, LightningModule):
     def __init__(self, hparams):
         super().__init__()
         self.hparams = hparams
@@ -77,16 +130,6 @@ class RoadMapBCE(LightningModule):
         """-> (logits [B,800,800], sigmoid(logits)).  roadmap_bce_v2.py:66-81."""
         y = self._logits(x, keeps)
         return y, ops.sigmoid(y.detach())
-
-    @property
-    def rm_threshold(self):
-        """The operating point ``validation_epoch_end`` calibrated (hparams.calibrate_threshold), a plain float, or None.  Kept in
-        ``hparams`` -- not a buffer, not in the state_dict -- so ``save_checkpoint`` / ``load_from_checkpoint`` carry it."""
-        return hparam(self.hparams, "rm_threshold", None)
-
-    @rm_threshold.setter
-    def rm_threshold(self, value):
-        self.hparams.rm_threshold = None if value is None else float(value)
 
     def predict_road_map(self, x, threshold=None):
         """The reference's "Predicting test images" step (run_test.py) for one batch: torch.bool [B,800,800], equal to ``forward``'s
@@ -137,25 +180,13 @@ class RoadMapBCE(LightningModule):
 
     def validation_step(self, batch, batch_idx):
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
-        val_ts = compute_ts_road_map(target_rm, pred_logit_rm)
-        val_ts_rounded = ops.threat_score(target_rm.contiguous(), pred_logit_rm.contiguous(), round_b=True)
-        out = {"val_loss": val_loss, "val_ts_rounded": val_ts_rounded, "val_ts": val_ts}
+        out = {"val_loss": val_loss, **road_map_scores(target_rm, pred_logit_rm)}
         return self._with_ts_hist(out, pred_logit_rm, target_rm)
-
-    def _with_ts_hist(self, out, probs, target_rm):
-        if hparam(self.hparams, "calibrate_threshold", False):
-            out["ts_hist"] = ops.ts_histogram(probs.detach().contiguous(), target_rm.contiguous())
-        return out
 
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
-        if hparam(self.hparams, "calibrate_threshold", False):
-            # the DATA SET's threat score at every threshold k / bins (the averages above are means of per-batch scores)
-            hist = torch.stack([x["ts_hist"] for x in outputs]).sum(0)
-            ts, best = ops.ts_curve(hist)
-            self.rm_threshold = best / ts.numel()
-            logs.update(best_threshold=self.rm_threshold, best_val_ts=float(ts[best]), val_ts_at_half=float(ts[ts.numel() // 2]))
+        self._calibrate(outputs, logs)
         return {"val_loss": avg["val_loss"], "log": logs}
 
     def configure_optimizers(self):

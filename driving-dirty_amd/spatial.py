@@ -182,6 +182,50 @@ def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent
     return tuple(boxes[i, :min(c, max_boxes)] for i, c in enumerate(counts))
 
 
+def require_bounding_boxes(targets):
+    """``box_metrics`` scores boxes against boxes: every target must hold its ``'bounding_box'`` tensor."""
+    missing = [i for i, t in enumerate(targets) if "bounding_box" not in t]
+    if missing:
+        raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
+
+
+def decoded_box_ats(hparams, pred_maps, targets):
+    """The task's own unit for one batch: boxes extracted from the predicted maps [b,800,800] as ``hparams`` ask (``box_fit``,
+    ``box_pad_px``, ``box_split_px``, ``box_grow_iters``) against the targets' boxes -> the batch's mean average threat score, 0-dim."""
+    fitted = boxes_from_map(pred_maps, fit=hparam(hparams, "box_fit", "extent"), pad_px=hparam(hparams, "box_pad_px", 0.5),
+                            split_px=hparam(hparams, "box_split_px", 0), grow_iters=hparam(hparams, "box_grow_iters", None))
+    return ops.ats_bounding_boxes(fitted, [t["bounding_box"] for t in targets]).mean()
+
+
+def mean_logs(outputs, keys):
+    """{'avg_' + k: mean over the epoch's outputs} for every k of ``keys`` that all outputs hold."""
+    return {"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in keys if outputs and all(k in x for x in outputs)}
+
+
+def add_box_args(p):
+    """The command-line flags of box validation and of the box-map loss, shared by every module with a box head."""
+    p.add_argument("--box_metrics", action="store_true",
+                   help="validation also extracts boxes from the predicted map and reports val_ats (average threat score against the "
+                        "targets' boxes) and val_ts (map-level threat score)")
+    p.add_argument("--box_fit", type=str, default="extent", choices=("extent", "oriented"),
+                   help="how box_metrics fits a box to a component of the predicted map: its axis-aligned extent, or the rectangle "
+                        "along its principal axis (the data set's boxes are rotated)")
+    p.add_argument("--box_pad_px", type=float, default=0.5,
+                   help="oriented fit: pixels added on each side of the pixel centres' extents (0.5 = the pixel squares, 0 = the centres)")
+    p.add_argument("--box_split_px", type=int, default=0,
+                   help="box_metrics: split blobs joined through a neck narrower than 2 * box_split_px + 1 pixels before fitting "
+                        "(touching cars); 0 = off, at most 8")
+    p.add_argument("--box_grow_iters", type=int, default=None,
+                   help="box_metrics with --box_split_px: rounds the eroded cores grow back inside the map (default 2 * box_split_px, at most 16)")
+    p.add_argument("--box_pos_weight", type=str, default=None,
+                   help="box-map loss: weight of the positive (car) elements in the BCE: a positive number, or 'auto' = each sample's own "
+                        "negatives / positives; default: unweighted (the reference's loss)")
+    p.add_argument("--box_bce_weight", type=float, default=1.0, help="box-map loss: factor of the (weighted) BCE term")
+    p.add_argument("--box_ts_weight", type=float, default=0.0,
+                   help="box-map loss: factor of the soft threat-score term 1 - (I + eps) / (U + eps), per sample; 0 = off")
+    p.add_argument("--box_ts_eps", type=float, default=1.0, help="box-map loss: eps of the soft threat score (>= 0)")
+
+
 class BBSpatialRoadMap(LightningModule):
     """spatial_w_rm.py:25-167.  ``bb_coord_to_map`` (the per-sample PIL polygon loop of src/utils/bb_to_img.py) runs
     as one launch of the HIP rasteriser over the batch's ``'bounding_box'`` tensors; batches may instead carry a
@@ -283,22 +327,15 @@ class BBSpatialRoadMap(LightningModule):
         if hparam(self.hparams, "box_metrics", False):
             # the task's own unit: boxes extracted from the predicted map against the targets' boxes, and the map-level threat score
             with torch.no_grad():
-                missing = [i for i, t in enumerate(batch[1]) if "bounding_box" not in t]
-                if missing:
-                    raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
-                pred = pred_bb_img.detach().reshape(-1, 800, 800).contiguous()
-                fitted = boxes_from_map(pred, fit=hparam(self.hparams, "box_fit", "extent"), pad_px=hparam(self.hparams, "box_pad_px", 0.5),
-                                        split_px=hparam(self.hparams, "box_split_px", 0), grow_iters=hparam(self.hparams, "box_grow_iters", None))
-                out["val_ats"] = ops.ats_bounding_boxes(fitted, [t["bounding_box"] for t in batch[1]]).mean()
+                require_bounding_boxes(batch[1])
+                out["val_ats"] = decoded_box_ats(self.hparams, pred_bb_img.detach().reshape(-1, 800, 800).contiguous(), batch[1])
                 out["val_ts"] = ops.threat_score(target_bb_img.contiguous(), pred_bb_img.detach().contiguous(), round_b=True)
         return out
 
     def validation_epoch_end(self, outputs):
         avg_val_loss = torch.stack([x["val_loss"] for x in outputs]).mean()
         logs = {"avg_val_loss": avg_val_loss}
-        for k in ("val_ats", "val_ts", "val_bce", "val_soft_ts"):          # present only under hparams.box_metrics / the box-map loss
-            if outputs and all(k in x for x in outputs):
-                logs["avg_" + k] = torch.stack([x[k] for x in outputs]).mean()
+        logs.update(mean_logs(outputs, ("val_ats", "val_ts", "val_bce", "val_soft_ts")))      # present only under hparams.box_metrics / the box-map loss
         return {"val_loss": avg_val_loss, "log": logs}
 
     def configure_optimizers(self):
@@ -311,26 +348,7 @@ class BBSpatialRoadMap(LightningModule):
         p.add_argument("--unfreeze_epoch_no", type=int, default=0)
         p.add_argument("--batch_size", type=int, default=16)
         p.add_argument("--mse_loss", action="store_true")
-        p.add_argument("--box_metrics", action="store_true",
-                       help="validation also extracts boxes from the predicted map and reports val_ats (average threat score against the "
-                            "targets' boxes) and val_ts (map-level threat score)")
-        p.add_argument("--box_fit", type=str, default="extent", choices=("extent", "oriented"),
-                       help="how box_metrics fits a box to a component of the predicted map: its axis-aligned extent, or the rectangle "
-                            "along its principal axis (the data set's boxes are rotated)")
-        p.add_argument("--box_pad_px", type=float, default=0.5,
-                       help="oriented fit: pixels added on each side of the pixel centres' extents (0.5 = the pixel squares, 0 = the centres)")
-        p.add_argument("--box_split_px", type=int, default=0,
-                       help="box_metrics: split blobs joined through a neck narrower than 2 * box_split_px + 1 pixels before fitting "
-                            "(touching cars); 0 = off, at most 8")
-        p.add_argument("--box_grow_iters", type=int, default=None,
-                       help="box_metrics with --box_split_px: rounds the eroded cores grow back inside the map (default 2 * box_split_px, at most 16)")
-        p.add_argument("--box_pos_weight", type=str, default=None,
-                       help="box-map loss: weight of the positive (car) elements in the BCE: a positive number, or 'auto' = each sample's own "
-                            "negatives / positives; default: unweighted (the reference's loss)")
-        p.add_argument("--box_bce_weight", type=float, default=1.0, help="box-map loss: factor of the (weighted) BCE term")
-        p.add_argument("--box_ts_weight", type=float, default=0.0,
-                       help="box-map loss: factor of the soft threat-score term 1 - (I + eps) / (U + eps), per sample; 0 = off")
-        p.add_argument("--box_ts_eps", type=float, default=1.0, help="box-map loss: eps of the soft threat score (>= 0)")
+        add_box_args(p)
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--pretrained_path", type=str, default="")
         p.add_argument("--output_img_freq", type=int, default=500)
