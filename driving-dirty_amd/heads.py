@@ -7,13 +7,9 @@ intermediates stay NHWC.
   SpatialMapFn       reference SpatialMappingCNN.forward          spatial_bb/components.py:28-77
   MergeFn            reference RoadMapBoxesMergingCNN / BoxesMergingCNN.forward   spatial_bb/components.py:141-170, 95-119
 """
-import ctypes as C
-
-import os
-
 import torch
 
-from . import _lib, ops
+from . import ops
 from ._lib import call, size
 from .gconv import EPI_BIAS, EPI_BIAS_RELU, Layer, View, add, copy_channels, view_to_nhwc4
 from . import gconv as gconv_mod
@@ -80,11 +76,7 @@ class DecoderConvStack(torch.autograd.Function):
 
     @staticmethod
     def _wino_desc(a1):
-        b, h, w, c = a1.shape
-        if c != 32 or h < 4 or w < 4:
-            return None
-        d = ops.conv_desc(b, h, w, 32, 1)
-        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
+        return ops.wino2_desc(*a1.shape[:3])      # a1 is this node's own [B, dh, dw, 32]
 
     @staticmethod
     def _as_conv(w):
@@ -180,11 +172,7 @@ class SpatialMapFn(torch.autograd.Function):
     @staticmethod
     def _wino_desc(mosaic):
         """The c2-layer descriptor under which the Winograd kernels take out_conv on this mosaic, or None."""
-        b, mh, mw, c = mosaic.shape
-        if c != 32 or not mosaic.is_contiguous() or mh < 4 or mw < 4:
-            return None
-        d = ops.conv_desc(b, mh, mw, 32, 1)
-        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
+        return ops.wino2_desc(*mosaic.shape[:3]) if mosaic.shape[3] == 32 and mosaic.is_contiguous() else None
 
     @staticmethod
     def forward(ctx, views, *params):
@@ -312,11 +300,7 @@ class MergeFn(torch.autograd.Function):
     @staticmethod
     def _rm2_wino_desc(b, rh, rw):
         """The c2-layer descriptor of the 9 b phase images of rm_conv_2's rh x rw input, or None when the Winograd kernels do not take them."""
-        ph, pw = (rh + 2) // 3, (rw + 2) // 3
-        if ph < 4 or pw < 4:
-            return None
-        d = ops.conv_desc(9 * b, ph, pw, 32, 1)
-        return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
+        return ops.wino2_desc(9 * b, (rh + 2) // 3, (rw + 2) // 3)
 
     @staticmethod
     def _dense_from_phase3(p, oh, ow):

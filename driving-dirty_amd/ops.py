@@ -627,6 +627,15 @@ def conv_wino_wgrad(x, dy, desc):
     return _wino_wgrad("dd_conv_wino", x, dy, desc)
 
 
+def wino2_desc(batch, h, w):
+    """The c2-layer descriptor under which the F(2x2,3x3) Winograd kernels (dd_conv_wino2_*) take a 32 -> 32, k3, padding-1 convolution of
+    ``batch`` NHWC images of h x w, or None where they do not (h, w >= 4 and dd_conv_wino2_packed_floats answers a size)."""
+    if h < 4 or w < 4:
+        return None
+    d = conv_desc(batch, h, w, 32, 1)
+    return d if _lib.lib().dd_conv_wino2_packed_floats(C.byref(d)) > 0 else None
+
+
 def conv_wino2_pack(weight, desc, kind):
     return _wino_pack("dd_conv_wino2", weight, desc, kind)
 

@@ -1,7 +1,9 @@
 """The calls that cross the C ABI during a few tiny training steps, against the list recorded before the Python side of the boundary
 was rewritten (tests/golden/abi_call_trace.json, written by tools/record_abi_call_trace.py: the steps, the recorder and the format
 live there).  Same symbols, same order, same scalars and descriptors, pointers where pointers were, NULL where NULL was: the same
-launches reach the library."""
+launches reach the library.  Seven steps: the roadmap, autoencoder (bf16 and fp32) and box-head steps on their default kernels, the box
+head with split products, BoxesMergingCNN alone, and the box-head step with every A/B switch of gconv / heads off (recorded before
+gconv.Layer's weight addressing moved into one derivation)."""
 import importlib.util
 import json
 import os

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """ss_conv's data gradient (csrc/ssconv.hip) against torch's at the box head's full size, with timings (diagnostic).
-DD_SSCONV_DGRAD=0 times the seven phase launches of the generic engine instead."""
+--generic times the seven phase launches of the generic engine instead (gconv.SSCONV_DGRAD = False)."""
+import argparse
 import os
 import sys
 
@@ -8,11 +9,16 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from driving_dirty_amd import gconv  # noqa: E402
 from driving_dirty_amd.gconv import Layer, View  # noqa: E402
 from tools.bench_gconv import timeit  # noqa: E402
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--generic", action="store_true", help="the data gradient by seven phase launches of the generic engine")
+    if ap.parse_args().generic:
+        gconv.SSCONV_DGRAD = False
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     L = Layer(32, 32, (1, 24), stride=(1, 7))

@@ -10,7 +10,10 @@ the Python side of the boundary has to keep; the test replays STEPS on the code 
 
 STEPS (the smallest models of the suite): RoadMapBCE in fp32 and the bf16 BasicAE on 16 x 22-pixel views at batch 3, two
 TrainStep calls each (the first holds the lazy packing and workspace queries, the second is the steady step), and one TrainStep
-call of BBSpatialRoadMap at the reference's view size, batch 2, frozen encoder, in exact fp32 and once more with split products."""
+call of BBSpatialRoadMap at the reference's view size, batch 2, frozen encoder, in exact fp32 and once more with split products.
+Then the paths those leave out: the fp32 BasicAE at the same tiny size (the decoder's narrow path: dc3 by four phase launches, dc4 on
+the generic engine), BoxesMergingCNN alone at batch 1 (the k8 d8 / k6 d6 output_padding layers, forward and backward), and the
+BBSpatialRoadMap step at batch 1 with every A/B switch of gconv and heads off (each layer's fallback on the generic engine)."""
 import argparse
 import ctypes
 import json
@@ -96,7 +99,7 @@ def autoencoder_bf16(dev):
     _train(ae, [synth.camera_batch(3, 16, 22, seed=31 + s).to(dev) for s in range(2)], lr=1e-3, big_numel=4096)
 
 
-def bbox_spatial(dev, precision=None):
+def bbox_spatial(dev, precision=None, batch=2):
     from driving_dirty_amd.autoencoder import BasicAE
     from driving_dirty_amd.spatial import BBSpatialRoadMap
     ae = BasicAE(Namespace(hidden_dim=16, latent_dim=8))
@@ -105,10 +108,10 @@ def bbox_spatial(dev, precision=None):
     model = model.to(dev)
     if precision is not None:
         model.box_merge.precision = precision             # the documented mode switch (hparams.precision sets the same attribute)
-    views, road = synth.camera_batch(2, seed=17).to(dev), synth.road_maps(2, seed=17).to(dev)
-    tgt = (synth.hash_uniform((2, 800, 800), synth.key_salt("bbt"), 0.0, 1.0) < 0.02).float().to(dev)
+    views, road = synth.camera_batch(batch, seed=17).to(dev), synth.road_maps(batch, seed=17).to(dev)
+    tgt = (synth.hash_uniform((batch, 800, 800), synth.key_salt("bbt"), 0.0, 1.0) < 0.02).float().to(dev)
     np.random.seed(9)
-    _train(model, [(tuple(views), tuple({"bb_map": tgt[i]} for i in range(2)), tuple(road))], lr=1e-3)
+    _train(model, [(tuple(views), tuple({"bb_map": tgt[i]} for i in range(batch)), tuple(road))], lr=1e-3)
 
 
 def bbox_split_products(dev):
@@ -117,7 +120,45 @@ def bbox_split_products(dev):
     bbox_spatial(dev, precision="fp32x3")
 
 
-STEPS = (roadmap_fp32, autoencoder_bf16, bbox_spatial, bbox_split_products)
+def autoencoder_fp32(dev):
+    """The fp32 BasicAE at autoencoder_bf16's sizes: the decoder's narrow path (dc3 by four phase launches, dc4 on the generic engine)."""
+    from driving_dirty_amd.autoencoder import BasicAE
+    ae = BasicAE(Namespace(learning_rate=1e-3, output_img_freq=10 ** 9, hidden_dim=16, latent_dim=8, input_height=16, input_width=132,
+                           output_height=16, output_width=22))
+    synth.fill_module(ae, seed=31)
+    ae = ae.to(dev)
+    np.random.seed(7)
+    _train(ae, [synth.camera_batch(3, 16, 22, seed=31 + s).to(dev) for s in range(2)], lr=1e-3, big_numel=4096)
+
+
+def box_merge_plain(dev):
+    """BoxesMergingCNN alone, forward + backward, batch 1: the k8 d8 / k6 d6 output_padding up-convs."""
+    from driving_dirty_amd.spatial import BoxesMergingCNN
+    bm = synth.fill_module(BoxesMergingCNN(), seed=7).to(dev)
+    ssr = synth.hash_uniform((1, 32, 128, 918), synth.key_salt("ssr"), 0.0, 1.0).to(dev).requires_grad_(True)
+    space = synth.hash_uniform((1, 32, 256, 256), synth.key_salt("space"), 0.0, 1.0).to(dev).requires_grad_(True)
+    pred = bm(ssr, space)
+    (pred * synth.hash_uniform(tuple(pred.shape), synth.key_salt("sp_wy")).to(dev)).sum().backward()
+    torch.cuda.synchronize()
+
+
+def bbox_generic_engine(dev):
+    """The bbox_spatial step at batch 1 with every A/B switch off: phased data gradients, the four-phase k2 s2 weight gradient, the
+    64-channel chunk loop (cin = 96), the role-swapped and flipped weight gradients, the six strip convs one by one."""
+    from driving_dirty_amd import gconv, heads
+    switches = [(gconv, n) for n in ("DCONV", "K2S2_WGRAD", "SSCONV_FWD", "SSCONV_DGRAD", "STRIP6")] + \
+               [(heads, n) for n in ("WINO_OUT", "WINO_DC2", "WINO_RM2")]
+    saved = [getattr(m, n) for m, n in switches]
+    try:
+        for m, n in switches:
+            setattr(m, n, False)
+        bbox_spatial(dev, batch=1)
+    finally:
+        for (m, n), v in zip(switches, saved):
+            setattr(m, n, v)
+
+
+STEPS = (roadmap_fp32, autoencoder_bf16, bbox_spatial, bbox_split_products, autoencoder_fp32, box_merge_plain, bbox_generic_engine)
 
 
 def record(dev=None):
