@@ -23,13 +23,14 @@ from . import ops
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 from .roadmap import CalibratedThreshold, eval_no_grad, predict_map, prediction_threshold, road_map_scores
-from .spatial import (RoadMapBoxesMergingCNN, SpatialMappingCNN, add_box_args, bb_coord_to_map, box_loss_config, boxes_from_map,
-                      decoded_box_ats, mean_logs, per_sample_inputs, require_bounding_boxes)
+from .spatial import (HALF_UNLESS_CALIBRATED, ONE_UNLESS_CONFIGURED, CalibratedBoxThreshold, RoadMapBoxesMergingCNN, SpatialMappingCNN,
+                      add_box_args, bb_coord_to_map, box_decode_point, box_loss_config, boxes_from_map, decoded_box_ats, mean_logs,
+                      per_sample_inputs, require_bounding_boxes)
 
 Prediction = namedtuple("Prediction", ("road_map", "boxes"))      # torch.bool [B,800,800], tuple of B tensors [n_i,2,4]
 
 
-class JointRoadMapBBox(CalibratedThreshold, LightningModule):
+class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningModule):
     box_loss = None      # spatial.box_loss_config(hparams): None = BCE on probabilities, as the reference's box model
     box_rm_input = "target"      # the road map the TRAINING step's box branch reads: "target" (ground truth) | "predicted" (the head's own)
 
@@ -51,6 +52,7 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
         self.box_rm_input = hparam(hparams, "box_rm_input", "target")
         if self.box_rm_input not in ("target", "predicted"):
             raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")
+        self._check_box_decode()
 
     # ------------------------------------------------------------------------------------------------ the parts of one pass
     def _features(self, x):
@@ -100,13 +102,18 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
         return self._road_logits(pooled), boxes
 
     # ------------------------------------------------------------------------------------------------ prediction
-    def predict(self, x, threshold=None, box_threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+    def predict(self, x, threshold=None, box_threshold=HALF_UNLESS_CALIBRATED, min_pixels=ONE_UNLESS_CONFIGURED, max_boxes=256, fit="extent",
+                pad_px=0.5, split_px=0, grow_iters=None):
         """What the task asks for, from the six cameras alone: ``Prediction(road_map, boxes)``, torch.bool [B,800,800] and a tuple of
         B tensors [n_i,2,4].  One encoder pass under ``no_grad`` in ``eval()`` mode (every submodule's mode is put back): the road
         map from ``ops.linear_sigmoid_gt`` at ``threshold`` (None: the calibrated ``rm_threshold``, else 0.5), that map into the box
-        branch, the box map at ``box_threshold`` through ``boxes_from_map``.  ``x``: whatever ``forward`` takes.  The same kernels on
-        the same inputs as ``predict_road_map(x)`` followed by ``predict_boxes(x, masks)``, minus the second encoder conv pass."""
+        branch, the box map at ``box_threshold`` through ``boxes_from_map``.  ``box_threshold`` left out (or None): the calibrated
+        ``box_threshold`` where there is one, else 0.5; ``min_pixels`` left out (or None): ``hparams.box_min_pixels``, else 1; a value the
+        caller gives wins, 0.5 and 1 included (``spatial.box_decode_point``; the two defaults show what they fall back to).  ``x``:
+        whatever ``forward`` takes.  The same kernels on the same inputs as ``predict_road_map(x)`` followed by
+        ``predict_boxes(x, masks)``, minus the second encoder conv pass."""
         tau = prediction_threshold(self, threshold)
+        box_threshold, min_pixels = box_decode_point(self.hparams, box_threshold, min_pixels)
         with eval_no_grad(self):
             feat, pooled, space_rep = self._features(x)
             z = self.ae.encoder._tail(pooled, (None, None))
@@ -115,11 +122,13 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
             boxes = boxes_from_map(probs, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
         return Prediction(road, boxes)
 
-    def predict_boxes(self, x, rm=None, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+    def predict_boxes(self, x, rm=None, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
         """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4].  ``rm=None``: camera-only,
-        the boxes of ``predict`` (the head's own road map at its calibrated threshold); a given ``rm`` is used as it is."""
+        the boxes of ``predict`` (the head's own road map at its calibrated threshold); a given ``rm`` is used as it is.
+        ``threshold=None`` / ``min_pixels=None``: the calibrated ``box_threshold``, else 0.5 / ``hparams.box_min_pixels``, else 1."""
         if rm is None:
             return self.predict(x, None, threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters).boxes
+        threshold, min_pixels = box_decode_point(self.hparams, threshold, min_pixels)
         with torch.no_grad():
             return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
@@ -129,20 +138,37 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
         return predict_map(self, lambda: self.ae.encoder.forward_nhwc4(ops.wide_image(views)), threshold)
 
     # ------------------------------------------------------------------------------------------------ the steps
+    @staticmethod
+    def _step_inputs(sample, road_image):
+        """A batch's views and road masks -> (x, rm, target_rm, per_sample).  ``per_sample``: the collate's tuples are read where they
+        lie (roadmap_bce_v2.py:87 / spatial_w_rm.py:100-105 without the stacks; ``target_rm`` is None then); else a stacked tensor of
+        views, rm [b,1,800,800] fp32 and target_rm [b,800,800]."""
+        per_sample = (per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image)
+                      and len(road_image) <= ops.PTR_TABLE_MAX)
+        if per_sample:
+            return tuple(sample), tuple(road_image), None, True
+        sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
+        target_rm = torch.stack(tuple(road_image), dim=0).float()
+        return sample, target_rm.unsqueeze(1), target_rm, False
+
+    def _camera_only_box_map(self, feat, space_rep, values, logits=False):
+        """The box map [B,800,800] as ``predict`` computes it: the box branch fed the road-map head's own map (``_own_road_masks`` of
+        ``values`` at ``rm_threshold``, else 0.5), contiguous."""
+        return self._box_branch(feat, space_rep, self._own_road_masks(values, self._own_tau(), logits)).contiguous()
+
+    def _box_sweep_of(self, batch):
+        sample, target, road_image = batch
+        require_bounding_boxes(target)
+        feat, pooled, space_rep = self._features(self._step_inputs(sample, road_image)[0])
+        return self._with_box_sweep({}, self._camera_only_box_map(feat, space_rep, self._road_logits(pooled), logits=True), target)
+
     def _run_step(self, batch, own_rm, want_probs):
         """One pass over a batch -> a dict: both losses (``loss_rm``, ``loss_bb``, the class-balanced loss's ``parts`` or None), the
         tensors validation scores (``logits``, ``boxes``, ``target_bb`` [b,800,800], ``probs`` when ``want_probs``) and what a second
         box-branch call needs (``feat``, ``space_rep``).  ``own_rm``: the box branch reads the head's own map instead of the batch's."""
         sample, target, road_image = batch
-        per_sample = (per_sample_inputs(sample, road_image) and all(t.numel() % 4 == 0 for t in road_image)
-                      and len(road_image) <= ops.PTR_TABLE_MAX)
-        if per_sample:
-            # roadmap_bce_v2.py:87 / spatial_w_rm.py:100-105 without the stacks: views and masks are read where the collate left them
-            sample, rm, dev = tuple(sample), tuple(road_image), sample[0].device
-        else:
-            sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
-            target_rm = torch.stack(tuple(road_image), dim=0).float()
-            rm, dev = target_rm.unsqueeze(1), sample.device
+        sample, rm, target_rm, per_sample = self._step_inputs(sample, road_image)
+        dev = sample[0].device if per_sample else sample.device
         b = len(road_image)
         target_bb = bb_coord_to_map(target, dev).to(dev).float()
         feat, pooled, space_rep = self._features(sample)
@@ -188,7 +214,11 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
         ``RoadMapBCE`` reports them, ``ts_hist`` under ``hparams.calibrate_threshold``.  Under ``hparams.box_metrics`` also
         ``val_ats_gt_rm`` (boxes decoded from the box map computed WITH the ground-truth road map), ``val_ats`` (the honest one: a
         second box-branch call fed the head's own map of this pass, at ``rm_threshold`` or 0.5) and ``val_box_ts`` (the rounded
-        map-level threat score of that camera-only box map)."""
+        map-level threat score of that camera-only box map); both decode at the calibrated ``box_threshold`` once there is one.  Under
+        ``hparams.calibrate_box_threshold`` also ``box_ats_sweep``: that same camera-only box map, the one ``predict`` decodes, decoded and
+        scored at every threshold of the grid.  With both calibrations on, an epoch's sweep is made of maps computed with the
+        ``rm_threshold`` found at the end of the PREVIOUS epoch (0.5 in the first): the two operating points are not iterated to a joint
+        optimum; the box threshold found is the best one for the road map the model had during that epoch."""
         sample, target, road_image = batch
         s = self._run_step(batch, False, True)
         out = {"val_loss": s["loss_rm"] + s["loss_bb"], "val_roadmap_loss": s["loss_rm"], "val_bbox_loss": s["loss_bb"]}
@@ -197,13 +227,17 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
         target_rm = torch.stack(tuple(road_image), dim=0).float()
         out.update(road_map_scores(target_rm, s["probs"]))
         self._with_ts_hist(out, s["probs"], target_rm)
-        if hparam(self.hparams, "box_metrics", False):
+        box_metrics, sweep = hparam(self.hparams, "box_metrics", False), self._wants_box_sweep()
+        if box_metrics or sweep:
             with torch.no_grad():
                 require_bounding_boxes(target)
-                out["val_ats_gt_rm"] = decoded_box_ats(self.hparams, s["boxes"].detach().contiguous(), target)
-                own = self._box_branch(s["feat"], s["space_rep"], self._own_road_masks(s["probs"], self._own_tau())).contiguous()
-                out["val_ats"] = decoded_box_ats(self.hparams, own, target)
-                out["val_box_ts"] = ops.threat_score(s["target_bb"].contiguous(), own, round_b=True)
+                own = self._camera_only_box_map(s["feat"], s["space_rep"], s["probs"])      # once, for whichever asks
+                if box_metrics:
+                    out["val_ats_gt_rm"] = decoded_box_ats(self.hparams, s["boxes"].detach().contiguous(), target)
+                    out["val_ats"] = decoded_box_ats(self.hparams, own, target)
+                    out["val_box_ts"] = ops.threat_score(s["target_bb"].contiguous(), own, round_b=True)
+                if sweep:
+                    self._with_box_sweep(out, own, target)
         return out
 
     def validation_epoch_end(self, outputs):
@@ -213,6 +247,8 @@ class JointRoadMapBBox(CalibratedThreshold, LightningModule):
                 "val_ats", "val_box_ts")
         logs = mean_logs(outputs, keys)
         self._calibrate(outputs, logs)
+        if self._wants_box_sweep():
+            self._calibrate_boxes(outputs, logs)      # sets box_threshold (spatial.CalibratedBoxThreshold)
         return {"val_loss": logs["avg_val_loss"], "log": logs}
 
     def configure_optimizers(self):

@@ -14,6 +14,7 @@ from . import gconv, ops
 from .autoencoder import BasicAE
 from .heads import MergeFn, SpatialMapFn, _ORDER, as_nhwc, road_map_taps
 from .lightning import LightningModule, hparam, pretrained_ae
+from .roadmap import eval_no_grad
 
 
 def _gpu(t, who):
@@ -167,16 +168,17 @@ def compute_ats_bounding_boxes(boxes1, boxes2):
     return ops.ats_bounding_boxes([boxes1], [boxes2])[0]
 
 
-def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+def boxes_from_map(maps, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None, warn_overflow=True):
     """[b,H,W] occupancy maps -> tuple of b [n_i,2,4] box tensors (``ops.component_boxes`` cut to each sample's count).
     ``fit="oriented"`` fits each component along its principal axis instead of taking its axis-aligned extent.  ``split_px > 0`` first
     splits blobs joined through a neck narrower than ``2 * split_px + 1`` pixels (``ops.split_components``; ``grow_iters=None`` =
-    ``2 * split_px``)."""
+    ``2 * split_px``).  ``warn_overflow=False``: a sample with more than ``max_boxes`` components is cut there without a warning (the
+    threshold sweep: at a low threshold on a noisy map that is the normal case)."""
     boxes, counts = ops.component_boxes(maps.detach().float().contiguous(), threshold, min_pixels, max_boxes, fit=fit, pad_px=pad_px,
                                         split_px=split_px, grow_iters=grow_iters)
     counts = counts.tolist()
     over = [i for i, c in enumerate(counts) if c > max_boxes]
-    if over:
+    if over and warn_overflow:
         warnings.warn(f"boxes_from_map: samples {over} have more than max_boxes={max_boxes} components "
                       f"({[counts[i] for i in over]}); only the first {max_boxes} are returned")
     return tuple(boxes[i, :min(c, max_boxes)] for i, c in enumerate(counts))
@@ -189,12 +191,167 @@ def require_bounding_boxes(targets):
         raise KeyError(f"box_metrics needs a 'bounding_box' tensor in every target (missing in samples {missing})")
 
 
+BOX_THRESHOLD_GRID = tuple(k / 16 for k in range(1, 16))      # the default candidates of the box threshold: exact in fp32, 0.5 among them
+
+
+def box_threshold_grid(hparams):
+    """``hparams.box_threshold_grid`` as a tuple of floats (default ``BOX_THRESHOLD_GRID``): the thresholds ``box_ats_sweep`` decodes at.
+    Strictly increasing numbers inside (0, 1), at least one; anything else raises ValueError (when the module is built)."""
+    grid = hparam(hparams, "box_threshold_grid", None)
+    if grid is None:
+        return BOX_THRESHOLD_GRID
+    if not isinstance(grid, (list, tuple)) or len(grid) == 0:
+        raise ValueError(f"box_threshold_grid must be a non-empty list of thresholds, got {grid!r}")
+    if any(isinstance(t, bool) or not isinstance(t, (int, float)) or not 0.0 < t < 1.0 for t in grid):
+        raise ValueError(f"box_threshold_grid: every threshold must be a number inside (0, 1), got {grid!r}")
+    grid = tuple(float(t) for t in grid)
+    if any(a >= b for a, b in zip(grid, grid[1:])):
+        raise ValueError(f"box_threshold_grid must be strictly increasing, got {grid!r}")
+    return grid
+
+
+def box_min_pixels(hparams):
+    """``hparams.box_min_pixels``: the smallest component the decode keeps (speckle removal), a whole number >= 1, default 1."""
+    n = hparam(hparams, "box_min_pixels", None)
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"box_min_pixels must be a whole number >= 1, got {n!r}")
+    return n
+
+
+class _ShownDefault:
+    """A default that a signature shows as the value it falls back to (``box_threshold=0.5``: what a call without the argument gets while
+    nothing is calibrated) and that is told from the same number GIVEN by a caller by its type: an explicit 0.5 is a plain float and
+    stays 0.5.  ``JointRoadMapBBox.predict``'s signature is pinned with these values; everywhere else "not given" is None."""
+    __slots__ = ()
+
+
+class _ShownFloat(_ShownDefault, float):
+    __slots__ = ()
+
+
+class _ShownInt(_ShownDefault, int):
+    __slots__ = ()
+
+
+HALF_UNLESS_CALIBRATED = _ShownFloat(0.5)      # JointRoadMapBBox.predict's box_threshold default
+ONE_UNLESS_CONFIGURED = _ShownInt(1)           # ... and its min_pixels default
+
+
+def box_decode_point(hparams, threshold=None, min_pixels=None):
+    """The operating point of a box decode -> (threshold, min_pixels).  THE ORDER, stated once: an explicit argument wins; an argument left
+    out (None, or one of the two shown defaults above) means the calibrated ``hparams.box_threshold`` where there is one, else 0.5, and
+    ``hparams.box_min_pixels``, else 1."""
+    if threshold is None or isinstance(threshold, _ShownDefault):
+        threshold = hparam(hparams, "box_threshold", None)
+    if min_pixels is None or isinstance(min_pixels, _ShownDefault):
+        min_pixels = hparam(hparams, "box_min_pixels", None)
+    return 0.5 if threshold is None else float(threshold), 1 if min_pixels is None else int(min_pixels)
+
+
+def _decode_args(hparams):
+    return dict(fit=hparam(hparams, "box_fit", "extent"), pad_px=hparam(hparams, "box_pad_px", 0.5),
+                split_px=hparam(hparams, "box_split_px", 0), grow_iters=hparam(hparams, "box_grow_iters", None))
+
+
 def decoded_box_ats(hparams, pred_maps, targets):
     """The task's own unit for one batch: boxes extracted from the predicted maps [b,800,800] as ``hparams`` ask (``box_fit``,
-    ``box_pad_px``, ``box_split_px``, ``box_grow_iters``) against the targets' boxes -> the batch's mean average threat score, 0-dim."""
-    fitted = boxes_from_map(pred_maps, fit=hparam(hparams, "box_fit", "extent"), pad_px=hparam(hparams, "box_pad_px", 0.5),
-                            split_px=hparam(hparams, "box_split_px", 0), grow_iters=hparam(hparams, "box_grow_iters", None))
+    ``box_pad_px``, ``box_split_px``, ``box_grow_iters``, ``box_min_pixels``; cut at the calibrated ``box_threshold`` when one is set,
+    else at 0.5) against the targets' boxes -> the batch's mean average threat score, 0-dim."""
+    threshold, min_pixels = box_decode_point(hparams)
+    fitted = boxes_from_map(pred_maps, threshold, min_pixels, **_decode_args(hparams))
     return ops.ats_bounding_boxes(fitted, [t["bounding_box"] for t in targets]).mean()
+
+
+def box_ats_sweep(hparams, pred_maps, targets, thresholds):
+    """``decoded_box_ats`` at every threshold of ``thresholds`` -> (sums fp64 [K] on the maps' device, the sample count b): sums[k] is the
+    SUM over the batch's samples of the per-sample average threat score of the map decoded at thresholds[k], so sums[k] / b is
+    ``decoded_box_ats`` with ``hparams.box_threshold = thresholds[k]``.  The same kernels with the same arguments and the same rule (a
+    pixel is in where ``map > t``, strictly, t rounded to fp32), one decode per threshold: the box score is no function of per-pixel
+    counts, so no histogram holds it (the road map's does, ``ops.ts_histogram``).  Sums, not means: batches of different sizes add up
+    to the data set's mean.  A threshold at which a sample has more than 256 components scores what its first 256 boxes score, quietly."""
+    _, min_pixels = box_decode_point(hparams)
+    maps = pred_maps.detach().float().contiguous()
+    boxes = [t["bounding_box"] for t in targets]
+    sums = [ops.ats_bounding_boxes(boxes_from_map(maps, t, min_pixels, warn_overflow=False, **_decode_args(hparams)), boxes).double().sum()
+            for t in thresholds]
+    return torch.stack(sums), len(boxes)
+
+
+def best_box_threshold(sums, count, thresholds):
+    """Summed sweeps -> (k, curve): curve[k] = sums[k] / count in fp64 (the data set's mean score at thresholds[k]; on the CPU), k its
+    maximum.  Ties go to the threshold nearest 0.5, then to the lower one, as ``ops.ts_curve`` breaks them.  Plain torch on K numbers."""
+    count = int(count)
+    if count <= 0:
+        raise ValueError(f"best_box_threshold: no samples were swept (count = {count})")
+    sums = torch.as_tensor(sums).detach().to("cpu", torch.float64).reshape(-1)
+    if sums.numel() != len(thresholds) or sums.numel() == 0:
+        raise ValueError(f"best_box_threshold: {sums.numel()} sums for {len(thresholds)} thresholds")
+    curve = sums / count
+    ties = [k for k in range(curve.numel()) if curve[k] == curve.max()]
+    if not ties:
+        raise ValueError(f"best_box_threshold: the curve has no maximum ({curve.tolist()})")
+    return min(ties, key=lambda k: (abs(float(thresholds[k]) - 0.5), k)), curve
+
+
+class CalibratedBoxThreshold:
+    """What a module with a box head needs to calibrate the threshold its map is decoded at on validation data
+    (hparams.calibrate_box_threshold) and to carry it: the ``box_threshold`` property, the per-batch sweep and the epoch's argmax.  Shared
+    by ``BBSpatialRoadMap`` and the joint model; the sibling of ``roadmap.CalibratedThreshold``.  Per process, like ``rm_threshold``:
+    nothing is reduced across data-parallel ranks."""
+
+    BOX_SWEEP = "box_ats_sweep"      # validation_step's key: fp64 [K + 1], the sweep's K sums and then the sample count
+
+    @property
+    def box_threshold(self):
+        """The threshold ``validation_epoch_end`` / ``calibrate_boxes`` calibrated, a plain float, or None.  Kept in ``hparams`` -- not a
+        buffer, not in the state_dict -- so ``save_checkpoint`` / ``load_from_checkpoint`` carry it, as they do ``rm_threshold``."""
+        return hparam(self.hparams, "box_threshold", None)
+
+    @box_threshold.setter
+    def box_threshold(self, value):
+        self.hparams.box_threshold = None if value is None else float(value)
+
+    def _check_box_decode(self):
+        """A bad ``box_threshold_grid`` or ``box_min_pixels`` fails when the module is built, not in the first validation step."""
+        box_threshold_grid(self.hparams)
+        box_min_pixels(self.hparams)
+
+    def _wants_box_sweep(self):
+        return bool(hparam(getattr(self, "hparams", None), "calibrate_box_threshold", False))      # off for a module without hparams
+
+    def _with_box_sweep(self, out, pred_maps, targets):
+        """``out[BOX_SWEEP]`` <- this batch's sweep of ``pred_maps`` [b,800,800], whether or not the hparams ask for one."""
+        sums, count = box_ats_sweep(self.hparams, pred_maps, targets, box_threshold_grid(self.hparams))
+        out[self.BOX_SWEEP] = torch.cat([sums, sums.new_tensor([count])])
+        return out
+
+    def _calibrate_boxes(self, outputs, logs):
+        """``box_threshold`` <- the grid's threshold with the best mean score of the DATA SET (the batches' summed sweeps over the number
+        of samples: a ragged last batch counts as what it is; the ``avg_*`` values are means of batch means), and its figures into
+        ``logs``.  -> the curve."""
+        grid = box_threshold_grid(self.hparams)
+        total = torch.stack([x[self.BOX_SWEEP] for x in outputs]).sum(0).cpu()
+        best, curve = best_box_threshold(total[:-1], round(float(total[-1])), grid)
+        self.box_threshold = grid[best]
+        logs.update(best_box_threshold=self.box_threshold, best_val_ats=float(curve[best]))
+        if 0.5 in grid:
+            logs["val_ats_at_half"] = float(curve[grid.index(0.5)])
+        return curve
+
+    def _box_sweep_of(self, batch):
+        """One validation batch -> its sweep as ``{BOX_SWEEP: ...}``: the forward pass and the sweep, nothing else (each module's own)."""
+        raise NotImplementedError
+
+    def calibrate_boxes(self, batches):
+        """Calibrate a module that was trained without ``--calibrate_box_threshold``: the forward pass and the sweep over an iterable of
+        validation batches, in ``eval()`` mode under ``no_grad`` (every submodule's mode is put back), then what
+        ``validation_epoch_end`` does with an epoch's sweeps.  Sets ``box_threshold``; -> (threshold, curve fp64 [K])."""
+        with eval_no_grad(self):
+            outputs = [self._box_sweep_of(batch) for batch in batches]
+        curve = self._calibrate_boxes(outputs, {})
+        return self.box_threshold, curve
 
 
 def mean_logs(outputs, keys):
@@ -224,9 +381,14 @@ def add_box_args(p):
     p.add_argument("--box_ts_weight", type=float, default=0.0,
                    help="box-map loss: factor of the soft threat-score term 1 - (I + eps) / (U + eps), per sample; 0 = off")
     p.add_argument("--box_ts_eps", type=float, default=1.0, help="box-map loss: eps of the soft threat score (>= 0)")
+    p.add_argument("--calibrate_box_threshold", action="store_true",
+                   help="validation also decodes the predicted box map at every threshold of a grid (1/16 .. 15/16) and keeps the one with "
+                        "the best data-set average threat score (box_threshold): val_ats and the predictions then decode there")
+    p.add_argument("--box_min_pixels", type=int, default=1,
+                   help="box decoding (validation, the threshold sweep, predictions): components of fewer pixels are dropped; >= 1")
 
 
-class BBSpatialRoadMap(LightningModule):
+class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
     """spatial_w_rm.py:25-167.  ``bb_coord_to_map`` (the per-sample PIL polygon loop of src/utils/bb_to_img.py) runs
     as one launch of the HIP rasteriser over the batch's ``'bounding_box'`` tensors; batches may instead carry a
     pre-rasterised ``'bb_map'`` [800,800] tensor in each target dict, or name their own ``hparams.rasterizer``."""
@@ -254,6 +416,7 @@ class BBSpatialRoadMap(LightningModule):
         if hparam(hparams, "precision", None) is not None:
             self.box_merge.precision = "fp32x3" if precision == "fp32x3" else "fp32"
         self.box_loss = box_loss_config(hparams)      # None: the reference's loss; a bad value fails here, not in the first step
+        self._check_box_decode()
 
     def wide_stitch_six_images(self, x):
         return ops.stitch6(x.contiguous(), want_nhwc4=False, want_nchw=True)[1]
@@ -274,21 +437,32 @@ class BBSpatialRoadMap(LightningModule):
     def _run_step(self, batch, batch_idx, step_name):
         return self._run_step_parts(batch, batch_idx, step_name)[:3]
 
+    @staticmethod
+    def _batch_inputs(sample, road_image):
+        """A batch's views and road maps -> (x, rm) as ``forward`` takes them.  The collate's tuples are read where they lie (pointer
+        tables) when they can be: no torch.stack of the 180 MB of views, no stack + float() of the road masks (spatial_w_rm.py:100-105);
+        else a stacked tensor of views and rm [b,1,800,800] fp32."""
+        if per_sample_inputs(sample, road_image):
+            return tuple(sample), tuple(road_image)
+        sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
+        return sample, torch.stack(tuple(road_image), dim=0).float().unsqueeze(1)
+
+    def _box_sweep_of(self, batch):
+        sample, target, road_image = batch
+        require_bounding_boxes(target)
+        return self._with_box_sweep({}, self(*self._batch_inputs(sample, road_image)), target)
+
     def _run_step_parts(self, batch, batch_idx, step_name):
         """-> (loss, target, prediction, parts): parts is None with the reference's loss, (L_bce, L_ts) with ``box_loss_config``'s."""
         sample, target, road_image = batch
-        if per_sample_inputs(sample, road_image):
-            # the collate's tuples are read where they lie (pointer tables): no torch.stack of the 180 MB of views, no stack +
-            # float() of the road masks (spatial_w_rm.py:100-105)
+        sample, rm = self._batch_inputs(sample, road_image)
+        if isinstance(sample, tuple):
             dev = sample[0].device
             target_bb_img = self.bb_coord_to_map(target, dev).to(dev).float()
-            pred_bb_img = self(tuple(sample), tuple(road_image))
         else:
-            sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
             target_bb_img = self.bb_coord_to_map(target, sample.device).to(sample.device)
             target_bb_img = target_bb_img.float() if sample.dtype == torch.uint8 else target_bb_img.type_as(sample)
-            rm = torch.stack(tuple(road_image), dim=0).float().unsqueeze(1)
-            pred_bb_img = self(sample, rm)
+        pred_bb_img = self(sample, rm)
         batch_size = target_bb_img.size(0)
         target_bb_img = target_bb_img.reshape(batch_size, -1)
         pred_bb_img = pred_bb_img.reshape(batch_size, -1)
@@ -311,15 +485,20 @@ class BBSpatialRoadMap(LightningModule):
             log["bbox_bce"], log["bbox_soft_ts"] = parts
         return {"loss": train_loss, "log": log}
 
-    def predict_boxes(self, x, rm, threshold=0.5, min_pixels=1, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+    def predict_boxes(self, x, rm, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
         """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
-        [n_i,2,4] in the data set's format.  A sample with more than ``max_boxes`` components is cut there, with a warning.
+        [n_i,2,4] in the data set's format.  ``threshold=None``: the calibrated ``box_threshold`` where there is one, else 0.5;
+        ``min_pixels=None``: ``hparams.box_min_pixels``, else 1; an explicit argument wins (``box_decode_point``).  A sample with more
+        than ``max_boxes`` components is cut there, with a warning.
         ``fit="oriented"``: rotated rectangles along each component's principal axis (which end is the front is arbitrary).
         ``split_px > 0``: touching cars joined through a neck are split first (``ops.split_components``)."""
+        threshold, min_pixels = box_decode_point(self.hparams, threshold, min_pixels)
         with torch.no_grad():
             return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
     def validation_step(self, batch, batch_idx):
+        """Under ``hparams.calibrate_box_threshold`` also ``box_ats_sweep``: the predicted map (computed with the batch's road map, as
+        everything this module validates) decoded and scored at every threshold of the grid."""
         val_loss, target_bb_img, pred_bb_img, parts = self._run_step_parts(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss}
         if parts is not None:
@@ -330,12 +509,18 @@ class BBSpatialRoadMap(LightningModule):
                 require_bounding_boxes(batch[1])
                 out["val_ats"] = decoded_box_ats(self.hparams, pred_bb_img.detach().reshape(-1, 800, 800).contiguous(), batch[1])
                 out["val_ts"] = ops.threat_score(target_bb_img.contiguous(), pred_bb_img.detach().contiguous(), round_b=True)
+        if self._wants_box_sweep():
+            with torch.no_grad():
+                require_bounding_boxes(batch[1])
+                self._with_box_sweep(out, pred_bb_img.detach().reshape(-1, 800, 800), batch[1])
         return out
 
     def validation_epoch_end(self, outputs):
         avg_val_loss = torch.stack([x["val_loss"] for x in outputs]).mean()
         logs = {"avg_val_loss": avg_val_loss}
         logs.update(mean_logs(outputs, ("val_ats", "val_ts", "val_bce", "val_soft_ts")))      # present only under hparams.box_metrics / the box-map loss
+        if self._wants_box_sweep():
+            self._calibrate_boxes(outputs, logs)      # sets box_threshold: the next epoch's val_ats and the predictions decode there
         return {"val_loss": avg_val_loss, "log": logs}
 
     def configure_optimizers(self):

@@ -1,10 +1,11 @@
 """Road maps AND boxes from six camera frames alone, with the joint model (``JointRoadMapBBox.predict``), and what the one pass saves.
 
     python tools/predict_joint.py [--ckpt joint.ckpt] [--frames frames.npy] [--scenes 16] [--batch_size 8] [--threshold 0.4]
-                                  [--box_threshold 0.5] [--out preds/] [--timing profiles/joint_predict_timing.json]
+                                  [--box_threshold 0.3] [--out preds/] [--timing profiles/joint_predict_timing.json]
 
-Model: ``--ckpt`` a checkpoint ``JointRoadMapBBox.save_checkpoint`` wrote (its calibrated ``rm_threshold`` is the default operating
-point), else a freshly initialised model at the reference's sizes (hidden 128 / latent 64, seeded).  Input: ``--frames`` a .npy of
+Model: ``--ckpt`` a checkpoint ``JointRoadMapBBox.save_checkpoint`` wrote (its calibrated ``rm_threshold`` and ``box_threshold`` are
+the default operating points of ``--threshold`` and ``--box_threshold``, 0.5 where it has none), else a freshly initialised model at
+the reference's sizes (hidden 128 / latent 64, seeded).  Input: ``--frames`` a .npy of
 decoded camera frames, uint8 [S,6,H,W,3], or of views as ToTensor delivers them, fp32 [S,6,3,H,W]; without it ``--scenes``
 closed-form synthetic scenes (driving_dirty_amd/synth.py).  Printed per batch: the road fraction of the predicted map and the number of
 boxes per scene; with ``--out``, ``road_map_00000.npy`` (bool [800,800]) and ``boxes_00000.npy`` ([n,2,4]) per scene.
@@ -82,7 +83,7 @@ def main():
     ap.add_argument("--latent_dim", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--threshold", type=float, default=None)
-    ap.add_argument("--box_threshold", type=float, default=0.5)
+    ap.add_argument("--box_threshold", type=float, default=None)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=25)
     ap.add_argument("--timing", default="")
@@ -92,13 +93,14 @@ def main():
     dev = torch.device("cuda:0")
     model = load_model(args, dev)
     tau = args.threshold if args.threshold is not None else (model.rm_threshold if model.rm_threshold is not None else 0.5)
+    box_tau = args.box_threshold if args.box_threshold is not None else (model.box_threshold if model.box_threshold is not None else 0.5)
     batches = load_scenes(args, model, dev)
 
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     n, counts, road_px = 0, [], 0
     for x in batches:
-        pred = model.predict(x, tau, args.box_threshold)
+        pred = model.predict(x, tau, box_tau)
         counts += [int(t.shape[0]) for t in pred.boxes]
         road_px += int(pred.road_map.sum())
         print(f"scenes {n} .. {n + len(pred.boxes) - 1}: road fraction {float(pred.road_map.float().mean()):.4f}, "
@@ -117,13 +119,13 @@ def main():
 
     def composition():
         masks = model.predict_road_map(x, tau)
-        return model.predict_boxes(x, tuple(masks), args.box_threshold)
+        return model.predict_boxes(x, tuple(masks), box_tau)
 
     def conv_stack():
         with torch.no_grad():
             return ops.encoder_conv_stack(wide4, enc.c1, enc.c2, enc.c3, 2, enc.rows_per_task)
 
-    paths = {"predict": lambda: model.predict(x, tau, args.box_threshold), "road_map_then_boxes": composition, "encoder_conv_forward": conv_stack}
+    paths = {"predict": lambda: model.predict(x, tau, box_tau), "road_map_then_boxes": composition, "encoder_conv_forward": conv_stack}
     torch.manual_seed(args.seed)      # the dense blocks' dropout is on in eval mode too (components.py:108): the same masks both ways
     one = paths["predict"]()
     torch.manual_seed(args.seed)
@@ -138,7 +140,7 @@ def main():
             ms[k].append(timed_ms(fn))
     result = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "torch": torch.__version__,
               "argv": sys.argv[1:], "hidden_dim": enc.hidden_dim, "latent_dim": enc.latent_dim, "batch": b, "rounds": args.rounds,
-              "warmup": args.warmup, "threshold": tau, "box_threshold": args.box_threshold, "scenes_predicted": n,
+              "warmup": args.warmup, "threshold": tau, "box_threshold": box_tau, "scenes_predicted": n,
               "road_fraction": road_px / (n * 800 * 800), "boxes_per_scene_mean": sum(counts) / max(n, 1), "same_boxes_both_ways": same}
     for k, v in ms.items():
         result[k] = summary(v)
