@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .augment import Augmenter, add_augment_args, current_rank
 from .components import Decoder, Encoder
 from .lightning import LightningModule, hparam
 
@@ -28,6 +29,9 @@ class BasicAE(LightningModule):
         self.decoder = self.init_decoder(self.hidden_dim, self.latent_dim, self.in_channels, self.output_height,
                                          self.output_width)
         self.precision = hparam(hparams, "precision", "fp32")
+        self.augment = Augmenter(hparams, rank=current_rank())      # train-time only; off unless an aug_* hparam is set
+        if self.augment.view_drop > 0:
+            raise ValueError("BasicAE: aug_view_drop > 0 -- the masked-view task already blanks one view of every sample")
 
     @property
     def precision(self):
@@ -94,6 +98,7 @@ class BasicAE(LightningModule):
         exp.add_image(f"{step_name}_target_images", y[:limit][0], step)
 
     def training_step(self, batch, batch_idx):
+        batch = self.augment.apply(batch)
         train_loss = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
@@ -123,4 +128,5 @@ class BasicAE(LightningModule):
         p.add_argument("--link", type=str, default="/scratch/ab8690/DLSP20Dataset/data")
         p.add_argument("--output_img_freq", type=int, default=500)
         p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16"))     # not a reference flag: bf16 mixed precision
+        add_augment_args(p)
         return p

@@ -1,11 +1,12 @@
-"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) with hipcc for gfx950.
+"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension library (``csrc/libdd_augment.so``) with hipcc for gfx950.
 
     python -m driving_dirty_amd.build          # or __graft_entry__.build()
 
 hipcc cross-compiles without a GPU.  The library is built IN-TREE so that it travels with the
 repository snapshot to the GPU box (a JIT cache under ~/.cache would not).  Each source is compiled
 to its own object (in parallel, re-done only when the source or a header is newer) and the objects
-are linked into the one library.
+are linked into the one library.  The extension library (``include/dd_augment.h``: the train-time augmentation) is built the same
+way, with the same flags, from its own sources, and links against the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.
 """
 import os
 import subprocess
@@ -23,6 +24,11 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 EXTRA_FLAGS = {"adam_rankb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 HEADER = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "dd_hotpath.h")      # the C ABI; _lib.py derives its ctypes table from it
 HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "adam_rankb_kernels.inc"), HEADER]
+# the extension library: launch functions that are not part of include/dd_hotpath.h (its set of functions is pinned); augment.py binds it
+AUG_LIB = os.path.join(CSRC, "libdd_augment.so")
+AUG_SOURCES = ["augment.hip"]
+AUG_HEADER = os.path.join(os.path.dirname(HEADER), "dd_augment.h")
+AUG_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, AUG_HEADER]
 
 
 def _obj(src):
@@ -36,8 +42,16 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def needs_build():
+def _main_needs_build():
     return _stale(LIB, [os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
+
+
+def _augment_needs_build():
+    return _stale(AUG_LIB, [os.path.join(CSRC, s) for s in AUG_SOURCES] + AUG_HEADERS)
+
+
+def needs_build():
+    return _main_needs_build() or _augment_needs_build()
 
 
 def build_diag(verbose=True):
@@ -62,9 +76,36 @@ def build_diag(verbose=True):
     return lib
 
 
+def _run(cmd, verbose):
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+def build_augment(force=False, verbose=True):
+    """``csrc/libdd_augment.so`` from AUG_SOURCES: the main library's flags; linked against ``libdd_hotpath.so`` (found beside it at load
+    time, $ORIGIN), which therefore has to exist."""
+    if not force and not _augment_needs_build():
+        return AUG_LIB
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    os.makedirs(OBJ, exist_ok=True)
+    for src in AUG_SOURCES:
+        if force or _stale(_obj(src), [os.path.join(CSRC, src)] + AUG_HEADERS):
+            _run([hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", _obj(src)], verbose)
+    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", AUG_LIB] + [_obj(s) for s in AUG_SOURCES]
+         + ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], verbose)
+    return AUG_LIB
+
+
 def build(force=False, verbose=True):
-    if not force and not needs_build():
-        return LIB
+    """Both libraries, each only when it is stale; returns the main library's path."""
+    if force or _main_needs_build():
+        _build_main(force, verbose)
+    build_augment(force, verbose)
+    return LIB
+
+
+def _build_main(force, verbose):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
     todo = [s for s in SOURCES if force or _stale(_obj(s), [os.path.join(CSRC, s)] + HEADERS)]

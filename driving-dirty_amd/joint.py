@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 from .roadmap import CalibratedThreshold, eval_no_grad, predict_map, prediction_threshold, road_map_scores
@@ -53,6 +54,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         if self.box_rm_input not in ("target", "predicted"):
             raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")
         self._check_box_decode()
+        self.augment = Augmenter(hparams, rank=current_rank())      # train-time only; off unless an aug_* hparam is set
 
     # ------------------------------------------------------------------------------------------------ the parts of one pass
     def _features(self, x):
@@ -201,6 +203,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         then, so the autograd order of the two branches SWAPS: the box head's backward runs first and the two big Linear gradients
         (``forward`` says why they come first by default) finish late in the backward, with little left to hide their reduction
         under in data-parallel training."""
+        batch = self.augment.apply(batch)
         s = self._run_step(batch, self.box_rm_input == "predicted", False)
         log = {}
         if s["parts"] is not None:
@@ -270,4 +273,5 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         p.add_argument("--output_img_freq", type=int, default=500)
         p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "fp32x3"),
                        help="fp32: the reference's arithmetic; fp32x3: the box head's dilated up-convs as six bf16 products per fp32 product")
+        add_augment_args(p)
         return p

@@ -13,6 +13,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import ops
+from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 
@@ -107,6 +108,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         if self.ae.encoder.precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {self.ae.encoder.precision!r}")
         self.fc1 = nn.Linear(self.ae.latent_dim, self.output_dim)
+        self.augment = Augmenter(hparams, rank=current_rank())      # train-time only; off unless an aug_* hparam is set
 
     def wide_stitch_six_images(self, sample):
         """tuple of B [6,3,H,W] -> [B,3,H,6W] (NCHW), views re-ordered.  roadmap_bce_v2.py:53-64."""
@@ -175,6 +177,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         if self.current_epoch >= self.hparams.unfreeze_epoch_no and self.frozen:
             self.frozen = False
             self.ae.unfreeze()
+        batch = self.augment.apply(batch)
         train_loss, _, _, _ = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
@@ -205,6 +208,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         p.add_argument("--output_img_freq", type=int, default=500)
         p.add_argument("--calibrate_threshold", action="store_true",
                        help="validation also finds the threshold with the best data-set threat score (rm_threshold)")
+        add_augment_args(p)
         return p
 
 
@@ -227,6 +231,7 @@ class RoadMap(RoadMapBCE):
         if self.current_epoch >= 30 and self.frozen:          # roadmap_pretrain_ae.py:131
             self.frozen = False
             self.ae.unfreeze()
+        batch = self.augment.apply(batch)
         train_loss, _, _ = self._run_step(batch, batch_idx, step_name="train")
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import gconv, ops
+from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .heads import MergeFn, SpatialMapFn, _ORDER, as_nhwc, road_map_taps
 from .lightning import LightningModule, hparam, pretrained_ae
@@ -417,6 +418,7 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
             self.box_merge.precision = "fp32x3" if precision == "fp32x3" else "fp32"
         self.box_loss = box_loss_config(hparams)      # None: the reference's loss; a bad value fails here, not in the first step
         self._check_box_decode()
+        self.augment = Augmenter(hparams, rank=current_rank())      # train-time only; off unless an aug_* hparam is set
 
     def wide_stitch_six_images(self, x):
         return ops.stitch6(x.contiguous(), want_nhwc4=False, want_nchw=True)[1]
@@ -479,6 +481,7 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
         if self.current_epoch >= self.hparams.unfreeze_epoch_no and self.frozen:
             self.frozen = False
             self.ae.unfreeze()
+        batch = self.augment.apply(batch)      # a mirrored sample's target map is rasterised from its mirrored boxes
         train_loss, _, _, parts = self._run_step_parts(batch, batch_idx, step_name="train")
         log = {"train_loss": train_loss}
         if parts is not None:
@@ -540,4 +543,5 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
         p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16", "fp32x3"),
                        help="fp32: the reference's arithmetic; bf16: encoder conv stack on the bf16 matrix cores; fp32x3: the box head's "
                             "dilated up-convs as six bf16 products per fp32 product (MI355X build only)")
+        add_augment_args(p)
         return p
