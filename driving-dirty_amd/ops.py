@@ -849,17 +849,29 @@ def pool4_relu_bwd_add(dpooled, feat, gfeat):
     return out
 
 
-# Callbacks fired when backward enters its long MFMA-bound stretch (the c2 weight / data gradient kernels, ~4.4 ms
-# at bs = 32 that use a third of the HBM bandwidth): the place to start bandwidth-bound side work such as the
-# optimizer pass of already-finished gradients (optim.HipAdam.overlap_with_backward).
-MFMA_PHASE_HOOKS = []
-# ... and fired again between c2's weight gradient and its data gradient, ~1.2 ms later: the place for work that has to WAIT for
-# something started at the top of the backward (factor mode of ddp.GradSync: the gathered factors of the two big Linear layers).
-MFMA_PHASE2_HOOKS = []
-C2_DGRAD_FIRST = False      # c2's data gradient before its weight gradient (same results; see EncoderConvStack.backward)
+# Observers of the encoder's backward (optim.HipAdam registers itself in overlap_with_backward and leaves in close).  Each has
+#   backward_phase1()  called when backward enters its long MFMA-bound stretch (the c2 weight / data gradient kernels, ~4.4 ms at
+#                      bs = 32 that use a third of the HBM bandwidth): the place to start bandwidth-bound side work such as the
+#                      optimizer pass of already-finished gradients;
+#   backward_phase2()  called between c2's two gradient kernels, ~1.2 ms later: the place for work that has to WAIT for something
+#                      started at the top of the backward (factor mode of ddp.GradSync: the gathered factors of the big Linear layers);
+#   c2_dgrad_first     whether it needs c2's data gradient in front of its weight gradient (same results either way; asked when the
+#                      backward runs, true if any observer says so: see EncoderConvStack.backward).
+# The list is the whole mechanism: which order an observer wants, and what it launches where, is the observer's business.
+BACKWARD_OBSERVERS = []
 
 # c1's weight gradient taken from c2's data gradient inside conv_wino2_fwd<EPI_RELU_BITS_W1> (2-D Winograd path only)
 FUSE_C1_WGRAD = True      # c1's weight gradient inside c2's data gradient (the 2-D Winograd form); tests may switch it off in process
+
+# c2's three kernel families by path: (pack, forward, data gradient, weight gradient).  NAMES, looked up in this module when they are
+# called: bench.py, tools/ and tests replace these functions by assignment on the module (_lib.py's docstring).
+_C2_PATHS = {"wino2": ("conv_wino2_pack", "conv_wino2_fwd_bits", "conv_wino2_dgrad_bits", "conv_wino2_wgrad"),
+             "wino": ("conv_wino_pack", "conv_wino_fwd_bits", "conv_wino_dgrad_bits", "conv_wino_wgrad"),
+             "direct": ("conv_pack", "conv_fwd_bits", "conv_dgrad_bits", "conv_wgrad")}
+
+
+def _c2(path):
+    return [globals()[name] for name in _C2_PATHS[path]]
 
 
 # Test hook: when set to a dict, EncoderConvStack.forward leaves its three ReLU outputs (NHWC) in it, so that a checker can
@@ -900,44 +912,31 @@ class EncoderConvStack(torch.autograd.Function):
         # that overlaps it -- 4 us alone, up to 390 us squeezed between Adam's workgroups) are packed on a side stream
         # while c1's forward runs: five 5-us launches less on the critical path.
         need = ctx.needs_input_grad               # (x4, w1, b1, w2, b2, w3, b3, ...)
+        path = "wino2" if WINOGRAD and WINOGRAD_2D else "wino" if WINOGRAD else "direct"      # c2: F(2x2,3x3), F(2,3) along x, direct
+        c2_pack, c2_fwd_bits, _, _ = _c2(path)
         p1 = conv_pack(w1, d1, PACK_FWD)
         main = torch.cuda.current_stream()
         side = _pack_stream(x4.device)
         side.wait_event(main.record_event())
         with torch.cuda.stream(side):
-            if WINOGRAD and WINOGRAD_2D:
-                p2 = conv_wino2_pack(w2, d2, 0)
-            elif WINOGRAD:
-                p2 = conv_wino_pack(w2, d2, 0)
-            else:
-                p2 = conv_pack(w2, d2, PACK_FWD)
+            p2 = c2_pack(w2, d2, PACK_FWD)
             p3 = conv_pack(w3, d3, PACK_FWD)
             p2d = p3d = torch.empty(0, device=x4.device)
             if need[1] or need[2] or need[3] or need[4]:
                 p3d = conv_pack(w3, d3, PACK_DGRAD_S2)
             if need[1] or need[2]:
-                if WINOGRAD and WINOGRAD_2D:
-                    p2d = conv_wino2_pack(w2, d2, 1)
-                elif WINOGRAD:
-                    p2d = conv_wino_pack(w2, d2, 1)
-                else:
-                    p2d = conv_pack(w2, d2, PACK_DGRAD_S1)
+                p2d = c2_pack(w2, d2, PACK_DGRAD_S1)
             for t in (p2, p3, p2d, p3d):
                 t.record_stream(main)             # allocated under the side stream, consumed on the main one
             packed_ready = side.record_event()
         # c1 / c2 also emit their ReLU signs as bit planes (60 MB instead of 1.9 GB to re-read in the backward)
         a1, s1 = conv_fwd_bits(x4, p1, b1, d1)
         main.wait_event(packed_ready)
-        if WINOGRAD and WINOGRAD_2D:
-            a2, s2 = conv_wino2_fwd_bits(a1, p2, b2, d2)
-        elif WINOGRAD:
-            a2, s2 = conv_wino_fwd_bits(a1, p2, b2, d2)
-        else:
-            a2, s2 = conv_fwd_bits(a1, p2, b2, d2)
+        a2, s2 = c2_fwd_bits(a1, p2, b2, d2)
         a3 = conv_fwd(a2, p3, b3, d3)
         if TRACE is not None:
             TRACE.update(a1=a1, a2=a2, a3=a3)
-        ctx.wino = (bool(WINOGRAD), bool(WINOGRAD and WINOGRAD_2D))
+        ctx.c2_path = path
         ctx.pool = int(pool)                  # 0: conv feature, 1: pooled vector, 2: both (joint roadmap + box model)
         ctx.rows_per_task = rows_per_task
         ctx.a3_shape = tuple(a3.shape)
@@ -958,7 +957,8 @@ class EncoderConvStack(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad, grad_pooled=None):
         x4, a1, a2, a3, p2d, p3d, s1, s2 = ctx.saved_tensors
-        wino, wino2 = ctx.wino
+        _, _, c2_dgrad_bits, c2_wgrad = _c2(ctx.c2_path)
+        wino2 = ctx.c2_path == "wino2"
         b, h, w, _ = x4.shape
         rpt = ctx.rows_per_task
         d1, d2, d3 = conv_desc(b, h, w, 3, 1, rpt), conv_desc(b, h, w, 32, 1, rpt), conv_desc(b, h, w, 32, 2, rpt)
@@ -984,47 +984,36 @@ class EncoderConvStack(torch.autograd.Function):
         if need[1] or need[2] or need[3] or need[4]:
             g2 = conv_dgrad_bits(g3, p3d, s2, d3)
             del g3
-            for hook in MFMA_PHASE_HOOKS:
-                hook()
+            for obs in BACKWARD_OBSERVERS:
+                obs.backward_phase1()
             reduced = None
 
             def c2_weight_gradient():
                 nonlocal dw2, db2, reduced
                 if need[3] or need[4]:
                     if wino2:      # the reduce of the partials runs on the side stream, beside c2's data gradient
-                        dw2, db2, reduced = conv_wino2_wgrad(a1, g2, d2, finish_stream=_pack_stream(g2.device))
-                    elif wino:
-                        dw2, db2 = conv_wino_wgrad(a1, g2, d2)
+                        dw2, db2, reduced = c2_wgrad(a1, g2, d2, finish_stream=_pack_stream(g2.device))
                     else:
-                        dw2, db2 = conv_wgrad(a1, g2, d2)
+                        dw2, db2 = c2_wgrad(a1, g2, d2)
 
             def c2_data_gradient():
                 nonlocal dw1, db1
                 if (need[1] or need[2]) and wino2 and FUSE_C1_WGRAD:
                     dw1, db1 = conv_wino2_dgrad_w1(g2, p2d, s1, x4, d2)      # g1 never leaves the registers
                 elif need[1] or need[2]:
-                    if wino2:
-                        g1 = conv_wino2_dgrad_bits(g2, p2d, s1, d2)
-                    elif wino:
-                        g1 = conv_wino_dgrad_bits(g2, p2d, s1, d2)
-                    else:
-                        g1 = conv_dgrad_bits(g2, p2d, s1, d2)
-                    dw1, db1 = conv_wgrad(x4, g1, d1)
+                    dw1, db1 = conv_wgrad(x4, c2_dgrad_bits(g2, p2d, s1, d2), d1)
 
-            # C2_DGRAD_FIRST (optim.HipAdam, factor mode of ddp.GradSync): the optimizer passes of the two big Linear layers can only
-            # start once their gathered factors have arrived, ~3 ms into the backward, and they can only run BESIDE c2's weight gradient
-            # (440 registers per SIMD: one 48-register Adam wave fits; the data-gradient kernel's 475 leave no room) -- so that kernel
-            # goes last and the second hook sits in front of it
-            if C2_DGRAD_FIRST:
-                c2_data_gradient()
-                for hook in MFMA_PHASE2_HOOKS:
-                    hook()
-                c2_weight_gradient()
-            else:
-                c2_weight_gradient()
-                for hook in MFMA_PHASE2_HOOKS:
-                    hook()
-                c2_data_gradient()
+            # Data gradient first when an observer asks for it (optim.HipAdam: rank-B passes, factor mode of ddp.GradSync): the optimizer
+            # passes of the two big Linear layers can only start once their gathered factors have arrived, ~3 ms into the backward, and
+            # they can only run BESIDE c2's weight gradient (440 registers per SIMD: one 48-register Adam wave fits; the data-gradient
+            # kernel's 475 leave no room) -- so that kernel goes last and phase 2 sits in front of it
+            first, second = c2_weight_gradient, c2_data_gradient
+            if any(obs.c2_dgrad_first for obs in BACKWARD_OBSERVERS):
+                first, second = second, first
+            first()
+            for obs in BACKWARD_OBSERVERS:
+                obs.backward_phase2()
+            second()
             del g2
             if reduced is not None:
                 torch.cuda.current_stream().wait_event(reduced)

@@ -186,8 +186,8 @@ class EncoderConvStackBf16(torch.autograd.Function):
         if need[1] or need[2] or need[3] or need[4]:
             g2 = conv_dgrad(g3, p3d, s2, d3)
             del g3
-            for hook in ops.MFMA_PHASE_HOOKS:
-                hook()
+            for obs in ops.BACKWARD_OBSERVERS:
+                obs.backward_phase1()
             if need[3] or need[4]:
                 dw2, db2 = conv_wgrad(a1, g2, d2)
             if need[1] or need[2]:

@@ -18,7 +18,7 @@ exist only for those slices (``state[p]["shards"][piece] = (exp_avg, exp_avg_sq)
 back to ``grad_sync.gather_shard`` -- piece k's all-gather is on the links while piece k+1's update runs.  Elementwise, so the
 owned elements get bit for bit the update of the whole-tensor pass.
 """
-import os
+from types import SimpleNamespace
 
 import torch
 
@@ -29,20 +29,17 @@ class HipAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._side = None
-        self._pending = []
-        self._early = set()
+        self._now = None           # this step's bookkeeping: reset_step()
+        self.reset_step()
         self._hooks = []
         self._hooked = set()
         self._big_numel = 1 << 20
         self._scale = 1.0
         self._sync = None
-        self._factored = []        # parameters whose factors are on the links (ddp.GradSync, factor mode)
         self._fgrad = {}           # p -> persistent buffer of the global-batch gradient formed from gathered factors
         self._rankb = {}           # weight -> bias (or None): Linear layers whose gradient is formed inside the Adam pass
         self._rankb_keys = {}      # data_ptr -> weight
-        self._rankb_now = {}       # weight -> (x, dy) of this step's backward, until the pass has been launched
-        self._held = []            # factors read by launches on the side stream: kept until step() has joined it
-        self._fac_now = {}         # weight -> gathered Factors that have arrived (factor mode of ddp.GradSync + rank-B)
+        self._plan_key = self._plan = None      # _rankb_plan()'s last answer
         self._last = False         # passes_last(): c2's data gradient first, the queued passes beside its weight gradient
         self._clip_max = 0.0       # set_clip(): clip the step's gradients to this global 2-norm (0: off)
         self._clip_track = False   # set_clip(): measure the global norm every step
@@ -52,6 +49,26 @@ class HipAdam(torch.optim.Optimizer):
         self.clip_coef = None
 
     SMALL_NUMEL = 1 << 16      # tensors up to this size go into one multi-tensor launch (0: never; tests set it per instance)
+    MAX_ROWS = 64      # dd_adam_step_rankb: batch rows (world x batch for gathered factors)
+    EARLY_SPARE_CUS = 8      # CUs an "early" pass leaves free of its workgroups (dd_set_adam_spare_cus)
+
+    def reset_step(self):
+        """Forget what a backward has left for this step's passes.  ``step()`` ends with it; ``close()`` and ``TrainStep.__call__`` call
+        it so that a step abandoned half way (an exception in ``training_step`` or in the backward) leaves nothing for the next one.
+        Nothing to forget (every step that ran to its end): no library call, no stream operation, no allocation.  Not called from the
+        backward: two backwards before one ``step()`` still add up."""
+        if self._now is not None:
+            if not any(vars(self._now).values()):
+                return
+            if self._side is not None:      # launches on the side stream may still read the factors in ``held``
+                torch.cuda.current_stream().wait_stream(self._side)
+        self._now = SimpleNamespace(
+            pending=[],        # (p, group) whose pass is launched on the side stream when backward reaches its MFMA-bound stretch
+            early=set(),       # tensors whose pass of this step has been launched
+            rankb_now={},      # weight -> (x, dy, bias) of this step's backward, until the pass has been launched
+            held=[],           # factors read by launches on the side stream: kept until the side stream has been joined
+            fac_now={},        # weight -> gathered Factors that have arrived (factor mode of ddp.GradSync + rank-B)
+            factored=[])       # parameters whose factors are on the links (ddp.GradSync, factor mode)
 
     def _state_of(self, p):
         st = self.state[p]
@@ -112,7 +129,7 @@ class HipAdam(torch.optim.Optimizer):
         """{tensor: "window" | "early"} for the registered tensors that take the rank-B pass at this batch size (overlap mode)."""
         live = sorted((q for q in self._rankb if q.requires_grad), key=lambda q: q.numel())
         key = (rows, self._last, tuple(id(q) for q in live))
-        if getattr(self, "_plan_key", None) == key:
+        if self._plan_key == key:
             return self._plan
         cost = lambda q: 24.0 * q.numel()
         plan = {}
@@ -151,22 +168,22 @@ class HipAdam(torch.optim.Optimizer):
         p = self._rankb_keys.get(weight.data_ptr())
         if p is None or not p.requires_grad or p.grad is not None or self._sync_blocks_rankb():
             return 0
-        if x.shape[0] > self.MAX_ROWS or (p not in self._rankb_now and not self._rankb_fits(p, x.shape[0])):
+        if x.shape[0] > self.MAX_ROWS or (p not in self._now.rankb_now and not self._rankb_fits(p, x.shape[0])):
             return 0
         if not (x.is_contiguous() and dy.is_contiguous() and x.dtype == torch.float32 and dy.dtype == torch.float32):
             return 0
         bias = self._rankb[p]
         if bias is not None and (not bias.requires_grad or bias.grad is not None):
             bias = None
-        if p in self._early:
+        if p in self._now.early:
             raise RuntimeError("HipAdam (rank-B mode): a Linear layer ran a second backward after its optimizer pass of this step was "
                                "launched; call step() between the backwards or build TrainStep(fuse_linear_wgrad=False)")
-        prev = self._rankb_now.get(p)
+        prev = self._now.rankb_now.get(p)
         if prev is not None:      # a second backward through the layer before the step (shared weight, retained graph): the gradients add
             x, dy = torch.cat([prev[0], x]), torch.cat([prev[1], dy])
         else:
             self._queue_rankb(p)
-        self._rankb_now[p] = (x, dy, bias)
+        self._now.rankb_now[p] = (x, dy, bias)
         if prev is None and self._side is not None and self._last and self._goes_early(p, x.shape[0]):
             # the window beside c2's weight gradient belongs to the LARGEST rank-B tensor (it fills it: fc1's pass 1.26 ms beside a 1.21 ms
             # kernel); a smaller one queued in front of it would push it past the kernel's end.  It goes to the side stream now, beside the
@@ -183,11 +200,8 @@ class HipAdam(torch.optim.Optimizer):
                     self._take_rankb(p, self._group_of(p), self._scale)
                 finally:
                     _lib.call("dd_set_adam_spare_cus", 0)
-            self._pending = [(q, g) for q, g in self._pending if q is not p]
+            self._now.pending = [(q, g) for q, g in self._now.pending if q is not p]
         return 2 if bias is not None else 1
-
-    MAX_ROWS = 64      # dd_adam_step_rankb: batch rows (world x batch for gathered factors)
-    EARLY_SPARE_CUS = 8      # CUs an "early" pass leaves free of its workgroups (dd_set_adam_spare_cus)
 
     def factor_bias(self, weight, rows):
         """Factor mode of ddp.GradSync: whether the pass over the gathered factors (``rows`` = world x batch of them) will update this
@@ -198,7 +212,7 @@ class HipAdam(torch.optim.Optimizer):
 
     def _queue_rankb(self, p):
         if self._side is not None and p.numel() >= self._big_numel:
-            self._pending.append((p, self._group_of(p)))      # launched on the side stream when backward reaches its MFMA-bound stretch
+            self._now.pending.append((p, self._group_of(p)))      # launched on the side stream when backward reaches its MFMA-bound stretch
 
     def _update_rankb(self, p, group, grad_scale, x, dy, bias):
         """The one place ``dd_adam_step_rankb`` is called: Adam on ``p`` (and ``bias``) with the gradient dy^T x formed on the fly."""
@@ -212,16 +226,16 @@ class HipAdam(torch.optim.Optimizer):
             bst["step"] += 1
             if bst["step"] != st["step"]:
                 raise RuntimeError("HipAdam: a Linear layer's weight and bias have taken different numbers of steps")
-            self._early.add(bias)
+            self._now.early.add(bias)
         b1, b2 = group["betas"]
         ops.adam_step_rankb(p.data, st["exp_avg"], st["exp_avg_sq"], dy, x, None if bias is None else bias.data,
                             None if bst is None else bst["exp_avg"], None if bst is None else bst["exp_avg_sq"],
                             group["lr"], b1, b2, group["eps"], st["step"], grad_scale)
-        self._held.append((x, dy, bias is not None))      # (the flag: what rankb_sqnorm needs when it measures a pass that already ran)
-        self._early.add(p)
+        self._now.held.append((x, dy, bias is not None))      # (the flag: what rankb_sqnorm needs when it measures a pass that already ran)
+        self._now.early.add(p)
 
     def _take_rankb(self, p, group, grad_scale):
-        now = self._rankb_now.pop(p, None)
+        now = self._now.rankb_now.pop(p, None)
         if now is None:
             return False
         self._update_rankb(p, group, grad_scale, *now)
@@ -231,7 +245,7 @@ class HipAdam(torch.optim.Optimizer):
         """Use ``grad_sync`` (ddp.GradSync) for per-piece waits and, in shard mode, for the shards and their all-gathers."""
         self._sync = grad_sync
         if getattr(grad_sync, "factor", False):
-            grad_sync.on_factors = self._factored.append
+            grad_sync.on_factors = lambda p: self._now.factored.append(p)
 
     def _group_of(self, p):
         for group in self.param_groups:
@@ -248,7 +262,7 @@ class HipAdam(torch.optim.Optimizer):
         for work in fac.works:
             work.wait()
         if p in self._rankb and fac.rows <= self.MAX_ROWS:      # rank-B mode: no gradient tensor, the gathered factors go straight into the Adam pass
-            self._fac_now[p] = fac
+            self._now.fac_now[p] = fac
             return True
         g = self._fgrad.get(p)
         if g is None or g.shape != p.shape or g.device != p.device:
@@ -259,7 +273,7 @@ class HipAdam(torch.optim.Optimizer):
 
     def _update_formed(self, p, group, grad_scale):
         """The Adam pass behind ``_form_factored``: from ``p.grad``, or -- rank-B mode -- straight from the gathered factors."""
-        fac = self._fac_now.pop(p, None)
+        fac = self._now.fac_now.pop(p, None)
         if fac is None:
             return self._update(p, group, grad_scale)
         bias = self._rankb[p]
@@ -275,20 +289,20 @@ class HipAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def _flush_factored(self):
-        """Between c2's weight and data gradient (ops.MFMA_PHASE2_HOOKS): the factors gathered since the top of the backward have
+        """Between c2's two gradient kernels (backward_phase2): the factors gathered since the top of the backward have
         arrived (N = 2: 202 MB over one link in ~3 ms).  The weight-gradient kernels run HERE, on the backward's stream -- on the side
         stream, beside conv kernels that fill every CU with 440-register waves, they starve (measured on a one-rank communicator:
         81 us -> 1.2 ms) -- and the Adam passes, built to run beside those kernels, go to the side stream behind them."""
-        if not self._factored:
+        if not self._now.factored:
             return
-        done = [p for p in self._factored if self._form_factored(p)]
-        self._factored.clear()
+        done = [p for p in self._now.factored if self._form_factored(p)]
+        self._now.factored.clear()
         ev = torch.cuda.current_stream().record_event()
         with torch.cuda.stream(self._side):
             self._side.wait_event(ev)
             for p in done:
                 self._update_formed(p, self._group_of(p), self._scale)
-                self._early.add(p)
+                self._now.early.add(p)
 
     def _update_shards(self, p, group, grad_scale, shards):
         """The update of the slices of ``p`` this rank owns: wait (on the current stream) for piece k's reduce-scatter, update the
@@ -419,33 +433,39 @@ class HipAdam(torch.optim.Optimizer):
         self._scale = grad_scale
         if grad_sync is not None:
             self._sync = grad_sync
-        self._pending = []
         self._big_numel = big_numel
         self._hooked = set()
-        # (c2's data gradient first, the passes beside its weight gradient last: same step time, round 5 A/B 7.51 / 7.51 ms)
-        ops.MFMA_PHASE_HOOKS.append(self._flush_pending)
-        ops.MFMA_PHASE2_HOOKS.append(self._flush_factored)
-        if getattr(self._sync, "factor", False):
-            ops.C2_DGRAD_FIRST = True             # the Adam passes behind the gathered factors run beside c2's weight gradient: it goes last
+        if self not in ops.BACKWARD_OBSERVERS:
+            ops.BACKWARD_OBSERVERS.append(self)
         self.refresh()
         lightning.on_unfreeze(self)
 
     def passes_last(self, on=True):
-        """Where the queued optimizer passes are launched in the encoder's backward: at the first MFMA hook (in front of c2's weight
+        """Where the queued optimizer passes are launched in the encoder's backward: at phase 1 of the backward (in front of c2's weight
         gradient, then its data gradient: the round-1..4 order) or, ``on``, with c2's DATA gradient first and the passes beside its
-        weight gradient, which then goes last (``ops.C2_DGRAD_FIRST``).  The rank-B passes (72 registers) fit beside the weight gradient
+        weight gradient, which then goes last (``c2_dgrad_first``).  The rank-B passes (72 registers) fit beside the weight gradient
         only: launched in front of it they are still resident when the 475-register data gradient is dispatched, and that kernel waits
         for them CU by CU (1.9 ms from dispatch to end for 1.4 ms of work).  Same step time either way on one GPU (round 5 A/B: 7.51 /
         7.51 ms), but with the passes last the step's longest kernel runs -- and is timed -- by itself."""
         if self._side is None:
             return
-        here, there = (ops.MFMA_PHASE2_HOOKS, ops.MFMA_PHASE_HOOKS) if on else (ops.MFMA_PHASE_HOOKS, ops.MFMA_PHASE2_HOOKS)
-        if self._flush_pending in there:
-            there.remove(self._flush_pending)
-        if self._flush_pending not in here:
-            here.insert(0, self._flush_pending)
         self._last = bool(on)
-        ops.C2_DGRAD_FIRST = bool(on) or bool(getattr(self._sync, "factor", False))
+
+    # ---- what ops.BACKWARD_OBSERVERS asks of its members (registered by overlap_with_backward, removed by close) -----------------------
+    @property
+    def c2_dgrad_first(self):
+        """The passes last, or factor mode of ddp.GradSync, where the Adam passes behind the gathered factors run beside c2's weight
+        gradient: either way that kernel goes last."""
+        return self._last or bool(getattr(self._sync, "factor", False))
+
+    def backward_phase1(self):
+        if not self._last:
+            self._flush_pending()
+
+    def backward_phase2(self):
+        if self._last:
+            self._flush_pending()
+        self._flush_factored()
 
     def refresh(self):
         """Hook the big parameters that require a gradient and are not hooked yet: a frozen feature extractor
@@ -460,7 +480,7 @@ class HipAdam(torch.optim.Optimizer):
                     self._hooked.add(p)
 
     def close(self):
-        """Undo overlap_with_backward: remove the gradient hooks and the backward-phase callback (an optimizer that is dropped
+        """Undo overlap_with_backward: remove the gradient hooks and leave ops.BACKWARD_OBSERVERS (an optimizer that is dropped
         while another model is trained in the same process would otherwise stay registered)."""
         for h in self._hooks:
             h.remove()
@@ -469,14 +489,10 @@ class HipAdam(torch.optim.Optimizer):
         for key in list(self._rankb_keys):
             if ops.RANKB.get(key) is self:
                 del ops.RANKB[key]
-        self._rankb, self._rankb_keys, self._rankb_now, self._fac_now = {}, {}, {}, {}
-        if self._flush_pending in ops.MFMA_PHASE_HOOKS:
-            ops.MFMA_PHASE_HOOKS.remove(self._flush_pending)
-        if self._flush_pending in ops.MFMA_PHASE2_HOOKS:
-            ops.MFMA_PHASE2_HOOKS.remove(self._flush_pending)
-        if self._flush_factored in ops.MFMA_PHASE2_HOOKS:
-            ops.MFMA_PHASE2_HOOKS.remove(self._flush_factored)
-            ops.C2_DGRAD_FIRST = False
+        self._rankb, self._rankb_keys = {}, {}
+        if self in ops.BACKWARD_OBSERVERS:
+            ops.BACKWARD_OBSERVERS.remove(self)
+        self.reset_step()
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
         self._side = None
@@ -508,8 +524,8 @@ class HipAdam(torch.optim.Optimizer):
         if s is not None and (getattr(s, "active", False) or getattr(s, "shard", False) or getattr(s, "factor", False)):
             raise NotImplementedError("HipAdam.set_clip: the global norm under a live GradSync (all-reduce, sharded, factor gather) is "
                                       "not implemented")
-        factors = [(x, dy, has_bias) for x, dy, has_bias in self._held]                  # passes that already ran (track, overlap mode)
-        factors += [(x, dy, bias is not None) for x, dy, bias in self._rankb_now.values()]
+        factors = [(x, dy, has_bias) for x, dy, has_bias in self._now.held]                  # passes that already ran (track, overlap mode)
+        factors += [(x, dy, bias is not None) for x, dy, bias in self._now.rankb_now.values()]
         big, small = [], []
         for group in self.param_groups:
             for p in group["params"]:
@@ -544,21 +560,21 @@ class HipAdam(torch.optim.Optimizer):
 
     def _early_step(self, p, group):
         if p.grad is not None:
-            self._pending.append((p, group))      # launched when backward reaches its MFMA-bound stretch
+            self._now.pending.append((p, group))      # launched when backward reaches its MFMA-bound stretch
 
     @torch.no_grad()
     def _flush_pending(self):
-        if not self._pending:
+        if not self._now.pending:
             return
         ev = torch.cuda.current_stream().record_event()
         with torch.cuda.stream(self._side):
             self._side.wait_event(ev)
             # rank-B passes first: they only fit beside the weight gradient, the plain passes behind them also run beside the data gradient
-            for p, group in self._pending:
-                if p in self._rankb_now:
+            for p, group in self._now.pending:
+                if p in self._now.rankb_now:
                     self._take_rankb(p, group, self._scale)
-            for p, group in self._pending:
-                if p in self._early:
+            for p, group in self._now.pending:
+                if p in self._now.early:
                     continue
                 shards = self._sync.shards(p) if self._sync is not None else None
                 pieces = self._sync.pieces(p) if self._sync is not None else None
@@ -568,28 +584,27 @@ class HipAdam(torch.optim.Optimizer):
                     self._update_pieces(p, group, self._scale, pieces)
                 else:
                     self._update(p, group, self._scale)
-                self._early.add(p)
-        self._pending = []
+                self._now.early.add(p)
+        self._now.pending = []
 
     @torch.no_grad()
     def step(self, grad_scale=1.0):
         if self._side is not None:
-            self._flush_pending()                 # backward never reached an MFMA phase hook (other models)
+            self._flush_pending()                 # backward never reached a phase (other models)
         if self._clip_max > 0 or self._clip_track:
             scale = self._measure(grad_scale)
             if self._clip_max > 0 and scale is not None:
                 grad_scale = scale                # every update below reads grad_scale x coef from the device
-        self._factored.clear()
         for group in self.param_groups:
             small = {}                            # step count -> [(p, g, m, v)]: one launch for all the small tensors
             for p in group["params"]:
-                if p in self._rankb_now and p not in self._early:      # rank-B mode without the side stream: here, after the backward
+                if p in self._now.rankb_now and p not in self._now.early:      # rank-B mode without the side stream: here, after the backward
                     self._take_rankb(p, group, grad_scale)
                     continue
-                if p not in self._early and self._sync is not None and getattr(self._sync, "factor", False) and self._sync.has_factors(p):
+                if p not in self._now.early and self._sync is not None and getattr(self._sync, "factor", False) and self._sync.has_factors(p):
                     self._update_factored(p, group, grad_scale)      # no side stream: here, after the backward
                     continue
-                if p.grad is None or p in self._early:
+                if p.grad is None or p in self._now.early:
                     continue
                 shards = self._sync.shards(p) if self._sync is not None else None
                 if shards:
@@ -605,9 +620,4 @@ class HipAdam(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             for step, quads in small.items():
                 ops.adam_step_multi(quads, group["lr"], b1, b2, group["eps"], step, grad_scale)
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-        self._early.clear()
-        self._held.clear()
-        self._rankb_now.clear()
-        self._fac_now.clear()
+        self.reset_step()                         # joins the side stream (every pass launched there is in the step's state)

@@ -117,6 +117,7 @@ class TrainStep:
 
     def __call__(self, batch, batch_idx):
         """One training step; returns ``training_step``'s dict (``out['loss']`` is the step's loss, still on the device)."""
+        self.optimizer.reset_step()              # a step that never reached step() (an exception on the way) leaves nothing for this one
         self.model.zero_grad(set_to_none=True)
         out = self.model.training_step(batch, batch_idx)
         loss = out["loss"]

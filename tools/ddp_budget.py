@@ -71,7 +71,7 @@ def curve():
     t_shard8 = min(sim["sim_c2_s8"]["ms_per_step"], sim["sim2_c2_s8"]["ms_per_step"])
     # factor gather (ddp.GradSync(factor_linear=True)): every rank receives (N - 1) x 202 MB -- fc1's 120 MB of pooled activations, on the
     # links from the end of the forward's conv part, and the head's 82 MB of dlogits from the top of the backward -- and needs them in
-    # front of c2's weight gradient, which goes LAST in this mode (ops.C2_DGRAD_FIRST).  Compute side measured on a one-rank RCCL
+    # front of c2's weight gradient, which goes LAST in this mode (HipAdam.c2_dgrad_first).  Compute side measured on a one-rank RCCL
     # communicator: +0.2 ms over the plain step (the two weight-gradient launches over N x 32 rows, the reordered backward).
     f_gb = 0.202
     w_fac = m["backward_end"] - 1.4 - m["forward_end"] + 0.5      # forward tail (0.5 ms) + the backward up to c2's weight gradient (its last ~1.4 ms)

@@ -13,7 +13,12 @@ TrainStep calls each (the first holds the lazy packing and workspace queries, th
 call of BBSpatialRoadMap at the reference's view size, batch 2, frozen encoder, in exact fp32 and once more with split products.
 Then the paths those leave out: the fp32 BasicAE at the same tiny size (the decoder's narrow path: dc3 by four phase launches, dc4 on
 the generic engine), BoxesMergingCNN alone at batch 1 (the k8 d8 / k6 d6 output_padding layers, forward and backward), and the
-BBSpatialRoadMap step at batch 1 with every A/B switch of gconv and heads off (each layer's fallback on the generic engine)."""
+BBSpatialRoadMap step at batch 1 with every A/B switch of gconv and heads off (each layer's fallback on the generic engine).
+
+    python tools/record_abi_call_trace.py --schedule [--out tests/golden/backward_schedule_trace.json]
+
+records the fixture of tests/test_gpu_backward_schedule.py instead: names only, of the optimizer passes and the conv stack's kernels
+in one steady TrainStep call, for each of ARRANGEMENTS of the optimizer beside the backward (``record_schedule``)."""
 import argparse
 import ctypes
 import json
@@ -173,15 +178,62 @@ def record(dev=None):
     return json.loads(json.dumps(out))                    # what the fixture holds: tuples as lists
 
 
+# ---- the order of optimizer passes and conv kernels in one step -------------------------------------------------------------------
+SCHEDULE_SYMBOLS = ("dd_adam_", "dd_conv_")               # the Adam passes; the entry points of c1 / c2 / c3, both Winograd families included
+ARRANGEMENTS = {"default": {}, "passes_first": dict(passes_last=False), "after_backward": dict(adam_overlap=False),
+                "materialised": dict(fuse_linear_wgrad=False)}
+
+
+def schedule_of(ts, batch, batch_idx):
+    """The SCHEDULE_SYMBOLS calls of ``ts(batch, batch_idx)``, names only, in call order."""
+    with Recorder() as calls:
+        ts(batch, batch_idx)
+        torch.cuda.synchronize()
+    return [symbol for symbol, _ in calls if symbol.startswith(SCHEDULE_SYMBOLS)]
+
+
+def _tiny():
+    """``_tiny_model`` / ``_tiny_batch`` of tests/test_gpu_round5.py: the suite's tiny RoadMapBCE and its batches."""
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_round5
+    return test_gpu_round5._tiny_model, test_gpu_round5._tiny_batch
+
+
+def tiny_train_step(dev, **kw):
+    """TrainStep over the tiny model with the head and the encoder's fc1 on rank-B passes (big_numel = 4096): the smallest
+    arrangement in which ``passes_last`` engages."""
+    from driving_dirty_amd.train import TrainStep
+    return TrainStep(_tiny()[0](dev), lr=1e-2, big_numel=4096, scheduler=False, **kw)
+
+
+def record_schedule(dev=None):
+    """{arrangement: [symbol, ...]} of the steady (second) TrainStep call in each of ARRANGEMENTS."""
+    dev = dev or torch.device("cuda:0")
+    batch = _tiny()[1]
+    out = {}
+    for name, kw in ARRANGEMENTS.items():
+        ts = tiny_train_step(dev, **kw)
+        try:
+            ts(batch(dev, 0, 0), 0)
+            out[name] = schedule_of(ts, batch(dev, 1, 0), 1)
+        finally:
+            ts.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "abi_call_trace.json"))
+    ap.add_argument("--schedule", action="store_true", help="record backward_schedule_trace.json (record_schedule) instead")
+    ap.add_argument("--out", default=None, help="default: abi_call_trace.json, or backward_schedule_trace.json, under tests/golden")
     ap.add_argument("--check", action="store_true", help="record twice and require the same lists before writing")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("record_abi_call_trace: needs a GPU")
-    out = record()
-    if args.check and record() != out:
+    rec = record_schedule if args.schedule else record
+    args.out = args.out or os.path.join(ROOT, "tests", "golden", "backward_schedule_trace.json" if args.schedule else "abi_call_trace.json")
+    out = rec()
+    if args.check and rec() != out:
         raise SystemExit("record_abi_call_trace: two recordings in one process differ")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
