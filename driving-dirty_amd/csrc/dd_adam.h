@@ -11,8 +11,15 @@
 // the rest: 34 vector instructions per four elements instead of 175.  The pass usually runs beside the conv backward, where its
 // vector instructions compete with the conv kernels' own (tools/ubench/mfma_issue.hip: they do overlap the MFMAs of another
 // wave but not its vector work): with the IEEE form the register-row data gradient took 1.95-1.97 ms in the step, with this one
-// 1.70-1.78.  m and v are exact (multiplies and fmas only); p differs from torch.optim.Adam's by at most the
-// rounding of an update term that is 2e-7 relative off (tests: 1e-6).
+// 1.70-1.78.
+// Accuracy against torch.optim.Adam's arithmetic in fp64 (bounds: tests/_element_ref.py, from an fp32 model of these operations
+// with a correctly rounded square root and reciprocal; held by tests/test_gpu_element_range.py over 30 decades of g and m, 60 of
+// v, steps 1 .. 2^31 - 1): m and v are multiplies and fused multiply-adds only, so they are the IEEE result of this sequence bit
+// for bit -- not exact: five roundings in v (within 6 x 2^-24 relative) and three in m (within 5 x 2^-24 of |b1 m| + |(1 - b1)
+// g|, its terms' magnitude: where the two terms cancel, m's RELATIVE error is that times magnitude / |m|, and the update
+// inherits it). The update p_new - p is within (5 magnitude / |m| + 5) 2^-24 of itself plus half an ulp of the larger of p and
+// p_new. Zero, subnormal, infinite and NaN inputs give fp32 torch.optim.Adam's pattern of zeros, infinities and NaNs (a result
+// below 2^-126 may be a subnormal where torch's order of operations underflows to zero).
 // omb1 = 1.f - b1, omb2 = 1.f - b2 (fp32 subtractions: the same bits on the host and on the device).  A kernel that passes them as
 // arguments keeps them in scalar registers; computed in the kernel they occupy vector registers (no scalar float ALU on gfx950).
 __device__ __forceinline__ void adam_elem2(f32x2& p, f32x2& m, f32x2& v, f32x2 g, float gscale, float b1, float b2, float omb1,

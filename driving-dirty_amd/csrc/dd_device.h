@@ -117,7 +117,15 @@ __device__ __forceinline__ void dd_barrier_dma() { asm volatile("s_waitcnt vmcnt
 // sigmoid(z) and softplus(-|z|) = log1p(exp(-|z|)) from the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32,
 // 1 ulp each) instead of libm's expf + log1pf + IEEE divisions: 145 -> ~25 instructions per element, which is what
 // made the loss pass compute-bound (87 us for 184 MB).  log1p(e) = log(u) * e / (u - 1) with u = fl(1 + e) undoes the
-// rounding of 1 + e (u - 1 is exact); one Newton step on the reciprocal keeps sigmoid within 1 ulp.
+// rounding of 1 + e (u - 1 is exact); one Newton step refines the reciprocal.
+// Accuracy against fp64 (tests/_element_ref.py derives the bounds from an fp32 model of this formula with correctly rounded
+// primitives; tests/test_gpu_element_range.py holds the kernels to them and prints what they use of each; DESIGN.md 3.4f has the
+// figures): sigmoid for z >= 0 within 3 x 2^-24 ABSOLUTE, and bit for bit the correctly rounded reciprocal of u wherever u is
+// determined -- that is what the Newton step buys; the absolute bound holds without it. For z < 0, and for the softplus, the
+// error is RELATIVE and grows with |z|: within (|z| + 11) 2^-24 and (|z| + 12) 2^-24 on the tested logits, below 2^-126 flushed
+// to zero. The |z| is the rounding of the exponent -|z| log2(e) -- half an ulp of it is up to 2^-24 |z| of e -- plus 0.22 |z|
+// for the rounded constant: so "within 1 ulp" holds in the absolute sense only, and a logit past |z| = 40 whose exponent rounds
+// the wrong way just above 64 can need 1.22 |z| + 3.
 // Here because it is the ONE sigmoid of the dense head: dd_sigmoid, the BCE pass (dense.hip) and dd_linear_sigmoid_gt (linear.hip) all
 // take theirs from it, so their probabilities agree bit for bit.
 __device__ __forceinline__ void dd_sigmoid_softplus(float z, float& sig, float& l1p) {
