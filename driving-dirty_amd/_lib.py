@@ -234,3 +234,57 @@ def size(name, *args):
     if n < 0:
         raise HotpathError(f"{name} refused (returned {n}): {lib().dd_last_error().decode()}")
     return n
+
+
+# ---- extension libraries --------------------------------------------------------------------------------------------------------
+class Extension:
+    """The binder of an extension library: launch functions that are not part of include/dd_hotpath.h (its set of functions is
+    pinned), declared in a header of their own and built into a library of their own that links against ``libdd_hotpath.so`` for
+    ``dd_fail`` / ``dd_last_error()`` (build.py).  ``augment.py`` and ``tta.py`` each hold one and publish its parts as module-level
+    names.  The ctypes table comes from the header through ``parse_header`` -- the one parser -- and ``launch(name, *operands)`` enters
+    a function the way ``call`` does: looked up on the ``CDLL`` at every call, operands in header order, the current torch stream
+    appended, ``HotpathError`` with the library's message on a non-zero return.  ``what``: the missing-library message's noun."""
+
+    def __init__(self, header, library, what):
+        self.header, self.library, self.what = header, library, what
+        with open(header) as f:
+            self.signatures, self.streamed = parse_header(f.read())
+        # every function ends in the stream, which launch() appends
+        self.operands = {name: len(args) - 1 for name, (res, args) in self.signatures.items()}
+        self._handle = None
+
+    def lib(self):
+        """Load the library once, after the main library (it links against it: ``dd_fail``); raise when it is absent."""
+        if self._handle is None:
+            lib()
+            if not os.path.exists(self.library):
+                raise HotpathError(f"{self.library} is missing: build the HIP extensions first (python -m driving_dirty_amd.build or "
+                                   f"__graft_entry__.build()). There is no CPU / eager fallback for {self.what}.")
+            handle = C.CDLL(self.library)
+            for name, (res, args) in self.signatures.items():
+                fn = getattr(handle, name)          # AttributeError if the .so lacks a declared symbol
+                fn.restype, fn.argtypes = res, args
+            self._handle = handle
+        return self._handle
+
+    def last_error(self):
+        """The message of the calling thread's last failure: ``dd_last_error()`` of the ``libdd_hotpath.so`` this library is linked
+        against (the one beside it; DD_HOTPATH_LIB may have sent ``lib()`` to another build)."""
+        from . import build as _build
+        hot = lib() if LIB == _build.LIB else C.CDLL(_build.LIB)
+        fn = hot.dd_last_error
+        fn.restype = C.c_char_p
+        return fn().decode()
+
+    def launch(self, name, *operands):
+        """Enter a launch function of the header with ``operands`` in header order; a tensor goes as its device pointer, ctypes
+        arrays, numbers and None as they are; the current torch stream is appended.  Raises HotpathError on another operand count
+        than the header's and on a non-zero return.  The function is looked up on the CDLL object NOW."""
+        if len(operands) != self.operands.get(name):
+            where = "include/" + os.path.basename(self.header)
+            raise HotpathError(f"{name}: " + (f"not a function of {where}" if name not in self.operands else
+                                              f"{len(operands)} operands given, the header declares {self.operands[name]} in front of the stream"))
+        args = [ptr(a) if isinstance(a, torch.Tensor) else a for a in operands]
+        rc = getattr(self.lib(), name)(*args, stream())
+        if rc != 0:
+            raise HotpathError(f"{name} failed (code {rc}): {self.last_error()}")

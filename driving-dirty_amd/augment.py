@@ -1,9 +1,10 @@
 """Train-time augmentation on the device: the left/right mirror of the six-camera rig, exposure jitter, view drop.
 
 Two parts.  The BINDER of ``csrc/libdd_augment.so`` (``include/dd_augment.h``): an extension library of its own, because the set of
-functions of ``include/dd_hotpath.h`` is pinned.  Its ctypes table comes from the header through ``_lib.parse_header`` -- the one
-parser -- and ``launch(name, *operands)`` enters a function the way ``_lib.call`` does: looked up on the ``CDLL`` at every call,
-operands in header order, the current torch stream appended, ``HotpathError`` with the library's message on a non-zero return.
+functions of ``include/dd_hotpath.h`` is pinned.  It is a ``_lib.Extension``, whose parts are this module's ``lib`` / ``launch`` /
+``last_error``: the ctypes table comes from the header through ``_lib.parse_header`` -- the one parser -- and
+``launch(name, *operands)`` enters a function the way ``_lib.call`` does: looked up on the ``CDLL`` at every call, operands in header
+order, the current torch stream appended, ``HotpathError`` with the library's message on a non-zero return.
 
 The ``Augmenter``: what a model's ``training_step`` calls first.  Off by default: with every probability and width at 0 ``apply``
 returns the batch object it was given and nothing is launched.
@@ -14,7 +15,6 @@ left to right, the road map's rows are reversed (the bird's-eye frame has x forw
 rows) and a box has its y negated and its left and right corners swapped.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -24,10 +24,9 @@ from ._lib import HotpathError
 from .lightning import hparam
 
 # ---- the binder ------------------------------------------------------------------------------------------------------------------
-LIB = _build.AUG_LIB
-with open(_build.AUG_HEADER) as _f:
-    SIGNATURES, STREAMED = _lib.parse_header(_f.read())
-OPERANDS = {name: len(args) - 1 for name, (res, args) in SIGNATURES.items()}      # every function ends in the stream, which launch() appends
+_EXT = _lib.Extension(_build.AUG_HEADER, _build.AUG_LIB, "the augmentation")      # the one binder of an extension library (_lib.py)
+LIB, SIGNATURES, STREAMED, OPERANDS = _EXT.library, _EXT.signatures, _EXT.streamed, _EXT.operands
+lib, launch, last_error = _EXT.lib, _EXT.launch, _EXT.last_error      # module-level names: the functions below reach ``launch`` through the module's globals at call time
 CHUNK = 32      # samples per kernel launch: kChunk of csrc/augment.hip (pointers, flags and colours travel in the kernel arguments)
 FLAG_MIRROR = 1
 
@@ -38,45 +37,6 @@ def flag_blank(view):
 
 
 MIRROR_VIEWS = (2, 1, 0, 5, 4, 3)      # output view v of a mirrored sample is input view MIRROR_VIEWS[v], reversed left to right
-_handle = None
-
-
-def lib():
-    """Load ``libdd_augment.so`` once, after the main library (it links against it: ``dd_fail``); raise when it is absent."""
-    global _handle
-    if _handle is None:
-        _lib.lib()
-        if not os.path.exists(LIB):
-            raise HotpathError(f"{LIB} is missing: build the HIP extensions first (python -m driving_dirty_amd.build or "
-                               "__graft_entry__.build()). There is no CPU / eager fallback for the augmentation.")
-        handle = C.CDLL(LIB)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)          # AttributeError if the .so lacks a declared symbol
-            fn.restype, fn.argtypes = res, args
-        _handle = handle
-    return _handle
-
-
-def last_error():
-    """The message of the calling thread's last failure: ``dd_last_error()`` of the ``libdd_hotpath.so`` this library is linked
-    against (the one beside it; DD_HOTPATH_LIB may have sent ``_lib`` to another build)."""
-    hot = _lib.lib() if _lib.LIB == _build.LIB else C.CDLL(_build.LIB)
-    fn = hot.dd_last_error
-    fn.restype = C.c_char_p
-    return fn().decode()
-
-
-def launch(name, *operands):
-    """Enter a launch function of ``dd_augment.h`` with ``operands`` in header order; a tensor goes as its device pointer, ctypes
-    arrays, numbers and None as they are; the current torch stream is appended.  Raises HotpathError on another operand count than
-    the header's and on a non-zero return.  The function is looked up on the CDLL object NOW."""
-    if len(operands) != OPERANDS.get(name):
-        raise HotpathError(f"{name}: " + ("not a function of include/dd_augment.h" if name not in OPERANDS else
-                                          f"{len(operands)} operands given, the header declares {OPERANDS[name]} in front of the stream"))
-    args = [_lib.ptr(a) if isinstance(a, torch.Tensor) else a for a in operands]
-    rc = getattr(lib(), name)(*args, _lib.stream())
-    if rc != 0:
-        raise HotpathError(f"{name} failed (code {rc}): {last_error()}")
 
 
 # ---- the three kernels as functions of tensors -------------------------------------------------------------------------------------

@@ -1,12 +1,13 @@
-"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension library (``csrc/libdd_augment.so``) with hipcc for gfx950.
+"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension libraries (``csrc/libdd_augment.so``, ``csrc/libdd_tta.so``) with hipcc for gfx950.
 
     python -m driving_dirty_amd.build          # or __graft_entry__.build()
 
 hipcc cross-compiles without a GPU.  The library is built IN-TREE so that it travels with the
 repository snapshot to the GPU box (a JIT cache under ~/.cache would not).  Each source is compiled
 to its own object (in parallel, re-done only when the source or a header is newer) and the objects
-are linked into the one library.  The extension library (``include/dd_augment.h``: the train-time augmentation) is built the same
-way, with the same flags, from its own sources, and links against the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.
+are linked into the one library.  The extension libraries (``include/dd_augment.h``: the train-time augmentation; ``include/dd_tta.h``:
+mirror test-time averaging) are built the same way, with the same flags, each from its own sources, and link against the main library,
+whose ``dd_fail`` / ``dd_last_error`` they use.
 """
 import os
 import subprocess
@@ -29,6 +30,11 @@ AUG_LIB = os.path.join(CSRC, "libdd_augment.so")
 AUG_SOURCES = ["augment.hip"]
 AUG_HEADER = os.path.join(os.path.dirname(HEADER), "dd_augment.h")
 AUG_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, AUG_HEADER]
+# ... and the second one: mirror test-time averaging (the sets of functions of both headers above are pinned); tta.py binds it
+TTA_LIB = os.path.join(CSRC, "libdd_tta.so")
+TTA_SOURCES = ["tta.hip"]
+TTA_HEADER = os.path.join(os.path.dirname(HEADER), "dd_tta.h")
+TTA_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, TTA_HEADER]
 
 
 def _obj(src):
@@ -50,8 +56,12 @@ def _augment_needs_build():
     return _stale(AUG_LIB, [os.path.join(CSRC, s) for s in AUG_SOURCES] + AUG_HEADERS)
 
 
+def _tta_needs_build():
+    return _stale(TTA_LIB, [os.path.join(CSRC, s) for s in TTA_SOURCES] + TTA_HEADERS)
+
+
 def needs_build():
-    return _main_needs_build() or _augment_needs_build()
+    return _main_needs_build() or _augment_needs_build() or _tta_needs_build()
 
 
 def build_diag(verbose=True):
@@ -82,26 +92,39 @@ def _run(cmd, verbose):
     subprocess.check_call(cmd)
 
 
-def build_augment(force=False, verbose=True):
-    """``csrc/libdd_augment.so`` from AUG_SOURCES: the main library's flags; linked against ``libdd_hotpath.so`` (found beside it at load
+def _build_extension(lib, sources, headers, force, verbose):
+    """An extension library from its own sources: the main library's flags; linked against ``libdd_hotpath.so`` (found beside it at load
     time, $ORIGIN), which therefore has to exist."""
-    if not force and not _augment_needs_build():
-        return AUG_LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
-    for src in AUG_SOURCES:
-        if force or _stale(_obj(src), [os.path.join(CSRC, src)] + AUG_HEADERS):
+    for src in sources:
+        if force or _stale(_obj(src), [os.path.join(CSRC, src)] + headers):
             _run([hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", _obj(src)], verbose)
-    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", AUG_LIB] + [_obj(s) for s in AUG_SOURCES]
+    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + [_obj(s) for s in sources]
          + ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], verbose)
-    return AUG_LIB
+    return lib
+
+
+def build_augment(force=False, verbose=True):
+    """``csrc/libdd_augment.so`` from AUG_SOURCES, when it is stale."""
+    if not force and not _augment_needs_build():
+        return AUG_LIB
+    return _build_extension(AUG_LIB, AUG_SOURCES, AUG_HEADERS, force, verbose)
+
+
+def build_tta(force=False, verbose=True):
+    """``csrc/libdd_tta.so`` from TTA_SOURCES, when it is stale."""
+    if not force and not _tta_needs_build():
+        return TTA_LIB
+    return _build_extension(TTA_LIB, TTA_SOURCES, TTA_HEADERS, force, verbose)
 
 
 def build(force=False, verbose=True):
-    """Both libraries, each only when it is stale; returns the main library's path."""
+    """The three libraries, each only when it is stale; returns the main library's path."""
     if force or _main_needs_build():
         _build_main(force, verbose)
     build_augment(force, verbose)
+    build_tta(force, verbose)
     return LIB
 
 

@@ -20,10 +20,12 @@ import torch
 from torch import nn
 
 from . import ops
+from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
-from .roadmap import CalibratedThreshold, eval_no_grad, predict_map, prediction_threshold, road_map_scores
+from .roadmap import (TTA_ROAD_KEYS, CalibratedThreshold, eval_no_grad, predict_map, predict_map_tta, prediction_threshold, road_map_scores,
+                      tta_road_map_scores)
 from .spatial import (HALF_UNLESS_CALIBRATED, ONE_UNLESS_CONFIGURED, CalibratedBoxThreshold, RoadMapBoxesMergingCNN, SpatialMappingCNN,
                       add_box_args, bb_coord_to_map, box_decode_point, box_loss_config, boxes_from_map, decoded_box_ats, mean_logs,
                       per_sample_inputs, require_bounding_boxes)
@@ -104,6 +106,23 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         return self._road_logits(pooled), boxes
 
     # ------------------------------------------------------------------------------------------------ prediction
+    def _tta_maps(self, scene, mirrored, tau):
+        """Mirror test-time averaging of the camera-only construction (tta.py), from the parts of the two passes: ``scene`` and
+        ``mirrored`` are each ``(feat, space_rep, road logits)``.  -> (road map torch.bool [B,800,800], averaged box map fp32
+        [B,800,800]).  The road map is ``tta.mean_gt`` of the two logits at ``tau``; the scene's box branch reads it, the mirrored
+        box branch reads ``tta.mirror_masks`` of it -- the map a mirrored training sample's box head was given -- and ``tta.mean_prob``
+        brings the two box maps together."""
+        (feat, space_rep, logits), (feat_m, space_rep_m, logits_m) = scene, mirrored
+        road = _tta.mean_gt(logits.detach().contiguous(), logits_m.detach().contiguous(), tau, True)
+        probs = self._box_branch(feat, space_rep, tuple(road.unbind(0)))
+        probs_m = self._box_branch(feat_m, space_rep_m, _tta.mirror_masks(road))
+        return road, _tta.mean_prob(probs.detach().contiguous(), probs_m.detach().contiguous(), False)
+
+    def _mirrored_parts(self, x):
+        """``(feat, space_rep, road logits)`` of the mirrored scene: the same code as the scene's pass on ``tta.mirror_views(x)``."""
+        feat_m, pooled_m, space_rep_m = self._features(_tta.mirror_views(x))
+        return feat_m, space_rep_m, self._road_logits(pooled_m)
+
     def predict(self, x, threshold=None, box_threshold=HALF_UNLESS_CALIBRATED, min_pixels=ONE_UNLESS_CONFIGURED, max_boxes=256, fit="extent",
                 pad_px=0.5, split_px=0, grow_iters=None):
         """What the task asks for, from the six cameras alone: ``Prediction(road_map, boxes)``, torch.bool [B,800,800] and a tuple of
@@ -113,9 +132,31 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         ``box_threshold`` where there is one, else 0.5; ``min_pixels`` left out (or None): ``hparams.box_min_pixels``, else 1; a value the
         caller gives wins, 0.5 and 1 included (``spatial.box_decode_point``; the two defaults show what they fall back to).  ``x``:
         whatever ``forward`` takes.  The same kernels on the same inputs as ``predict_road_map(x)`` followed by
-        ``predict_boxes(x, masks)``, minus the second encoder conv pass."""
+        ``predict_boxes(x, masks)``, minus the second encoder conv pass.
+
+        Under ``hparams.tta_mirror`` (default off) the prediction is made with mirror test-time averaging.  This method's signature is
+        pinned, so it follows the hparams; ``predict_mode`` is the same method with the mode as an argument.
+
+        Mirror test-time averaging (``_tta_maps``): two passes at B -- the scene, and the same code on ``tta.mirror_views(x)`` -- the
+        road map from the mean of the two heads' probabilities, the box map the mean of the two box branches' maps, each fed the road
+        map in its own orientation.  The dense
+        blocks' dropout is on in eval mode too, as in the reference, so the two passes also draw two dropout masks.  The thresholds
+        left out are the one ``rm_threshold`` / ``box_threshold`` in either mode: under ``hparams.tta_mirror`` validation calibrates them
+        on the averaged maps, and ``tta=False`` on such a checkpoint reuses them as they are."""
+        return self.predict_mode(x, None, threshold, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
+
+    def predict_mode(self, x, tta=None, threshold=None, box_threshold=HALF_UNLESS_CALIBRATED, min_pixels=ONE_UNLESS_CONFIGURED, max_boxes=256,
+                     fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+        """``predict`` with the averaging mode as an argument: ``tta`` None = ``hparams.tta_mirror`` (what ``predict`` does), False = off,
+        True / "mirror" = mirror test-time averaging.  Everything else as ``predict``'s."""
         tau = prediction_threshold(self, threshold)
         box_threshold, min_pixels = box_decode_point(self.hparams, box_threshold, min_pixels)
+        if _tta.resolve(self, tta) is not None:
+            with eval_no_grad(self):
+                feat, pooled, space_rep = self._features(x)
+                road, probs = self._tta_maps((feat, space_rep, self._road_logits(pooled)), self._mirrored_parts(x), tau)
+                boxes = boxes_from_map(probs, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
+            return Prediction(road, boxes)
         with eval_no_grad(self):
             feat, pooled, space_rep = self._features(x)
             z = self.ae.encoder._tail(pooled, (None, None))
@@ -124,19 +165,30 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
             boxes = boxes_from_map(probs, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
         return Prediction(road, boxes)
 
-    def predict_boxes(self, x, rm=None, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+    def predict_boxes(self, x, rm=None, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None,
+                      tta=None):
         """The box head's map as boxes, as ``BBSpatialRoadMap.predict_boxes``: a tuple of B tensors [n_i,2,4].  ``rm=None``: camera-only,
         the boxes of ``predict`` (the head's own road map at its calibrated threshold); a given ``rm`` is used as it is.
-        ``threshold=None`` / ``min_pixels=None``: the calibrated ``box_threshold``, else 0.5 / ``hparams.box_min_pixels``, else 1."""
+        ``threshold=None`` / ``min_pixels=None``: the calibrated ``box_threshold``, else 0.5 / ``hparams.box_min_pixels``, else 1.
+        ``tta``: as ``predict``'s; with a given ``rm`` as ``BBSpatialRoadMap.predict_boxes``'s: the mean of ``self(x, rm)``'s box map and
+        of the one of ``tta.mirror_views(x)`` with ``tta.mirror_masks(rm)``, in ``eval()`` mode."""
         if rm is None:
-            return self.predict(x, None, threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters).boxes
+            return self.predict_mode(x, tta, None, threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters).boxes
         threshold, min_pixels = box_decode_point(self.hparams, threshold, min_pixels)
+        if _tta.resolve(self, tta) is not None:
+            with eval_no_grad(self):
+                probs = _tta.mean_prob(self(x, rm)[1].detach().contiguous(),
+                                       self(_tta.mirror_views(x), _tta.mirror_masks(rm))[1].detach().contiguous(), False)
+                return boxes_from_map(probs, threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
         with torch.no_grad():
             return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
-    def predict_road_map(self, x, threshold=None):
-        """The road-map branch as a boolean map, as ``RoadMapBCE.predict_road_map``: torch.bool [B,800,800]; the box branch is not run."""
+    def predict_road_map(self, x, threshold=None, tta=None):
+        """The road-map branch as a boolean map, as ``RoadMapBCE.predict_road_map`` (``tta`` included): torch.bool [B,800,800]; the box
+        branch is not run."""
         views = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
+        if _tta.resolve(self, tta) is not None:
+            return predict_map_tta(self, lambda v: self.ae.encoder.forward_nhwc4(ops.wide_image(v)), views, threshold)
         return predict_map(self, lambda: self.ae.encoder.forward_nhwc4(ops.wide_image(views)), threshold)
 
     # ------------------------------------------------------------------------------------------------ the steps
@@ -161,7 +213,10 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
     def _box_sweep_of(self, batch):
         sample, target, road_image = batch
         require_bounding_boxes(target)
-        feat, pooled, space_rep = self._features(self._step_inputs(sample, road_image)[0])
+        x = self._step_inputs(sample, road_image)[0]
+        feat, pooled, space_rep = self._features(x)
+        if _tta.resolve(self, None) is not None:      # the averaged box map: the one ``predict`` decodes in this mode
+            return self._with_box_sweep({}, self._tta_maps((feat, space_rep, self._road_logits(pooled)), self._mirrored_parts(x), self._own_tau())[1], target)
         return self._with_box_sweep({}, self._camera_only_box_map(feat, space_rep, self._road_logits(pooled), logits=True), target)
 
     def _run_step(self, batch, own_rm, want_probs):
@@ -193,7 +248,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         else:
             loss_bb = ops.BceProbs.apply(boxes.reshape(b, -1), target_bb.reshape(b, -1))
         return {"b": b, "loss_rm": loss_rm, "loss_bb": loss_bb, "parts": parts, "logits": logits, "boxes": boxes, "target_bb": target_bb,
-                "probs": None if probs is None else probs.detach().reshape(b, 800, 800), "feat": feat, "space_rep": space_rep}
+                "probs": None if probs is None else probs.detach().reshape(b, 800, 800), "feat": feat, "space_rep": space_rep, "sample": sample}
 
     def training_step(self, batch, batch_idx):
         """``hparams.box_rm_input = "target"`` (the default): the box branch reads the batch's road map, the step the reference's two
@@ -221,7 +276,12 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         ``hparams.calibrate_box_threshold`` also ``box_ats_sweep``: that same camera-only box map, the one ``predict`` decodes, decoded and
         scored at every threshold of the grid.  With both calibrations on, an epoch's sweep is made of maps computed with the
         ``rm_threshold`` found at the end of the PREVIOUS epoch (0.5 in the first): the two operating points are not iterated to a joint
-        optimum; the box threshold found is the best one for the road map the model had during that epoch."""
+        optimum; the box threshold found is the best one for the road map the model had during that epoch.
+
+        Under ``hparams.tta_mirror`` also one pass over the mirrored batch (``no_grad``): the road map's ``val_ts_tta`` /
+        ``val_ts_rounded_tta`` from the averaged probabilities, which ``ts_hist`` is then taken from; under ``hparams.box_metrics``
+        ``val_ats_tta``, camera-only, the construction of ``predict`` in this mode (``_tta_maps``) with the features of both passes
+        reused; and ``box_ats_sweep`` reads that averaged box map.  Every other key keeps its meaning."""
         sample, target, road_image = batch
         s = self._run_step(batch, False, True)
         out = {"val_loss": s["loss_rm"] + s["loss_bb"], "val_roadmap_loss": s["loss_rm"], "val_bbox_loss": s["loss_bb"]}
@@ -229,25 +289,36 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
             out["val_bce"], out["val_soft_ts"] = s["parts"]
         target_rm = torch.stack(tuple(road_image), dim=0).float()
         out.update(road_map_scores(target_rm, s["probs"]))
-        self._with_ts_hist(out, s["probs"], target_rm)
+        averaged = _tta.resolve(self, None) is not None
+        if averaged:
+            with torch.no_grad():
+                mirrored = self._mirrored_parts(s["sample"])
+                avg = _tta.mean_prob(s["logits"].detach().contiguous(), mirrored[2].detach().contiguous(), True)
+            self._with_ts_hist(tta_road_map_scores(out, target_rm, avg), avg, target_rm)
+        else:
+            self._with_ts_hist(out, s["probs"], target_rm)
         box_metrics, sweep = hparam(self.hparams, "box_metrics", False), self._wants_box_sweep()
         if box_metrics or sweep:
             with torch.no_grad():
                 require_bounding_boxes(target)
-                own = self._camera_only_box_map(s["feat"], s["space_rep"], s["probs"])      # once, for whichever asks
+                if box_metrics or not averaged:
+                    own = self._camera_only_box_map(s["feat"], s["space_rep"], s["probs"])      # once, for whichever asks
                 if box_metrics:
                     out["val_ats_gt_rm"] = decoded_box_ats(self.hparams, s["boxes"].detach().contiguous(), target)
                     out["val_ats"] = decoded_box_ats(self.hparams, own, target)
                     out["val_box_ts"] = ops.threat_score(s["target_bb"].contiguous(), own, round_b=True)
+                own_avg = self._tta_maps((s["feat"], s["space_rep"], s["logits"]), mirrored, self._own_tau())[1] if averaged else None
+                if box_metrics and averaged:
+                    out["val_ats_tta"] = decoded_box_ats(self.hparams, own_avg, target)
                 if sweep:
-                    self._with_box_sweep(out, own, target)
+                    self._with_box_sweep(out, own_avg if averaged else own, target)
         return out
 
     def validation_epoch_end(self, outputs):
         """The mean of every per-batch value as ``avg_*``; ``val_loss`` is the monitored value; under ``hparams.calibrate_threshold``
         ``rm_threshold`` is set from the epoch's summed histogram, as in ``RoadMapBCE``."""
         keys = ("val_loss", "val_roadmap_loss", "val_bbox_loss", "val_bce", "val_soft_ts", "val_ts", "val_ts_rounded", "val_ats_gt_rm",
-                "val_ats", "val_box_ts")
+                "val_ats", "val_box_ts", "val_ats_tta") + TTA_ROAD_KEYS
         logs = mean_logs(outputs, keys)
         self._calibrate(outputs, logs)
         if self._wants_box_sweep():
@@ -274,4 +345,5 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "fp32x3"),
                        help="fp32: the reference's arithmetic; fp32x3: the box head's dilated up-convs as six bf16 products per fp32 product")
         add_augment_args(p)
+        _tta.add_tta_args(p)
         return p

@@ -13,6 +13,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import ops
+from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
@@ -48,6 +49,29 @@ def predict_map(module, latent, threshold):
     with eval_no_grad(module):
         y = ops.linear_sigmoid_gt(latent(), module.fc1.weight, module.fc1.bias, tau)
     return y.reshape(y.size(0), 800, 800)
+
+
+def predict_map_tta(module, encode, x, threshold):
+    """``predict_map`` under mirror test-time averaging (tta.py): TWO passes at B, not one at 2 B -- ``encode(x)`` is the un-averaged
+    path's encoder at its shapes, ``encode(tta.mirror_views(x))`` the same code on the mirrored scene -- ``ops.linear`` with
+    ``module.fc1`` gives the logits of each, and ``tta.mean_gt`` the map: sigmoid of both, the mirrored one's rows reversed, the mean
+    and the comparison in one kernel.  Same mode handling as ``predict_map``.  The dense blocks' dropout is on in eval mode too, as in
+    the reference, so the two passes also draw two dropout masks."""
+    tau = prediction_threshold(module, threshold)
+    with eval_no_grad(module):
+        weight, bias = module.fc1.weight, module.fc1.bias
+        logits = ops.linear(encode(x), weight, bias).reshape(-1, 800, 800)
+        logits_m = ops.linear(encode(_tta.mirror_views(x)), weight, bias).reshape(-1, 800, 800)
+        return _tta.mean_gt(logits, logits_m, tau, True)
+
+
+def tta_road_map_scores(out, target_rm, avg_probs):
+    """``out`` <- ``val_ts_tta`` / ``val_ts_rounded_tta``: ``road_map_scores`` of the averaged probabilities (hparams.tta_mirror)."""
+    out.update({k + "_tta": v for k, v in road_map_scores(target_rm, avg_probs).items()})
+    return out
+
+
+TTA_ROAD_KEYS = ("val_ts_tta", "val_ts_rounded_tta")
 
 
 def compute_ts_road_map(road_map1, road_map2):
@@ -133,12 +157,20 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         y = self._logits(x, keeps)
         return y, ops.sigmoid(y.detach())
 
-    def predict_road_map(self, x, threshold=None):
+    def predict_road_map(self, x, threshold=None, tta=None):
         """The reference's "Predicting test images" step (run_test.py) for one batch: torch.bool [B,800,800], equal to ``forward``'s
         probabilities ``> threshold`` in eval mode.  ``x``: whatever ``forward`` takes.  Encoder, then the head, the sigmoid and the
         comparison in one kernel: neither logits nor probabilities are written.  (The dense blocks' dropout is on in eval mode too, as
-        in the reference, components.py:108.)"""
-        return predict_map(self, lambda: self._encode(x), threshold)
+        in the reference, components.py:108.)
+
+        ``tta``: None = ``hparams.tta_mirror`` (default off), False = off, True / "mirror" = mirror test-time averaging
+        (``predict_map_tta``): the scene and its mirror, each through encoder and head, the mean of the two probabilities
+        ``> threshold``.  With dropout on the two passes draw two masks.  ``threshold=None`` is the one calibrated ``rm_threshold`` in
+        either mode: under ``hparams.tta_mirror`` validation calibrates it on the averaged probabilities, and ``tta=False`` on such a
+        checkpoint reuses it as it is."""
+        if _tta.resolve(self, tta) is None:
+            return predict_map(self, lambda: self._encode(x), threshold)
+        return predict_map_tta(self, self._encode, x, threshold)
 
     def _run_step(self, batch, batch_idx, step_name, keeps=(None, None)):
         sample, target, road_image = batch
@@ -182,13 +214,21 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         return {"loss": train_loss, "log": {"train_loss": train_loss}}
 
     def validation_step(self, batch, batch_idx):
+        """Under ``hparams.tta_mirror`` also a mirrored pass (``no_grad``) and ``val_ts_tta`` / ``val_ts_rounded_tta``, the scores of the
+        averaged probabilities; ``ts_hist`` (``hparams.calibrate_threshold``) is then taken from those, so ``rm_threshold`` is
+        calibrated in the mode the checkpoint predicts in.  ``val_loss``, ``val_ts`` and ``val_ts_rounded`` keep their meaning."""
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, **road_map_scores(target_rm, pred_logit_rm)}
-        return self._with_ts_hist(out, pred_logit_rm, target_rm)
+        if _tta.resolve(self, None) is None:
+            return self._with_ts_hist(out, pred_logit_rm, target_rm)
+        with torch.no_grad():
+            avg = _tta.mean_prob(pred_rm.detach().contiguous(), self._logits(_tta.mirror_views(batch[0])), True)
+        return self._with_ts_hist(tta_road_map_scores(out, target_rm, avg), avg, target_rm)
 
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
+        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS if outputs and all(k in x for x in outputs)})
         self._calibrate(outputs, logs)
         return {"val_loss": avg["val_loss"], "log": logs}
 
@@ -209,6 +249,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         p.add_argument("--calibrate_threshold", action="store_true",
                        help="validation also finds the threshold with the best data-set threat score (rm_threshold)")
         add_augment_args(p)
+        _tta.add_tta_args(p)
         return p
 
 
@@ -239,4 +280,8 @@ class RoadMap(RoadMapBCE):
         val_loss, target_rm, pred_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, "val_ts": compute_ts_road_map(target_rm, pred_rm),
                "val_ts_rounded": ops.threat_score(target_rm.contiguous(), pred_rm.contiguous(), round_b=True)}
-        return self._with_ts_hist(out, pred_rm, target_rm)
+        if _tta.resolve(self, None) is None:
+            return self._with_ts_hist(out, pred_rm, target_rm)
+        with torch.no_grad():      # ``forward`` ends in the head's sigmoid here: the mean of the two PROBABILITIES, the same bits as from the logits
+            avg = _tta.mean_prob(pred_rm.detach().contiguous(), self(_tta.mirror_views(batch[0])).contiguous(), False)
+        return self._with_ts_hist(tta_road_map_scores(out, target_rm, avg), avg, target_rm)

@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import gconv, ops
+from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
 from .autoencoder import BasicAE
 from .heads import MergeFn, SpatialMapFn, _ORDER, as_nhwc, road_map_taps
@@ -449,10 +450,20 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
         sample = torch.stack(tuple(sample), dim=0) if isinstance(sample, (tuple, list)) else sample
         return sample, torch.stack(tuple(road_image), dim=0).float().unsqueeze(1)
 
+    def _tta_box_map(self, x, rm, scene=None):
+        """The averaged box map [b,800,800] of mirror test-time averaging (tta.py): ``self(x, rm)`` (or ``scene``, where the caller
+        has it) and the same code on the mirrored scene, ``self(tta.mirror_views(x), tta.mirror_masks(rm))``, through
+        ``tta.mean_prob``.  Two passes at B, not one at 2 B.  Outside autograd."""
+        with torch.no_grad():
+            scene = self(x, rm) if scene is None else scene
+            mirrored = self(_tta.mirror_views(x), _tta.mirror_masks(rm))
+            return _tta.mean_prob(scene.detach().reshape(-1, 800, 800).contiguous(), mirrored.detach().contiguous(), False)
+
     def _box_sweep_of(self, batch):
         sample, target, road_image = batch
         require_bounding_boxes(target)
-        return self._with_box_sweep({}, self(*self._batch_inputs(sample, road_image)), target)
+        x, rm = self._batch_inputs(sample, road_image)
+        return self._with_box_sweep({}, self(x, rm) if _tta.resolve(self, None) is None else self._tta_box_map(x, rm), target)
 
     def _run_step_parts(self, batch, batch_idx, step_name):
         """-> (loss, target, prediction, parts): parts is None with the reference's loss, (L_bce, L_ts) with ``box_loss_config``'s."""
@@ -488,24 +499,44 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
             log["bbox_bce"], log["bbox_soft_ts"] = parts
         return {"loss": train_loss, "log": log}
 
-    def predict_boxes(self, x, rm, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+    def predict_boxes(self, x, rm, threshold=None, min_pixels=None, max_boxes=256, fit="extent", pad_px=0.5, split_px=0, grow_iters=None,
+                      tta=None):
         """Forward pass, then the predicted map's connected components as boxes (``ops.component_boxes``): a tuple of b tensors
         [n_i,2,4] in the data set's format.  ``threshold=None``: the calibrated ``box_threshold`` where there is one, else 0.5;
         ``min_pixels=None``: ``hparams.box_min_pixels``, else 1; an explicit argument wins (``box_decode_point``).  A sample with more
         than ``max_boxes`` components is cut there, with a warning.
         ``fit="oriented"``: rotated rectangles along each component's principal axis (which end is the front is arbitrary).
-        ``split_px > 0``: touching cars joined through a neck are split first (``ops.split_components``)."""
+        ``split_px > 0``: touching cars joined through a neck are split first (``ops.split_components``).
+
+        ``tta``: None = ``hparams.tta_mirror`` (default off), False = off, True / "mirror" = mirror test-time averaging: the map decoded
+        is ``_tta_box_map(x, rm)``, the mean of the scene's map and the mirrored scene's, reflected back; that path runs in ``eval()``
+        mode (every submodule's mode is put back).  The encoder's dense blocks are not part of this model's forward, so the two passes
+        draw no dropout masks here; in the models that run them (the road-map head) dropout is on in eval mode too and each pass draws
+        its own.  ``threshold=None`` is the one ``box_threshold`` in either mode: under ``hparams.tta_mirror`` it is calibrated on the
+        averaged map, and ``tta=False`` on such a checkpoint reuses it as it is."""
         threshold, min_pixels = box_decode_point(self.hparams, threshold, min_pixels)
+        if _tta.resolve(self, tta) is not None:
+            with eval_no_grad(self):
+                return boxes_from_map(self._tta_box_map(x, rm), threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
         with torch.no_grad():
             return boxes_from_map(self(x, rm), threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
     def validation_step(self, batch, batch_idx):
         """Under ``hparams.calibrate_box_threshold`` also ``box_ats_sweep``: the predicted map (computed with the batch's road map, as
-        everything this module validates) decoded and scored at every threshold of the grid."""
+        everything this module validates) decoded and scored at every threshold of the grid.  Under ``hparams.tta_mirror`` the sweep
+        reads the averaged map (``_tta_box_map``: one more forward pass, on the mirrored batch), and ``hparams.box_metrics`` adds
+        ``val_ats_tta`` / ``val_ts_tta`` from it; the other keys keep their meaning."""
         val_loss, target_bb_img, pred_bb_img, parts = self._run_step_parts(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss}
         if parts is not None:
             out["val_bce"], out["val_soft_ts"] = parts
+        sweep_map = pred_bb_img.detach().reshape(-1, 800, 800)
+        if _tta.resolve(self, None) is not None and (hparam(self.hparams, "box_metrics", False) or self._wants_box_sweep()):
+            sweep_map = self._tta_box_map(*self._batch_inputs(batch[0], batch[2]), scene=pred_bb_img)
+            if hparam(self.hparams, "box_metrics", False):
+                require_bounding_boxes(batch[1])
+                out["val_ats_tta"] = decoded_box_ats(self.hparams, sweep_map, batch[1])
+                out["val_ts_tta"] = ops.threat_score(target_bb_img.contiguous(), sweep_map.reshape(target_bb_img.shape), round_b=True)
         if hparam(self.hparams, "box_metrics", False):
             # the task's own unit: boxes extracted from the predicted map against the targets' boxes, and the map-level threat score
             with torch.no_grad():
@@ -515,13 +546,13 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
         if self._wants_box_sweep():
             with torch.no_grad():
                 require_bounding_boxes(batch[1])
-                self._with_box_sweep(out, pred_bb_img.detach().reshape(-1, 800, 800), batch[1])
+                self._with_box_sweep(out, sweep_map, batch[1])
         return out
 
     def validation_epoch_end(self, outputs):
         avg_val_loss = torch.stack([x["val_loss"] for x in outputs]).mean()
         logs = {"avg_val_loss": avg_val_loss}
-        logs.update(mean_logs(outputs, ("val_ats", "val_ts", "val_bce", "val_soft_ts")))      # present only under hparams.box_metrics / the box-map loss
+        logs.update(mean_logs(outputs, ("val_ats", "val_ts", "val_bce", "val_soft_ts", "val_ats_tta", "val_ts_tta")))      # present only under hparams.box_metrics / the box-map loss
         if self._wants_box_sweep():
             self._calibrate_boxes(outputs, logs)      # sets box_threshold: the next epoch's val_ats and the predictions decode there
         return {"val_loss": avg_val_loss, "log": logs}
@@ -544,4 +575,5 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
                        help="fp32: the reference's arithmetic; bf16: encoder conv stack on the bf16 matrix cores; fp32x3: the box head's "
                             "dilated up-convs as six bf16 products per fp32 product (MI355X build only)")
         add_augment_args(p)
+        _tta.add_tta_args(p)
         return p
