@@ -1,4 +1,4 @@
-"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension libraries (``csrc/libdd_augment.so``, ``csrc/libdd_tta.so``) with hipcc for gfx950.
+"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension libraries (``csrc/libdd_augment.so``, ``csrc/libdd_tta.so``, ``csrc/libdd_ema.so``) with hipcc for gfx950.
 
     python -m driving_dirty_amd.build          # or __graft_entry__.build()
 
@@ -6,7 +6,7 @@ hipcc cross-compiles without a GPU.  The library is built IN-TREE so that it tra
 repository snapshot to the GPU box (a JIT cache under ~/.cache would not).  Each source is compiled
 to its own object (in parallel, re-done only when the source or a header is newer) and the objects
 are linked into the one library.  The extension libraries (``include/dd_augment.h``: the train-time augmentation; ``include/dd_tta.h``:
-mirror test-time averaging) are built the same way, with the same flags, each from its own sources, and link against the main library,
+mirror test-time averaging; ``include/dd_ema.h``: the moving average of the parameters) are built the same way, with the same flags, each from its own sources, and link against the main library,
 whose ``dd_fail`` / ``dd_last_error`` they use.
 """
 import os
@@ -35,6 +35,11 @@ TTA_LIB = os.path.join(CSRC, "libdd_tta.so")
 TTA_SOURCES = ["tta.hip"]
 TTA_HEADER = os.path.join(os.path.dirname(HEADER), "dd_tta.h")
 TTA_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, TTA_HEADER]
+# ... and the third: the exponential moving average of the parameters and the exchange with it (the three headers above are pinned); ema.py binds it
+EMA_LIB = os.path.join(CSRC, "libdd_ema.so")
+EMA_SOURCES = ["ema.hip"]
+EMA_HEADER = os.path.join(os.path.dirname(HEADER), "dd_ema.h")
+EMA_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, EMA_HEADER]
 
 
 def _obj(src):
@@ -60,8 +65,12 @@ def _tta_needs_build():
     return _stale(TTA_LIB, [os.path.join(CSRC, s) for s in TTA_SOURCES] + TTA_HEADERS)
 
 
+def _ema_needs_build():
+    return _stale(EMA_LIB, [os.path.join(CSRC, s) for s in EMA_SOURCES] + EMA_HEADERS)
+
+
 def needs_build():
-    return _main_needs_build() or _augment_needs_build() or _tta_needs_build()
+    return _main_needs_build() or _augment_needs_build() or _tta_needs_build() or _ema_needs_build()
 
 
 def build_diag(verbose=True):
@@ -119,12 +128,20 @@ def build_tta(force=False, verbose=True):
     return _build_extension(TTA_LIB, TTA_SOURCES, TTA_HEADERS, force, verbose)
 
 
+def build_ema(force=False, verbose=True):
+    """``csrc/libdd_ema.so`` from EMA_SOURCES, when it is stale."""
+    if not force and not _ema_needs_build():
+        return EMA_LIB
+    return _build_extension(EMA_LIB, EMA_SOURCES, EMA_HEADERS, force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The three libraries, each only when it is stale; returns the main library's path."""
+    """The four libraries, each only when it is stale; returns the main library's path."""
     if force or _main_needs_build():
         _build_main(force, verbose)
     build_augment(force, verbose)
     build_tta(force, verbose)
+    build_ema(force, verbose)
     return LIB
 
 

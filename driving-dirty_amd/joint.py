@@ -22,6 +22,7 @@ from torch import nn
 from . import ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
+from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 from .roadmap import (TTA_ROAD_KEYS, CalibratedThreshold, eval_no_grad, predict_map, predict_map_tta, prediction_threshold, road_map_scores,
@@ -346,4 +347,5 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
                        help="fp32: the reference's arithmetic; fp32x3: the box head's dilated up-convs as six bf16 products per fp32 product")
         add_augment_args(p)
         _tta.add_tta_args(p)
+        add_ema_args(p)
         return p

@@ -15,6 +15,7 @@ from torch.nn import functional as F
 from . import ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
+from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 
@@ -250,6 +251,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
                        help="validation also finds the threshold with the best data-set threat score (rm_threshold)")
         add_augment_args(p)
         _tta.add_tta_args(p)
+        add_ema_args(p)
         return p
 
 

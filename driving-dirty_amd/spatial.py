@@ -13,6 +13,7 @@ from torch import nn
 from . import gconv, ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
+from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .heads import MergeFn, SpatialMapFn, _ORDER, as_nhwc, road_map_taps
 from .lightning import LightningModule, hparam, pretrained_ae
@@ -576,4 +577,5 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
                             "dilated up-convs as six bf16 products per fp32 product (MI355X build only)")
         add_augment_args(p)
         _tta.add_tta_args(p)
+        add_ema_args(p)
         return p

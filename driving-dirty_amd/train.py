@@ -17,6 +17,8 @@ exactly that (torch.optim.Adam): a caller with its own loop keeps working.  This
     ``shard_optimizer=True`` -- reduce-scatter, Adam on the owned 1/N, in-place all-gather under the next forward; or -- with
     ``factor_linear=True``, for 2-4 ranks -- the big Linear layers send their factors (input, output gradient) instead of their
     weight gradients and every rank forms the global-batch gradient itself (ddp.py);
+  * ``ema_decay`` / ``ema_every`` / ``ema_warmup`` (``--ema_*``): an exponential moving average of the parameters kept on the device
+    (``ema.WeightEMA``), updated after the optimizer step; ``averaged()`` evaluates it in place; one GPU only;
   * frozen feature extractors (``self.ae.freeze()`` in the fine-tuning modules) are handled: both objects are built over the model
     as constructed and re-arm when ``training_step`` unfreezes it (lightning.on_unfreeze);
   * ``validation_epoch_end(val_loss)`` steps ``ReduceLROnPlateau`` the way Lightning does for a scheduler returned beside the
@@ -34,7 +36,8 @@ from .optim import HipAdam
 class TrainStep:
     def __init__(self, model, lr=None, adam_overlap="auto", shard_optimizer=False, reserve_cus=None, process_group=None,
                  force_collectives=False, simulate_world=0, scheduler="auto", big_numel=1 << 20, chunk_numel=1 << 25, factor_linear=False,
-                 fuse_linear_wgrad=True, passes_last="auto", gradient_clip_val=None, track_grad_norm=False):
+                 fuse_linear_wgrad=True, passes_last="auto", gradient_clip_val=None, track_grad_norm=False, ema_decay=None, ema_every=None,
+                 ema_warmup=None):
         self.model = model
         hp = getattr(model, "hparams", None)
         if lr is None:
@@ -68,6 +71,30 @@ class TrainStep:
             self.sync.remove()
             raise NotImplementedError("TrainStep: gradient_clip_val / track_grad_norm under a live GradSync (all-reduce, sharded, factor "
                                       "gather) is not implemented: one GPU only")
+        # --ema_decay / --ema_every / --ema_warmup (ema.add_ema_args): an exponential moving average of the parameters, updated on the
+        # device after every optimizer step (ema.WeightEMA).  Off (decay 0 or absent): self.ema is None and the step is unchanged.
+        if ema_decay is None:
+            ema_decay = getattr(hp, "ema_decay", 0.0)
+        if ema_every is None:
+            ema_every = getattr(hp, "ema_every", 1)
+        if ema_warmup is None:
+            ema_warmup = getattr(hp, "ema_warmup", False)
+        ema_decay = float(ema_decay or 0.0)
+        if not 0.0 <= ema_decay < 1.0:
+            self.sync.remove()
+            raise ValueError(f"TrainStep: ema_decay = {ema_decay} is outside [0, 1)")
+        if ema_decay > 0 and (self.sync.active or self.sync.shard or self.sync.factor):
+            self.sync.remove()
+            raise NotImplementedError("TrainStep: ema_decay under a live GradSync (all-reduce, sharded, factor gather) is not implemented: "
+                                      "one GPU only (a sharded all-gather still writes parameters under the next forward)")
+        self.ema = None
+        if ema_decay > 0:
+            from .ema import WeightEMA
+            try:
+                self.ema = WeightEMA(model, ema_decay, every=int(ema_every or 1), warmup=bool(ema_warmup))
+            except Exception:
+                self.sync.remove()
+                raise
         if self.clip > 0 and adam_overlap == "auto":
             adam_overlap = False      # no optimizer pass may start before every gradient exists: the after-backward arrangement
         if adam_overlap == "auto":
@@ -126,6 +153,8 @@ class TrainStep:
         loss.backward(self._one)                 # the root gradient is a kept tensor: no ones_like fill launch per step
         self.sync.finish()
         self.optimizer.step(grad_scale=self.sync.grad_scale)
+        if self.ema is not None:                 # step() ended in reset_step(), which joined the side stream: every pass of this step has landed
+            self.ema.update()
         if self.track:                           # Lightning's key for --track_grad_norm 2; the value stays on the device
             out.setdefault("log", {})["grad_2.0_norm_total"] = self.optimizer.grad_norm
         self.last = out
@@ -142,6 +171,13 @@ class TrainStep:
         if self.scheduler is not None:
             self.scheduler.step(float(val_loss))
 
+    def averaged(self):
+        """``with step.averaged():`` the model holds the averaged weights (``ema.WeightEMA.applied``): wrap a validation epoch, a
+        threshold calibration or a prediction in it.  Buffers (BatchNorm statistics) stay the live model's."""
+        if self.ema is None:
+            raise RuntimeError("TrainStep.averaged(): weight averaging is off (ema_decay is 0 or absent)")
+        return self.ema.applied()
+
     @property
     def lr(self):
         return self.optimizer.param_groups[0]["lr"]
@@ -150,3 +186,5 @@ class TrainStep:
         self.sync_params()
         self.optimizer.close()
         self.sync.remove()
+        if self.ema is not None:
+            self.ema.close()
