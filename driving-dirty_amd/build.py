@@ -1,4 +1,4 @@
-"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension libraries (``csrc/libdd_augment.so``, ``csrc/libdd_tta.so``, ``csrc/libdd_ema.so``) with hipcc for gfx950.
+"""Build the C-ABI shared library (``csrc/libdd_hotpath.so``) and its extension libraries (``csrc/libdd_augment.so``, ``csrc/libdd_tta.so``, ``csrc/libdd_ema.so``, ``csrc/libdd_rm_loss.so``) with hipcc for gfx950.
 
     python -m driving_dirty_amd.build          # or __graft_entry__.build()
 
@@ -6,7 +6,7 @@ hipcc cross-compiles without a GPU.  The library is built IN-TREE so that it tra
 repository snapshot to the GPU box (a JIT cache under ~/.cache would not).  Each source is compiled
 to its own object (in parallel, re-done only when the source or a header is newer) and the objects
 are linked into the one library.  The extension libraries (``include/dd_augment.h``: the train-time augmentation; ``include/dd_tta.h``:
-mirror test-time averaging; ``include/dd_ema.h``: the moving average of the parameters) are built the same way, with the same flags, each from its own sources, and link against the main library,
+mirror test-time averaging; ``include/dd_ema.h``: the moving average of the parameters; ``include/dd_rm_loss.h``: the road-map loss on logits) are built the same way, with the same flags, each from its own sources, and link against the main library,
 whose ``dd_fail`` / ``dd_last_error`` they use.
 """
 import os
@@ -40,6 +40,11 @@ EMA_LIB = os.path.join(CSRC, "libdd_ema.so")
 EMA_SOURCES = ["ema.hip"]
 EMA_HEADER = os.path.join(os.path.dirname(HEADER), "dd_ema.h")
 EMA_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, EMA_HEADER]
+# ... and the fourth: weighted BCE-with-logits + soft threat score on the road-map head's logits (the four headers above are pinned); rm_loss.py binds it
+RM_LOSS_LIB = os.path.join(CSRC, "libdd_rm_loss.so")
+RM_LOSS_SOURCES = ["rm_loss.hip"]
+RM_LOSS_HEADER = os.path.join(os.path.dirname(HEADER), "dd_rm_loss.h")
+RM_LOSS_HEADERS = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h"), HEADER, RM_LOSS_HEADER]
 
 
 def _obj(src):
@@ -69,8 +74,12 @@ def _ema_needs_build():
     return _stale(EMA_LIB, [os.path.join(CSRC, s) for s in EMA_SOURCES] + EMA_HEADERS)
 
 
+def _rm_loss_needs_build():
+    return _stale(RM_LOSS_LIB, [os.path.join(CSRC, s) for s in RM_LOSS_SOURCES] + RM_LOSS_HEADERS)
+
+
 def needs_build():
-    return _main_needs_build() or _augment_needs_build() or _tta_needs_build() or _ema_needs_build()
+    return _main_needs_build() or _augment_needs_build() or _tta_needs_build() or _ema_needs_build() or _rm_loss_needs_build()
 
 
 def build_diag(verbose=True):
@@ -135,13 +144,21 @@ def build_ema(force=False, verbose=True):
     return _build_extension(EMA_LIB, EMA_SOURCES, EMA_HEADERS, force, verbose)
 
 
+def build_rm_loss(force=False, verbose=True):
+    """``csrc/libdd_rm_loss.so`` from RM_LOSS_SOURCES, when it is stale."""
+    if not force and not _rm_loss_needs_build():
+        return RM_LOSS_LIB
+    return _build_extension(RM_LOSS_LIB, RM_LOSS_SOURCES, RM_LOSS_HEADERS, force, verbose)
+
+
 def build(force=False, verbose=True):
-    """The four libraries, each only when it is stale; returns the main library's path."""
+    """The five libraries, each only when it is stale; returns the main library's path."""
     if force or _main_needs_build():
         _build_main(force, verbose)
     build_augment(force, verbose)
     build_tta(force, verbose)
     build_ema(force, verbose)
+    build_rm_loss(force, verbose)
     return LIB
 
 

@@ -25,8 +25,8 @@ from .augment import Augmenter, add_augment_args, current_rank
 from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
-from .roadmap import (TTA_ROAD_KEYS, CalibratedThreshold, eval_no_grad, predict_map, predict_map_tta, prediction_threshold, road_map_scores,
-                      tta_road_map_scores)
+from .roadmap import (RM_LOSS_KEYS, TTA_ROAD_KEYS, CalibratedThreshold, add_rm_loss_args, eval_no_grad, predict_map, predict_map_tta,
+                      prediction_threshold, rm_loss_config, road_map_loss_parts, road_map_scores, tta_road_map_scores)
 from .spatial import (HALF_UNLESS_CALIBRATED, ONE_UNLESS_CONFIGURED, CalibratedBoxThreshold, RoadMapBoxesMergingCNN, SpatialMappingCNN,
                       add_box_args, bb_coord_to_map, box_decode_point, box_loss_config, boxes_from_map, decoded_box_ats, mean_logs,
                       per_sample_inputs, require_bounding_boxes)
@@ -36,6 +36,7 @@ Prediction = namedtuple("Prediction", ("road_map", "boxes"))      # torch.bool [
 
 class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningModule):
     box_loss = None      # spatial.box_loss_config(hparams): None = BCE on probabilities, as the reference's box model
+    rm_loss = None       # roadmap.rm_loss_config(hparams): None = mean BCE-with-logits, as the reference's road-map model
     box_rm_input = "target"      # the road map the TRAINING step's box branch reads: "target" (ground truth) | "predicted" (the head's own)
 
     def __init__(self, hparams):
@@ -53,6 +54,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
                 raise ValueError(f"precision must be 'fp32' or 'fp32x3', got {precision!r}")
             self.box_merge.precision = precision
         self.box_loss = box_loss_config(hparams)      # None: BCE on probabilities as the reference's box model (spatial_w_rm.py:131)
+        self.rm_loss = rm_loss_config(hparams)        # None: mean BCE-with-logits (roadmap_bce_v2.py:106)
         self.box_rm_input = hparam(hparams, "box_rm_input", "target")
         if self.box_rm_input not in ("target", "predicted"):
             raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")
@@ -236,8 +238,10 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         else:
             boxes = self._box_branch(feat, space_rep, rm)      # first: see forward
             logits = self._road_logits(pooled)
-        probs = None
-        if per_sample:
+        probs, rm_parts = None, None
+        if self.rm_loss is not None:      # weighted BCE-with-logits + soft threat score; its pass writes the probabilities in either form
+            loss_rm, probs, rm_parts = road_map_loss_parts(self.rm_loss, logits.reshape(b, -1), rm if per_sample else target_rm.reshape(b, -1))
+        elif per_sample:
             loss_rm, probs = ops.BceWithLogitsProbs.apply(logits.reshape(b, -1), rm)
         else:
             loss_rm = ops.BceWithLogits.apply(logits.reshape(b, -1), target_rm.reshape(b, -1))
@@ -248,7 +252,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
             loss_bb, *parts = ops.box_loss(boxes.reshape(b, -1), target_bb.reshape(b, -1).contiguous(), return_parts=True, **self.box_loss)
         else:
             loss_bb = ops.BceProbs.apply(boxes.reshape(b, -1), target_bb.reshape(b, -1))
-        return {"b": b, "loss_rm": loss_rm, "loss_bb": loss_bb, "parts": parts, "logits": logits, "boxes": boxes, "target_bb": target_bb,
+        return {"b": b, "loss_rm": loss_rm, "loss_bb": loss_bb, "parts": parts, "rm_parts": rm_parts, "logits": logits, "boxes": boxes, "target_bb": target_bb,
                 "probs": None if probs is None else probs.detach().reshape(b, 800, 800), "feat": feat, "space_rep": space_rep, "sample": sample}
 
     def training_step(self, batch, batch_idx):
@@ -264,12 +268,14 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         log = {}
         if s["parts"] is not None:
             log["bbox_bce"], log["bbox_soft_ts"] = s["parts"]
+        if s["rm_parts"] is not None:
+            log["rm_bce"], log["rm_soft_ts"] = s["rm_parts"]
         loss = s["loss_rm"] + s["loss_bb"]
         return {"loss": loss, "log": {"train_loss": loss, "roadmap_loss": s["loss_rm"], "bbox_loss": s["loss_bb"], **log}}
 
     def validation_step(self, batch, batch_idx):
         """One encoder pass, one road-map head pass.  Always: ``val_loss`` = ``val_roadmap_loss`` + ``val_bbox_loss`` (the training
-        step's losses; ``val_bce`` / ``val_soft_ts`` with the class-balanced box loss), the road map's ``val_ts`` / ``val_ts_rounded`` as
+        step's losses; ``val_bce`` / ``val_soft_ts`` with the class-balanced box loss, ``val_rm_bce`` / ``val_rm_soft_ts`` under an ``rm_*`` setting), the road map's ``val_ts`` / ``val_ts_rounded`` as
         ``RoadMapBCE`` reports them, ``ts_hist`` under ``hparams.calibrate_threshold``.  Under ``hparams.box_metrics`` also
         ``val_ats_gt_rm`` (boxes decoded from the box map computed WITH the ground-truth road map), ``val_ats`` (the honest one: a
         second box-branch call fed the head's own map of this pass, at ``rm_threshold`` or 0.5) and ``val_box_ts`` (the rounded
@@ -288,6 +294,8 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         out = {"val_loss": s["loss_rm"] + s["loss_bb"], "val_roadmap_loss": s["loss_rm"], "val_bbox_loss": s["loss_bb"]}
         if s["parts"] is not None:
             out["val_bce"], out["val_soft_ts"] = s["parts"]
+        if s["rm_parts"] is not None:
+            out["val_rm_bce"], out["val_rm_soft_ts"] = s["rm_parts"]
         target_rm = torch.stack(tuple(road_image), dim=0).float()
         out.update(road_map_scores(target_rm, s["probs"]))
         averaged = _tta.resolve(self, None) is not None
@@ -319,7 +327,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         """The mean of every per-batch value as ``avg_*``; ``val_loss`` is the monitored value; under ``hparams.calibrate_threshold``
         ``rm_threshold`` is set from the epoch's summed histogram, as in ``RoadMapBCE``."""
         keys = ("val_loss", "val_roadmap_loss", "val_bbox_loss", "val_bce", "val_soft_ts", "val_ts", "val_ts_rounded", "val_ats_gt_rm",
-                "val_ats", "val_box_ts", "val_ats_tta") + TTA_ROAD_KEYS
+                "val_ats", "val_box_ts", "val_ats_tta") + TTA_ROAD_KEYS + RM_LOSS_KEYS
         logs = mean_logs(outputs, keys)
         self._calibrate(outputs, logs)
         if self._wants_box_sweep():
@@ -348,4 +356,5 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         add_augment_args(p)
         _tta.add_tta_args(p)
         add_ema_args(p)
+        add_rm_loss_args(p)
         return p

@@ -87,6 +87,59 @@ def road_map_scores(target_rm, probs):
     return {"val_ts": ops.threat_score(target_rm, probs), "val_ts_rounded": ops.threat_score(target_rm, probs, round_b=True)}
 
 
+RM_LOSS_KEYS = ("val_rm_bce", "val_rm_soft_ts")      # validation's components of the road-map loss, under an ``rm_*`` setting
+
+
+def rm_loss_config(hparams):
+    """The road-map loss as the hparams ask for it: None when it is off (``rm_pos_weight`` None, ``rm_ts_weight`` 0, ``rm_bce_weight`` 1:
+    the reference's mean BCE-with-logits, roadmap_bce_v2.py:106), else the keyword arguments of ``rm_loss.road_map_loss`` -- weighted
+    BCE-with-logits plus the soft threat score on the logits.  ``rm_pos_weight``: None, a positive number (or a string
+    that parses as one), or "auto" = each sample's own negatives / positives.  A value the kernels would refuse raises ValueError
+    here, when the module is built.  ``rm_loss`` itself is imported by the step that takes the loss, not here."""
+    pos_weight = hparam(hparams, "rm_pos_weight", None)
+    if isinstance(pos_weight, str) and pos_weight != "auto":
+        try:
+            pos_weight = float(pos_weight)
+        except ValueError:
+            raise ValueError(f"rm_pos_weight must be a positive number or 'auto', got {pos_weight!r}") from None
+    if pos_weight is not None and pos_weight != "auto":
+        if isinstance(pos_weight, bool) or not isinstance(pos_weight, (int, float)) or not 0 < pos_weight < float("inf"):
+            raise ValueError(f"rm_pos_weight must be a positive number or 'auto', got {pos_weight!r}")
+        pos_weight = float(pos_weight)
+    weights = {}
+    for name, default in (("rm_bce_weight", 1.0), ("rm_ts_weight", 0.0), ("rm_ts_eps", 1.0)):
+        try:
+            weights[name] = float(hparam(hparams, name, default))
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {hparam(hparams, name, default)!r}") from None
+        if not 0 <= weights[name] < float("inf"):
+            raise ValueError(f"{name} must be a finite number >= 0, got {weights[name]!r}")
+    if weights["rm_bce_weight"] == 0 and weights["rm_ts_weight"] == 0:
+        raise ValueError("rm_bce_weight and rm_ts_weight are both 0: the loss would be constant")
+    if pos_weight is None and weights["rm_ts_weight"] == 0 and weights["rm_bce_weight"] == 1:
+        return None
+    return {"pos_weight": pos_weight, "bce_weight": weights["rm_bce_weight"], "ts_weight": weights["rm_ts_weight"], "ts_eps": weights["rm_ts_eps"]}
+
+
+def add_rm_loss_args(p):
+    """``--rm_pos_weight`` / ``--rm_bce_weight`` / ``--rm_ts_weight`` / ``--rm_ts_eps``, for the modules with a road-map head on logits."""
+    p.add_argument("--rm_pos_weight", type=str, default=None,
+                   help="road-map loss: weight of the positive (road) elements in the BCE: a positive number, or 'auto' = each sample's own "
+                        "negatives / positives; default: unweighted (the reference's loss)")
+    p.add_argument("--rm_bce_weight", type=float, default=1.0, help="road-map loss: factor of the (weighted) BCE-with-logits term")
+    p.add_argument("--rm_ts_weight", type=float, default=0.0,
+                   help="road-map loss: factor of the soft threat-score term 1 - (I + eps) / (U + eps), per sample; 0 = off")
+    p.add_argument("--rm_ts_eps", type=float, default=1.0, help="road-map loss: eps of the soft threat score (>= 0)")
+    return p
+
+
+def road_map_loss_parts(setting, logits, target):
+    """The loss of ``rm_loss_config``'s ``setting`` (not None) on ``logits`` [B, P] -> (loss, probs [B, P], (L_bce, L_ts))."""
+    from . import rm_loss      # here, not at the top: a model with the rm_* hparams off never imports or loads the library
+    loss, probs, bce, ts, _ = rm_loss.road_map_loss(logits, target, return_parts=True, **setting)
+    return loss, probs, (bce, ts)
+
+
 class CalibratedThreshold:
     """What a module with a road-map head needs to calibrate its operating point on validation data (hparams.calibrate_threshold)
     and to carry it: the ``rm_threshold`` property, the per-batch histogram and the epoch's argmax.  Shared by the road-map modules
@@ -119,9 +172,13 @@ class CalibratedThreshold:
 
 
 class RoadMapBCE(CalibratedThreshold, LightningModule):
+    rm_loss = None      # rm_loss_config(hparams): None = mean BCE-with-logits, the reference's loss
+    _rm_parts = None    # (L_bce, L_ts) of the last ``_run_step`` under a setting
+
     def __init__(self, hparams):
         super().__init__()
         self.hparams = hparams
+        self.rm_loss = rm_loss_config(hparams)
         self.output_dim = 800 * 800
         # pretrained feature extractor (roadmap_bce_v2.py:43-47); ``pretrained_ae`` lets callers hand in
         # an already-built BasicAE when no checkpoint file exists (the reference's paths are NYU-local)
@@ -183,7 +240,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
             # (a pointer table) instead of torch.stack-ing them first (roadmap_bce_v2.py:87)
             pred_rm = self._logits(sample, keeps)
             b = len(per_sample)
-            loss, probs = ops.BceWithLogitsProbs.apply(pred_rm.reshape(b, -1), per_sample)
+            loss, probs = self._loss_and_probs(pred_rm.reshape(b, -1), per_sample)
             return loss, None, pred_rm, probs.reshape(b, 800, 800)
         masks = torch.stack(per_sample, dim=0)            # bool as the dataset hands them over (data_helper.py:137-139)
         # self(sample) of the reference = (logits, probabilities); here the probabilities come out of the loss kernel's pass
@@ -193,11 +250,19 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         target_rm = masks.float() if (logging or step_name != "train" or masks.dtype.is_floating_point) else masks
         batch_size = masks.size(0)
         loss_target = masks if masks.dtype in (torch.bool, torch.uint8) else target_rm
-        loss, probs = ops.BceWithLogitsProbs.apply(pred_rm.reshape(batch_size, -1), loss_target.reshape(batch_size, -1).contiguous())
+        loss, probs = self._loss_and_probs(pred_rm.reshape(batch_size, -1), loss_target.reshape(batch_size, -1).contiguous())
         pred_logit_rm = probs.reshape(batch_size, 800, 800)
         if logging:
             self._log_rm_images(self.wide_stitch_six_images(sample), target_rm, pred_logit_rm, step_name)
         return loss, target_rm, pred_rm, pred_logit_rm
+
+    def _loss_and_probs(self, logits, target):
+        """(loss, sigmoid(logits)) of ``logits`` [B, P] from one pass: the reference's mean BCE-with-logits, or under an ``rm_*`` setting
+        (``rm_loss_config``) the weighted BCE + soft threat score, whose two components are then kept in ``_rm_parts``."""
+        if self.rm_loss is None:
+            return ops.BceWithLogitsProbs.apply(logits, target)
+        loss, probs, self._rm_parts = road_map_loss_parts(self.rm_loss, logits, target)
+        return loss, probs
 
     def _log_rm_images(self, x, target_rm, pred_rm, step_name, limit=1):
         exp = self.logger.experiment
@@ -212,14 +277,21 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
             self.ae.unfreeze()
         batch = self.augment.apply(batch)
         train_loss, _, _, _ = self._run_step(batch, batch_idx, step_name="train")
-        return {"loss": train_loss, "log": {"train_loss": train_loss}}
+        log = {"train_loss": train_loss}
+        if self.rm_loss is not None:
+            log["rm_bce"], log["rm_soft_ts"] = self._rm_parts
+        return {"loss": train_loss, "log": log}
 
     def validation_step(self, batch, batch_idx):
         """Under ``hparams.tta_mirror`` also a mirrored pass (``no_grad``) and ``val_ts_tta`` / ``val_ts_rounded_tta``, the scores of the
         averaged probabilities; ``ts_hist`` (``hparams.calibrate_threshold``) is then taken from those, so ``rm_threshold`` is
-        calibrated in the mode the checkpoint predicts in.  ``val_loss``, ``val_ts`` and ``val_ts_rounded`` keep their meaning."""
+        calibrated in the mode the checkpoint predicts in.  ``val_loss``, ``val_ts`` and ``val_ts_rounded`` keep their meaning.  Under an
+        ``rm_*`` setting ``val_loss`` is the composite loss and ``val_rm_bce`` / ``val_rm_soft_ts`` its two components; the scores and
+        ``ts_hist`` read the loss pass's probabilities as before."""
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, **road_map_scores(target_rm, pred_logit_rm)}
+        if self.rm_loss is not None:
+            out["val_rm_bce"], out["val_rm_soft_ts"] = self._rm_parts
         if _tta.resolve(self, None) is None:
             return self._with_ts_hist(out, pred_logit_rm, target_rm)
         with torch.no_grad():
@@ -229,7 +301,8 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
-        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS if outputs and all(k in x for x in outputs)})
+        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS + RM_LOSS_KEYS
+                     if outputs and all(k in x for x in outputs)})
         self._calibrate(outputs, logs)
         return {"val_loss": avg["val_loss"], "log": logs}
 
@@ -252,11 +325,19 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         add_augment_args(p)
         _tta.add_tta_args(p)
         add_ema_args(p)
+        add_rm_loss_args(p)
         return p
 
 
 class RoadMap(RoadMapBCE):
-    """MSE twin (roadmap_pretrain_ae.py): sigmoid inside ``forward``, ``mse_loss(target, pred)``, unfreeze at epoch 30."""
+    """MSE twin (roadmap_pretrain_ae.py): sigmoid inside ``forward``, ``mse_loss(target, pred)``, unfreeze at epoch 30.  Its loss is taken
+    from the probabilities: the ``rm_*`` hparams select a loss on logits and are refused."""
+
+    def __init__(self, hparams):
+        super().__init__(hparams)
+        if self.rm_loss is not None:
+            raise ValueError("rm_pos_weight / rm_bce_weight / rm_ts_weight select a loss on the road-map head's logits; RoadMap (roadmap_mse) "
+                             "trains on the MSE of its probabilities: use RoadMapBCE")
 
     def forward(self, x, keeps=(None, None)):
         """-> sigmoid(Linear(z)) [B,800,800], differentiable (roadmap_pretrain_ae.py:67-82)."""
