@@ -238,20 +238,25 @@ def size(name, *args):
 
 # ---- extension libraries --------------------------------------------------------------------------------------------------------
 class Extension:
-    """The binder of an extension library: launch functions that are not part of include/dd_hotpath.h (its set of functions is
-    pinned), declared in a header of their own and built into a library of their own that links against ``libdd_hotpath.so`` for
-    ``dd_fail`` / ``dd_last_error()`` (build.py).  ``augment.py`` and ``tta.py`` each hold one and publish its parts as module-level
-    names.  The ctypes table comes from the header through ``parse_header`` -- the one parser -- and ``launch(name, *operands)`` enters
-    a function the way ``call`` does: looked up on the ``CDLL`` at every call, operands in header order, the current torch stream
-    appended, ``HotpathError`` with the library's message on a non-zero return.  ``what``: the missing-library message's noun."""
+    """The binder of an extension library, from its entry in ``build.EXTENSIONS``: launch functions that are not part of
+    include/dd_hotpath.h (its set of functions is pinned), declared in a header of their own and built into a library of their own that
+    links against ``libdd_hotpath.so`` for ``dd_fail`` / ``dd_last_error()`` (build.py).  The module of each extension holds one and
+    publishes its parts as module-level names.  The ctypes table comes from the header through ``parse_header`` -- the one parser -- and
+    ``launch(name, *operands)`` enters a function the way ``call`` does: looked up on the ``CDLL`` at every call, operands in header
+    order, the current torch stream appended, ``HotpathError`` with the library's message on a non-zero return."""
 
-    def __init__(self, header, library, what):
-        self.header, self.library, self.what = header, library, what
-        with open(header) as f:
-            self.signatures, self.streamed = parse_header(f.read())
+    def __init__(self, entry):
+        self.header, self.library, self.what = entry.header, entry.lib, entry.what      # ``what``: the missing-library message's noun
+        with open(self.header) as f:
+            self.text = f.read()
+        self.signatures, self.streamed = parse_header(self.text)
         # every function ends in the stream, which launch() appends
         self.operands = {name: len(args) - 1 for name, (res, args) in self.signatures.items()}
         self._handle = None
+
+    def constant(self, name, cast=int):
+        """The number a ``#define`` of the header gives ``name``, brackets and a float's ``f`` taken off: ``(-1.0f)`` is -1.0 to float."""
+        return cast(re.search(rf"^#define {name} \(?(-?[\d.]+)f?\)?", self.text, re.M).group(1))
 
     def lib(self):
         """Load the library once, after the main library (it links against it: ``dd_fail``); raise when it is absent."""

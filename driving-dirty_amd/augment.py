@@ -24,7 +24,7 @@ from ._lib import HotpathError
 from .lightning import hparam
 
 # ---- the binder ------------------------------------------------------------------------------------------------------------------
-_EXT = _lib.Extension(_build.AUG_HEADER, _build.AUG_LIB, "the augmentation")      # the one binder of an extension library (_lib.py)
+_EXT = _lib.Extension(_build.EXTENSIONS["augment"])      # the one binder of an extension library (_lib.py)
 LIB, SIGNATURES, STREAMED, OPERANDS = _EXT.library, _EXT.signatures, _EXT.streamed, _EXT.operands
 lib, launch, last_error = _EXT.lib, _EXT.launch, _EXT.last_error      # module-level names: the functions below reach ``launch`` through the module's globals at call time
 CHUNK = 32      # samples per kernel launch: kChunk of csrc/augment.hip (pointers, flags and colours travel in the kernel arguments)

@@ -6,7 +6,7 @@
 // A workgroup belongs to one sample; no atomics, every sum has a fixed order: two launches give the same bits.
 #include <limits.h>
 
-#include "dd_common.h"
+#include "dd_loss_stats.h"
 
 namespace {
 
@@ -18,33 +18,13 @@ constexpr int kGradQuads = 4;            // quads per thread of the gradient pas
 
 int stats_blocks(long n4) { return (int)max(1L, min((long)kMaxBlocksPerSample, (n4 + kThreads * kRun - 1) / (kThreads * kRun))); }
 
-// The workgroup's totals of the threads' kStats sums, in a fixed order: the lanes of a wave by shuffle, then the four waves; thread k < kStats
-// writes total k to out[k].
-__device__ __forceinline__ void block_sum(const double (&acc)[kStats], double* __restrict__ out) {
-  __shared__ double red[kStats][kThreads / 64];
-  static_assert(kThreads == 256, "block_sum adds four waves");
-#pragma unroll
-  for (int k = 0; k < kStats; ++k) {
-    double d = acc[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = d;
-  }
-  __syncthreads();
-  if (threadIdx.x < kStats) {
-    const double* r = red[threadIdx.x];
-    out[threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
-  }
-}
-
 template <typename TT>
 __device__ __forceinline__ f32x4 load_target4(const TT* t, long quad);
 template <>
 __device__ __forceinline__ f32x4 load_target4<float>(const float* t, long quad) { return ((const f32x4*)t)[quad]; }
 template <>
 __device__ __forceinline__ f32x4 load_target4<unsigned char>(const unsigned char* t, long quad) {
-  const unsigned w = ((const unsigned*)t)[quad];
-  return f32x4{(float)(w & 0xff), (float)((w >> 8) & 0xff), (float)((w >> 16) & 0xff), (float)(w >> 24)};
+  return dd_bytes_f32x4(((const unsigned*)t)[quad]);
 }
 
 // -max(log p, -100) and -max(log(1 - p), -100).  u = fl(1 - p) loses up to half an ulp of 1, which is 1.5e-6 of log(1 - p) at
@@ -94,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void box_loss_stats_kernel(const float* _
 #pragma unroll
     for (int k = 0; k < kStats; ++k) acc[k] += (double)s[k];
   }
-  block_sum(acc, partial + (long)blockIdx.x * kStats);
+  dd_block_sum<kStats, kThreads>(acc, partial + (long)blockIdx.x * kStats);
 }
 
 // One workgroup; wave w takes the samples w, w + 4, ...: lane l adds the partials of workgroups l, l + 64, ... of the sample, the lanes
@@ -108,26 +88,8 @@ __global__ __launch_bounds__(kThreads) void box_loss_final_kernel(const double* 
   double bce = 0.0, ts = 0.0;
   for (int b = wave; b < batch; b += kThreads / 64) {
     double v[kStats] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int j = lane; j < bps; j += 64) {
-#pragma unroll
-      for (int k = 0; k < kStats; ++k) v[k] += partial[((long)b * bps + j) * kStats + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kStats; ++k) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o);
-    }
-    if (lane == 0) {
-      const double T = v[0], S = v[1], I = v[2], A = v[3], Cq = v[4];
-      const double w = pos_weight == DD_POS_WEIGHT_AUTO ? (per_sample - T) / fmax(T, 1.0) : (double)pos_weight;
-      const double den = S + T - I + eps, num = I + eps;
-      bce += w * A + Cq;
-      ts += 1.0 - num / den;
-#pragma unroll
-      for (int k = 0; k < kStats; ++k) stats[(long)b * kStats + k] = v[k];
-      *(f32x4*)(coef + 4L * b) = f32x4{(float)(alpha * w * inv_bp), (float)(alpha * inv_bp), (float)(beta * inv_b / den),
-                                       (float)(beta * inv_b * num / (den * den))};
-    }
+    dd_sample_sum(partial, b, bps, lane, v);
+    if (lane == 0) dd_sample_finish(v, b, per_sample, pos_weight, DD_POS_WEIGHT_AUTO, alpha, beta, eps, inv_b, inv_bp, bce, ts, stats, coef);
   }
   if (lane == 0) {
     red[0][wave] = bce;

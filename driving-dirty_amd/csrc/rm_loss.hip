@@ -1,7 +1,7 @@
 // The road-map loss on the head's logits (include/dd_rm_loss.h; csrc/libdd_rm_loss.so, a library of its own):
 //   dd_rm_loss_fwd / dd_rm_loss_fwd_u8_ptrs   weighted BCE-with-logits + soft threat score, the probabilities beside them
 //   dd_rm_loss_bwd / dd_rm_loss_bwd_u8_ptrs   dL/dlogits from the saved probabilities
-// The logit-domain counterpart of box_loss.hip, and the same plan: a statistics pass that reduces five sums per sample, from which the
+// The logit-domain counterpart of box_loss.hip, and the same plan (what the two share is dd_loss_stats.h): a statistics pass that reduces five sums per sample, from which the
 // loss for ANY weight comes out (the per-sample "auto" weight needs T before it can weigh A), a finalise launch that turns them into
 // four gradient coefficients per sample, and a gradient pass that divides by no statistic and calls no transcendental.
 // Both big passes are streams.  A workgroup takes one piece of kChunk elements of ONE sample (the target's pointer -- a table entry in
@@ -14,7 +14,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "dd_common.h"
+#include "dd_loss_stats.h"
 
 #include "../../include/dd_rm_loss.h"
 
@@ -34,10 +34,7 @@ struct TargetF32 {
   __device__ __forceinline__ Sample sample(int b, long per) const { return t + (long)b * per; }
   static __device__ __forceinline__ f32x4 quad(Sample s, long i) { return *(const f32x4*)(s + i); }
 };
-__device__ __forceinline__ f32x4 bytes4(const unsigned char* s, long i) {
-  const unsigned w = *(const unsigned*)(s + i);
-  return f32x4{(float)(w & 0xff), (float)((w >> 8) & 0xff), (float)((w >> 16) & 0xff), (float)(w >> 24)};
-}
+__device__ __forceinline__ f32x4 bytes4(const unsigned char* s, long i) { return dd_bytes_f32x4(*(const unsigned*)(s + i)); }
 struct TargetU8 {
   const unsigned char* t;
   typedef const unsigned char* Sample;
@@ -50,25 +47,6 @@ struct TargetPtrs {      // by value in the kernel arguments
   __device__ __forceinline__ Sample sample(int b, long) const { return p[b]; }
   static __device__ __forceinline__ f32x4 quad(Sample s, long i) { return bytes4(s, i); }
 };
-
-// The workgroup's totals of the threads' kStats sums, in a fixed order (box_loss.hip's scheme): the lanes of a wave by shuffle, then
-// the four waves; thread k < kStats writes total k to out[k].
-__device__ __forceinline__ void block_sum(const double (&acc)[kStats], double* __restrict__ out) {
-  __shared__ double red[kStats][kThreads / 64];
-  static_assert(kThreads == 256, "block_sum adds four waves");
-#pragma unroll
-  for (int k = 0; k < kStats; ++k) {
-    double d = acc[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = d;
-  }
-  __syncthreads();
-  if (threadIdx.x < kStats) {
-    const double* r = red[threadIdx.x];
-    out[threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
-  }
-}
 
 // THE per-vector function of the forward: the probabilities of four logits, and their terms added to the thread's fp32 sums
 __device__ __forceinline__ f32x4 stat_quad(const f32x4 z, const f32x4 t, float (&s)[kStats]) {
@@ -127,7 +105,7 @@ __global__ __launch_bounds__(kThreads) void rm_loss_stats_kernel(const float* __
   double acc[kStats];
 #pragma unroll
   for (int k = 0; k < kStats; ++k) acc[k] = (double)s[k];
-  block_sum(acc, partial + (long)blockIdx.x * kStats);
+  dd_block_sum<kStats, kThreads>(acc, partial + (long)blockIdx.x * kStats);
 }
 
 // One workgroup of sixteen waves; wave w takes the samples w, w + 16, ...: lane l adds the partials of pieces l, l + 64, ... of the
@@ -144,26 +122,8 @@ __global__ __launch_bounds__(kFinalThreads) void rm_loss_final_kernel(const doub
   double bce = 0.0, ts = 0.0;
   for (int b = wave; b < batch; b += kWaves) {
     double v[kStats] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int j = lane; j < pps; j += 64) {
-#pragma unroll
-      for (int k = 0; k < kStats; ++k) v[k] += partial[((long)b * pps + j) * kStats + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kStats; ++k) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o);
-    }
-    if (lane == 0) {
-      const double T = v[0], S = v[1], I = v[2], A = v[3], Cq = v[4];
-      const double w = pos_weight == DD_RM_POS_WEIGHT_AUTO ? (per - T) / fmax(T, 1.0) : (double)pos_weight;
-      const double den = S + T - I + eps, num = I + eps;
-      bce += w * A + Cq;
-      ts += 1.0 - num / den;
-#pragma unroll
-      for (int k = 0; k < kStats; ++k) stats[(long)b * kStats + k] = v[k];
-      *(f32x4*)(coef + 4L * b) = f32x4{(float)(alpha * w * inv_bp), (float)(alpha * inv_bp), (float)(beta * inv_b / den),
-                                       (float)(beta * inv_b * num / (den * den))};
-    }
+    dd_sample_sum(partial, b, pps, lane, v);
+    if (lane == 0) dd_sample_finish(v, b, per, pos_weight, DD_RM_POS_WEIGHT_AUTO, alpha, beta, eps, inv_b, inv_bp, bce, ts, stats, coef);
   }
   if (lane == 0) {
     red[0][wave] = bce;

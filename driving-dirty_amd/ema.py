@@ -3,8 +3,7 @@ iterate.
 
 The next tool against over-fitting after the class-balanced losses, the calibrated thresholds, the augmentation and the mirror
 averaging: it costs no forward pass and composes with all of them.  Two parts.  The BINDER of ``csrc/libdd_ema.so``
-(``include/dd_ema.h``), a ``_lib.Extension`` as ``augment.py``'s and ``tta.py``'s: a library of its own because the sets of functions
-of the three other headers are pinned.  And ``WeightEMA``, which ``train.TrainStep`` holds when ``--ema_decay`` is set.
+(``include/dd_ema.h``), a ``_lib.Extension`` of its entry in ``build.EXTENSIONS``.  And ``WeightEMA``, which ``train.TrainStep`` holds when ``--ema_decay`` is set.
 
 THE SEMANTICS are the header's: per element ``e' = fmaf(alpha, w - e, e)``, one rounded subtract and one fused multiply-add;
 ``e == w`` keeps ``e``'s bits.  The exchange moves 32-bit words.  The cost is 4 bytes per parameter for the shadows and, per update,
@@ -14,7 +13,6 @@ One GPU, fp32 parameters, buffers stay live.
 """
 import contextlib
 import ctypes as C
-import re
 
 import torch
 
@@ -23,18 +21,11 @@ from . import build as _build
 from ._lib import HotpathError
 
 # ---- the binder ------------------------------------------------------------------------------------------------------------------
-_EXT = _lib.Extension(_build.EMA_HEADER, _build.EMA_LIB, "the weight average")
+_EXT = _lib.Extension(_build.EXTENSIONS["ema"])
 LIB, SIGNATURES, STREAMED, OPERANDS = _EXT.library, _EXT.signatures, _EXT.streamed, _EXT.operands
 lib, launch, last_error = _EXT.lib, _EXT.launch, _EXT.last_error      # module-level names: the methods below reach ``launch`` through the module's globals at call time
-
-
-def _constant(name):
-    with open(_build.EMA_HEADER) as f:
-        return int(re.search(rf"^#define {name} (\d+)", f.read(), re.M).group(1))
-
-
-CHUNK = _constant("DD_EMA_CHUNK")              # elements per piece of the kernels' flat work list
-TABLE_MAX = _constant("DD_EMA_TABLE_MAX")      # tensors per launch; a longer table is split
+CHUNK = _EXT.constant("DD_EMA_CHUNK")              # elements per piece of the kernels' flat work list
+TABLE_MAX = _EXT.constant("DD_EMA_TABLE_MAX")      # tensors per launch; a longer table is split
 
 
 def pointer_tables(a, b):

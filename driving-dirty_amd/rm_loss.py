@@ -3,8 +3,7 @@
 The logit-domain counterpart of ``ops.box_loss``.  The box loss works on probabilities: it clamps the logs at -100
 and divides by ``p`` and ``1 - p``, and a confident road-map head has logits past |z| = 17, where ``1 - p`` is 0 in fp32.  Here the
 loss is ``softplus(+-z)`` and the gradient goes through ``p (1 - p)``: finite for every finite logit.  Two parts.  The BINDER of
-``csrc/libdd_rm_loss.so`` (``include/dd_rm_loss.h``), a ``_lib.Extension`` as ``ema.py``'s: a library of its own because the sets of
-functions of the four other headers are pinned.  And ``road_map_loss``, which ``RoadMapBCE`` and ``JointRoadMapBBox`` take when an
+``csrc/libdd_rm_loss.so`` (``include/dd_rm_loss.h``), a ``_lib.Extension`` of its entry in ``build.EXTENSIONS``.  And ``road_map_loss``, which ``RoadMapBCE`` and ``JointRoadMapBBox`` take when an
 ``rm_*`` hparam is set (``roadmap.rm_loss_config`` parses them, ``roadmap.add_rm_loss_args`` are the flags); with all of them at their
 defaults neither imports this module.
 
@@ -16,7 +15,6 @@ One GPU, fp32 logits.  The loss is a per-rank quantity: under data-parallel trai
 and ``ddp.GradSync`` averages the gradients, as for every other loss of the package.
 """
 import ctypes as C
-import re
 
 import torch
 
@@ -25,19 +23,12 @@ from . import build as _build
 from ._lib import HotpathError
 
 # ---- the binder ------------------------------------------------------------------------------------------------------------------
-_EXT = _lib.Extension(_build.RM_LOSS_HEADER, _build.RM_LOSS_LIB, "the road-map loss")
+_EXT = _lib.Extension(_build.EXTENSIONS["rm_loss"])
 LIB, SIGNATURES, STREAMED, OPERANDS = _EXT.library, _EXT.signatures, _EXT.streamed, _EXT.operands
 lib, launch, last_error = _EXT.lib, _EXT.launch, _EXT.last_error      # module-level names: the functions below reach ``launch`` through the module's globals at call time
-
-
-def _constant(name, number=r"\d+"):
-    with open(_build.RM_LOSS_HEADER) as f:
-        return re.search(rf"^#define {name} \(?(-?{number})f?\)?", f.read(), re.M).group(1)
-
-
-CHUNK = int(_constant("DD_RM_LOSS_CHUNK"))                 # elements per piece: a workgroup's share of one sample
-TABLE_MAX = int(_constant("DD_RM_LOSS_TABLE_MAX"))         # per-sample masks of a pointer table; a longer tuple is stacked
-POS_WEIGHT_AUTO = float(_constant("DD_RM_POS_WEIGHT_AUTO", r"\d+\.\d*"))
+CHUNK = _EXT.constant("DD_RM_LOSS_CHUNK")                  # elements per piece: a workgroup's share of one sample
+TABLE_MAX = _EXT.constant("DD_RM_LOSS_TABLE_MAX")          # per-sample masks of a pointer table; a longer tuple is stacked
+POS_WEIGHT_AUTO = _EXT.constant("DD_RM_POS_WEIGHT_AUTO", float)
 TARGET_F32, TARGET_U8 = 0, 1                               # dd_hotpath.h: DD_TARGET_F32 / DD_TARGET_U8
 ACC_TERMS = CHUNK // 256                                   # elements a thread adds in fp32 before it goes to fp64
 

@@ -3,8 +3,7 @@ average the PROBABILITIES before the threshold.
 
 The other half of ``augment.py``'s mirror: a model trained with ``--aug_mirror`` has seen both orientations of every
 scene, and this is how a prediction uses both.  Two parts.  The BINDER of ``csrc/libdd_tta.so`` (``include/dd_tta.h``), a
-``_lib.Extension`` as ``augment.py``'s: a library of its own because the sets of functions of ``include/dd_hotpath.h`` and
-``include/dd_augment.h`` are pinned.  And the pieces a model's ``predict_*`` / ``validation_step`` are composed of: ``mirror_views``,
+``_lib.Extension`` of its entry in ``build.EXTENSIONS``.  And the pieces a model's ``predict_*`` / ``validation_step`` are composed of: ``mirror_views``,
 ``mirror_masks``, ``mean_prob``, ``mean_gt``, ``resolve``.
 
 THE SEMANTICS are the header's: ``mean[b,r,c] = 0.5f * (P(a[b,r,c]) + P(m[b,h-1-r,c]))`` with ``a`` from the scene and ``m`` from the
@@ -25,7 +24,7 @@ from ._lib import HotpathError
 from .lightning import hparam
 
 # ---- the binder ------------------------------------------------------------------------------------------------------------------
-_EXT = _lib.Extension(_build.TTA_HEADER, _build.TTA_LIB, "mirror test-time averaging")
+_EXT = _lib.Extension(_build.EXTENSIONS["tta"])
 LIB, SIGNATURES, STREAMED, OPERANDS = _EXT.library, _EXT.signatures, _EXT.streamed, _EXT.operands
 lib, launch, last_error = _EXT.lib, _EXT.launch, _EXT.last_error      # module-level names: the functions below reach ``launch`` through the module's globals at call time
 

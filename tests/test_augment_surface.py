@@ -2,7 +2,6 @@
 the augmenter's draws, defaults, flags and errors, and the box mirror."""
 import ctypes as C
 import os
-import struct
 from argparse import ArgumentParser, Namespace
 
 import numpy as np
@@ -10,41 +9,21 @@ import pytest
 import torch
 
 import _augment_ref as ref
+from _surface import exported_symbols, header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AUG = dict(aug_mirror=0.5, aug_brightness=0.2, aug_contrast=0.1, aug_per_view=0.05, aug_view_drop=0.25, aug_seed=7)
-
-
-def exported_symbols(path):
-    """Names the shared library DEFINES in its dynamic symbol table (ELF64, little endian), read with ``struct``."""
-    data = open(path, "rb").read()
-    assert data[:6] == b"\x7fELF\x02\x01", "an ELF64 little-endian file"
-    shoff, = struct.unpack_from("<Q", data, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
-    names = set()
-    for s in sections:
-        if s[1] != 11:      # SHT_DYNSYM
-            continue
-        stroff = sections[s[6]][4]
-        for off in range(s[4], s[4] + s[5], 24):
-            st_name, _info, _other, shndx = struct.unpack_from("<IBBH", data, off)
-            if shndx != 0 and st_name:
-                end = data.index(b"\0", stroff + st_name)
-                names.add(data[stroff + st_name:end].decode())
-    return names
 
 
 def test_header_declares_launch_functions_of_its_own_and_the_library_exports_exactly_them():
     from driving_dirty_amd import _lib, augment, build
-    signatures, streamed = _lib.parse_header(open(os.path.join(ROOT, "include", "dd_augment.h")).read())
+    signatures, streamed = header("dd_augment.h")
     assert set(signatures) == {"dd_aug_views_u8_ptrs", "dd_aug_views_ptrs", "dd_aug_masks_u8_ptrs"}
     assert set(signatures) == set(streamed), "every function of dd_augment.h is a launch function (void* stream last)"
     assert all(n.startswith("dd_aug_") for n in signatures)
     assert not set(signatures) & set(_lib.SIGNATURES)
     assert augment.SIGNATURES == signatures and augment.OPERANDS == {n: len(a) - 1 for n, (_, a) in signatures.items()}
-    assert os.path.exists(build.AUG_LIB), "build the HIP libraries first (python __graft_entry__.py)"
-    assert {n for n in exported_symbols(build.AUG_LIB) if n.startswith("dd_")} == set(signatures)
+    assert os.path.exists(build.EXTENSIONS["augment"].lib), "build the HIP libraries first (python __graft_entry__.py)"
+    assert {n for n in exported_symbols(build.EXTENSIONS["augment"].lib) if n.startswith("dd_")} == set(signatures)
     assert build.build(force=False, verbose=False) == build.LIB and not build.needs_build()
     assert "launch" in vars(augment) and "call" not in vars(augment) and "size" not in vars(augment)
 

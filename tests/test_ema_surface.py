@@ -3,20 +3,13 @@ shares with the augmentation and the mirror averaging, the decay schedule as num
 import ctypes as C
 import math
 import os
-import sys
 from argparse import ArgumentParser, Namespace
 
 import pytest
 
-from test_augment_surface import exported_symbols
+from _surface import ROOT, exported_symbols, header, kernel_resources
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = {"dd_ema_update_ptrs", "dd_ema_swap_ptrs"}
-
-
-def header(name):
-    from driving_dirty_amd import _lib
-    return _lib.parse_header(open(os.path.join(ROOT, "include", name)).read())
 
 
 def models():
@@ -31,12 +24,10 @@ def test_header_declares_the_two_launch_functions_and_the_library_exports_exactl
     from driving_dirty_amd import build, ema
     signatures, streamed = header("dd_ema.h")
     assert set(signatures) == FUNCTIONS and set(streamed) == FUNCTIONS, "both are launch functions (void* stream last)"
-    for other in ("dd_hotpath.h", "dd_augment.h", "dd_tta.h"):
-        assert not FUNCTIONS & set(header(other)[0]), other
     assert ema.SIGNATURES == signatures and ema.STREAMED == streamed
     assert ema.OPERANDS == {"dd_ema_update_ptrs": 5, "dd_ema_swap_ptrs": 4}
-    assert os.path.exists(build.EMA_LIB), "build the HIP libraries first (python __graft_entry__.py)"
-    assert {n for n in exported_symbols(build.EMA_LIB) if n.startswith("dd_")} == FUNCTIONS
+    assert os.path.exists(build.EXTENSIONS["ema"].lib), "build the HIP libraries first (python __graft_entry__.py)"
+    assert {n for n in exported_symbols(build.EXTENSIONS["ema"].lib) if n.startswith("dd_")} == FUNCTIONS
     assert build.build(force=False, verbose=False) == build.LIB and not build.needs_build()
 
 
@@ -53,7 +44,7 @@ def test_one_binder_serves_the_three_extension_libraries():
         fn = vars(ema)[name]      # module-level names, so that a monkeypatched ``launch`` takes effect
         assert isinstance(fn.__self__, _lib.Extension) and fn.__func__ is getattr(_lib.Extension, name)
         assert fn.__self__ is ema.lib.__self__
-    assert ema.LIB == build.EMA_LIB and ema.SIGNATURES == header("dd_ema.h")[0]
+    assert ema.LIB == build.EXTENSIONS["ema"].lib and ema.SIGNATURES == header("dd_ema.h")[0]
     assert "call" not in vars(ema) and "size" not in vars(ema)
     assert ema.lib.__self__ is not augment.lib.__self__ and ema.lib.__self__ is not tta.lib.__self__
     assert ema.lib() is ema.lib()
@@ -67,12 +58,7 @@ def test_one_binder_serves_the_three_extension_libraries():
 
 def test_the_kernels_use_no_scratch_no_lds_and_no_spills():
     from driving_dirty_amd import build
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import kernel_resources
-    finally:
-        sys.path.pop(0)
-    ks = kernel_resources.kernels(build.EMA_LIB)
+    ks = kernel_resources().kernels(build.EXTENSIONS["ema"].lib)
     assert len(ks) == 2, [k[".name"] for k in ks]      # one kernel per function: the whole table, every size
     for k in ks:
         assert k[".private_segment_fixed_size"] == 0 and k[".group_segment_fixed_size"] == 0, k[".name"]

@@ -7,16 +7,10 @@ from argparse import ArgumentParser, Namespace
 
 import pytest
 
-from test_augment_surface import exported_symbols
+from _surface import ROOT, exported_symbols, header, kernel_resources
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = {"dd_rm_loss_fwd", "dd_rm_loss_fwd_u8_ptrs", "dd_rm_loss_bwd", "dd_rm_loss_bwd_u8_ptrs"}
 FLAGS_OFF = dict(rm_pos_weight=None, rm_bce_weight=1.0, rm_ts_weight=0.0, rm_ts_eps=1.0)
-
-
-def header(name):
-    from driving_dirty_amd import _lib
-    return _lib.parse_header(open(os.path.join(ROOT, "include", name)).read())
 
 
 def road_map_models():
@@ -34,17 +28,16 @@ def tiny(cls, **hp):
 
 def test_header_declares_the_four_launch_functions_and_the_library_exports_exactly_them():
     from driving_dirty_amd import build, rm_loss
+    entry = build.EXTENSIONS["rm_loss"]
     signatures, streamed = header("dd_rm_loss.h")
     assert set(signatures) == FUNCTIONS and set(streamed) == FUNCTIONS, "all four are launch functions (void* stream last): no size query"
-    for other in ("dd_hotpath.h", "dd_augment.h", "dd_tta.h", "dd_ema.h"):
-        assert not FUNCTIONS & set(header(other)[0]), other
     assert rm_loss.SIGNATURES == signatures and rm_loss.STREAMED == streamed
     assert rm_loss.OPERANDS == {"dd_rm_loss_fwd": 15, "dd_rm_loss_fwd_u8_ptrs": 14, "dd_rm_loss_bwd": 8, "dd_rm_loss_bwd_u8_ptrs": 7}
-    assert os.path.exists(build.RM_LOSS_LIB), "build the HIP libraries first (python __graft_entry__.py)"
-    assert {n for n in exported_symbols(build.RM_LOSS_LIB) if n.startswith("dd_")} == FUNCTIONS
+    assert os.path.exists(entry.lib), "build the HIP libraries first (python __graft_entry__.py)"
+    assert {n for n in exported_symbols(entry.lib) if n.startswith("dd_")} == FUNCTIONS
     assert build.build(force=False, verbose=False) == build.LIB and not build.needs_build()
-    assert build.build_rm_loss(verbose=False) == build.RM_LOSS_LIB
-    assert build.RM_LOSS_SOURCES == ["rm_loss.hip"] and build.RM_LOSS_HEADER in build.RM_LOSS_HEADERS
+    assert build.build_extension("rm_loss", verbose=False) == entry.lib
+    assert entry.sources == ["rm_loss.hip"] and entry.header in entry.headers
 
 
 def test_the_constants_are_the_headers():
@@ -66,7 +59,7 @@ def test_the_binder_is_the_extension_binder():
         fn = vars(rm_loss)[name]      # module-level names, so that a monkeypatched ``launch`` takes effect
         assert isinstance(fn.__self__, _lib.Extension) and fn.__func__ is getattr(_lib.Extension, name)
         assert fn.__self__ is rm_loss.lib.__self__
-    assert rm_loss.LIB == build.RM_LOSS_LIB and "call" not in vars(rm_loss) and "size" not in vars(rm_loss)
+    assert rm_loss.LIB == build.EXTENSIONS["rm_loss"].lib and "call" not in vars(rm_loss) and "size" not in vars(rm_loss)
     assert rm_loss.lib.__self__ is not ema.lib.__self__ and rm_loss.lib() is rm_loss.lib()
     with pytest.raises(rm_loss.HotpathError, match="operands given"):
         rm_loss.launch("dd_rm_loss_bwd", None, None, 0, 1, 4, None, 1.0)
@@ -76,12 +69,7 @@ def test_the_binder_is_the_extension_binder():
 
 def test_the_kernels_use_no_scratch_and_no_spills():
     from driving_dirty_amd import build
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import kernel_resources
-    finally:
-        sys.path.pop(0)
-    ks = kernel_resources.kernels(build.RM_LOSS_LIB)
+    ks = kernel_resources().kernels(build.EXTENSIONS["rm_loss"].lib)
     assert len(ks) == 7, [k[".name"] for k in ks]      # statistics and gradient for the three forms of the target, one finalise
     for k in ks:
         assert k[".private_segment_fixed_size"] == 0, k[".name"]

@@ -2,20 +2,13 @@
 binder it shares with the augmentation, the mode's resolution, the command line, and where the flag is kept."""
 import inspect
 import os
-import sys
 from argparse import ArgumentParser, Namespace
 
 import pytest
 
-from test_augment_surface import exported_symbols
+from _surface import exported_symbols, header, kernel_resources
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = {"dd_tta_mean_prob", "dd_tta_mean_gt"}
-
-
-def header(name):
-    from driving_dirty_amd import _lib
-    return _lib.parse_header(open(os.path.join(ROOT, "include", name)).read())
 
 
 def small_ae():
@@ -38,17 +31,16 @@ def test_header_declares_the_two_launch_functions_and_the_library_exports_exactl
     from driving_dirty_amd import build, tta
     signatures, streamed = header("dd_tta.h")
     assert set(signatures) == FUNCTIONS and set(streamed) == FUNCTIONS, "both are launch functions (void* stream last)"
-    assert not FUNCTIONS & set(header("dd_hotpath.h")[0]) and not FUNCTIONS & set(header("dd_augment.h")[0])
     assert tta.SIGNATURES == signatures and tta.STREAMED == streamed
     assert tta.OPERANDS == {"dd_tta_mean_prob": 7, "dd_tta_mean_gt": 8}
-    assert os.path.exists(build.TTA_LIB), "build the HIP libraries first (python __graft_entry__.py)"
-    assert {n for n in exported_symbols(build.TTA_LIB) if n.startswith("dd_")} == FUNCTIONS
+    assert os.path.exists(build.EXTENSIONS["tta"].lib), "build the HIP libraries first (python __graft_entry__.py)"
+    assert {n for n in exported_symbols(build.EXTENSIONS["tta"].lib) if n.startswith("dd_")} == FUNCTIONS
     assert build.build(force=False, verbose=False) == build.LIB and not build.needs_build()
 
 
 def test_one_binder_serves_both_extension_libraries():
     from driving_dirty_amd import _lib, augment, build, tta
-    for mod, lib, hdr in ((augment, build.AUG_LIB, "dd_augment.h"), (tta, build.TTA_LIB, "dd_tta.h")):
+    for mod, lib, hdr in ((augment, build.EXTENSIONS["augment"].lib, "dd_augment.h"), (tta, build.EXTENSIONS["tta"].lib, "dd_tta.h")):
         for name in ("lib", "launch", "last_error"):
             fn = vars(mod)[name]      # module-level names, so that a monkeypatched ``launch`` takes effect
             assert isinstance(fn.__self__, _lib.Extension) and fn.__func__ is getattr(_lib.Extension, name)
@@ -64,12 +56,7 @@ def test_one_binder_serves_both_extension_libraries():
 
 def test_the_kernels_use_no_scratch_and_no_lds():
     from driving_dirty_amd import build
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import kernel_resources
-    finally:
-        sys.path.pop(0)
-    ks = kernel_resources.kernels(build.TTA_LIB)
+    ks = kernel_resources().kernels(build.EXTENSIONS["tta"].lib)
     assert len(ks) >= 6, [k[".name"] for k in ks]      # vector and scalar forms, bytes and fp32, logits and probabilities
     for k in ks:
         assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0 and k[".group_segment_fixed_size"] == 0, k[".name"]

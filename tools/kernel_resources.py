@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Per-kernel register / scratch / LDS usage read from the gfx950 code objects embedded in csrc/libdd_hotpath.so
-(the AMDGPU metadata note every kernel carries): no recompilation, no GPU.
+"""Per-kernel register / scratch / LDS usage read from the gfx950 code objects embedded in a library (csrc/libdd_hotpath.so, or the
+one --lib names: an extension library, another build) -- the AMDGPU metadata note every kernel carries: no recompilation, no GPU.
 
-    python tools/kernel_resources.py [--spills-only]
-    python tools/kernel_resources.py --diff OTHER_LIB      # kernels whose machine code or resources differ from OTHER_LIB's
+    python tools/kernel_resources.py [--lib MINE] [--spills-only]
+    python tools/kernel_resources.py [--lib MINE] --diff OTHER_LIB      # kernels whose machine code or resources differ from OTHER_LIB's
 """
 import os
 import re
@@ -105,13 +105,14 @@ def kernel_text(lib=LIB):
     return out
 
 
-def diff(other):
-    """Names of the kernels that exist in one library only, or whose machine code or resource counts differ; 0 when there are none."""
-    mine, theirs = kernel_text(LIB), kernel_text(other)
-    res = [{k[".name"]: tuple(k.get(r, 0) for r in RESOURCES) for k in kernels(lib)} for lib in (LIB, other)]
+def diff(other, lib=LIB):
+    """Names of the kernels that exist in one of the two libraries only, or whose machine code or resource counts differ; 0 when there
+    are none."""
+    mine, theirs = kernel_text(lib), kernel_text(other)
+    res = [{k[".name"]: tuple(k.get(r, 0) for r in RESOURCES) for k in kernels(path)} for path in (lib, other)]
     bad = 0
     for name in sorted(set(mine) | set(theirs)):
-        what = ("only in " + os.path.relpath(LIB, ROOT) if name not in theirs else "only in " + other if name not in mine else
+        what = ("only in " + os.path.relpath(lib, ROOT) if name not in theirs else "only in " + other if name not in mine else
                 "code differs" if mine[name] != theirs[name] else "resources differ" if res[0][name] != res[1][name] else None)
         if what:
             bad += 1
@@ -121,11 +122,12 @@ def diff(other):
 
 
 def main():
+    lib = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else LIB
     if "--diff" in sys.argv:
-        sys.exit(diff(sys.argv[sys.argv.index("--diff") + 1]))
-    ks = kernels()
+        sys.exit(diff(sys.argv[sys.argv.index("--diff") + 1], lib))
+    ks = kernels(lib)
     spills_only = "--spills-only" in sys.argv
-    print(f"{len(ks)} kernels in {os.path.relpath(LIB, ROOT)}")
+    print(f"{len(ks)} kernels in {os.path.relpath(lib, ROOT)}")
     print(f"{'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'scratch':>8} {'vspill':>7} {'lds':>7}  name")
     for k in sorted(ks, key=lambda k: k[".name"]):
         if spills_only and not (k[".private_segment_fixed_size"] or k.get(".vgpr_spill_count", 0)):
