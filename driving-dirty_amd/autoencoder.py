@@ -8,6 +8,7 @@ import torch
 
 from . import ops
 from .augment import Augmenter, add_augment_args, current_rank
+from .adamw import add_weight_decay_args
 from .ema import add_ema_args
 from .components import Decoder, Encoder
 from .lightning import LightningModule, hparam
@@ -131,4 +132,5 @@ class BasicAE(LightningModule):
         p.add_argument("--precision", type=str, default="fp32", choices=("fp32", "bf16"))     # not a reference flag: bf16 mixed precision
         add_augment_args(p)
         add_ema_args(p)
+        add_weight_decay_args(p)
         return p

@@ -7,8 +7,9 @@ hipcc cross-compiles without a GPU.  The libraries are built IN-TREE so that the
 (a JIT cache under ~/.cache would not).  Each source is compiled to its own object (in parallel, re-done only when the source or a
 header is newer) and the objects are linked into their library.  An extension library holds launch functions that are not part of
 ``include/dd_hotpath.h`` (its set of functions is pinned): a header and sources of its own, the main library's flags, linked against
-the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS``; the module that
-binds it holds a ``_lib.Extension`` of that entry.
+the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS`` or -- a library of
+the optimizer -- of ``OPTIMIZER_EXTENSIONS``; the module that binds it holds a ``_lib.Extension`` of that entry.  ``extensions()`` is both
+tables as one mapping: what is built, and what every function here that takes an extension's name looks it up in.
 """
 import os
 import subprocess
@@ -48,6 +49,15 @@ EXTENSIONS = {e.name: e for e in (
     _extension("ema", ["ema.hip"], "the weight average"),                            # ema.py: the moving average of the parameters
     _extension("rm_loss", ["rm_loss.hip"], "the road-map loss", [_LOSS_STATS]),      # rm_loss.py: weighted BCE + soft threat score on logits
 )}
+# The optimizer's extension libraries: the same kind of entry, the same rules, a table of their own.
+OPTIMIZER_EXTENSIONS = {e.name: e for e in (
+    _extension("adamw", ["adamw.hip"], "decoupled weight decay", [os.path.join(CSRC, "dd_adam.h")]),      # adamw.py: AdamW passes, the rank-B pre-scale
+)}
+
+
+def extensions():
+    """Every extension library by name: ``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS``."""
+    return {**EXTENSIONS, **OPTIMIZER_EXTENSIONS}
 
 
 def _stale(target, deps):
@@ -62,12 +72,12 @@ def _library_stale(lib, sources, headers):
 
 
 def extension_needs_build(name):
-    e = EXTENSIONS[name]
+    e = extensions()[name]
     return _library_stale(e.lib, e.sources, e.headers)
 
 
 def needs_build():
-    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in EXTENSIONS)
+    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in extensions())
 
 
 def _run(cmd, verbose):
@@ -109,9 +119,9 @@ def build_diag(verbose=True):
 
 
 def build_extension(name, force=False, verbose=True):
-    """``EXTENSIONS[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
+    """``extensions()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
     beside it at load time, $ORIGIN), which therefore has to exist."""
-    e = EXTENSIONS[name]
+    e = extensions()[name]
     if not force and not extension_needs_build(name):
         return e.lib
     return _library(e.lib, e.sources, OBJ, e.headers, [], ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], force, verbose)
@@ -121,7 +131,7 @@ def build(force=False, verbose=True):
     """The main library and every extension library, each only when it is stale; returns the main library's path."""
     if force or _library_stale(LIB, SOURCES, HEADERS):
         _build_main(force, verbose)
-    for name in EXTENSIONS:
+    for name in extensions():
         build_extension(name, force, verbose)
     return LIB
 

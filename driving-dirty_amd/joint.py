@@ -22,6 +22,7 @@ from torch import nn
 from . import ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
+from .adamw import add_weight_decay_args
 from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
@@ -356,5 +357,6 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         add_augment_args(p)
         _tta.add_tta_args(p)
         add_ema_args(p)
+        add_weight_decay_args(p)
         add_rm_loss_args(p)
         return p

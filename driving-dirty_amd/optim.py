@@ -17,17 +17,25 @@ that travels as reduce-scatter + all-gather is updated only in the slices this r
 exist only for those slices (``state[p]["shards"][piece] = (exp_avg, exp_avg_sq)``), and each updated slice is handed straight
 back to ``grad_sync.gather_shard`` -- piece k's all-gather is on the links while piece k+1's update runs.  Elementwise, so the
 owned elements get bit for bit the update of the whole-tensor pass.
+
+Decoupled weight decay (``weight_decay=``; ``adamw.py``, include/dd_adamw.h): torch.optim.AdamW's step.  A decayed parameter is
+multiplied by ``keep = float32(1 - lr * weight_decay)`` in front of its Adam update, inside the same streaming pass (``dd_adamw_step``,
+``dd_adamw_step_multi``: no extra HBM bytes); a rank-B tensor, whose kernels do not take the factor, is pre-scaled by ``dd_decay`` on
+the same stream directly in front of its pass.  The moments never see the decay.  Off (0, the default) every call is the one made
+without the option, and ``adamw`` is never entered.
 """
 from types import SimpleNamespace
 
 import torch
 
-from . import _lib, lightning, ops
+from . import _lib, adamw, lightning, ops
 
 
 class HipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        weight_decay = adamw.check_weight_decay(weight_decay, "HipAdam")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._no_decay = set()     # id(p) of the parameters exclude_from_decay() has marked
         self._side = None
         self._now = None           # this step's bookkeeping: reset_step()
         self.reset_step()
@@ -78,10 +86,36 @@ class HipAdam(torch.optim.Optimizer):
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         return st
 
-    def _launch(self, p, g, m, v, group, step, grad_scale):
-        """The one place the elementwise kernel is called (flat fp32 device tensors of equal length)."""
+    # ---- decoupled weight decay ----------------------------------------------------------------------------------------------
+    def exclude_from_decay(self, params):
+        """Mark ``params`` as never decayed (biases, BatchNorm scale and shift): their ``keep`` is 1 whatever the group's
+        ``weight_decay``.  One param group stays one param group: the state dict's layout does not change."""
+        self._no_decay.update(id(p) for p in params)
+
+    def _keep(self, p, group):
+        """The fp32 factor ``p`` is multiplied by in front of its update: 1.0 when the group's decay is 0 (or absent: a state dict
+        saved before the option existed) or ``p`` is excluded, else ``adamw.keep_of`` of the group's CURRENT lr (a scheduler moves it)."""
+        wd = group.get("weight_decay", 0.0)
+        if not wd or id(p) in self._no_decay:
+            return 1.0
+        return adamw.keep_of(group["lr"], wd)
+
+    def _launch(self, p, g, m, v, group, step, grad_scale, keep=1.0):
+        """The one place the elementwise kernel is called (flat fp32 device tensors of equal length).  ``keep``: the factor of the
+        parameter these operands are (slices of); 1: dd_adam_step(_dev), else dd_adamw_step with the same operands."""
         b1, b2 = group["betas"]
-        ops.adam_step_flat(p, g, m, v, group["lr"], b1, b2, group["eps"], step, grad_scale)
+        if keep == 1.0:
+            ops.adam_step_flat(p, g, m, v, group["lr"], b1, b2, group["eps"], step, grad_scale)
+        else:
+            adamw.step_flat(p, g, m, v, group["lr"], b1, b2, group["eps"], step, grad_scale, keep)
+
+    def _pass(self, p, g, m, v, group, step, grad_scale, keep):
+        """``_launch`` for operands of a parameter whose factor is ``keep``.  1 makes the call made before the option existed,
+        argument for argument: a subclass that replaces ``_launch`` in that form (tests/test_shard_gloo.py) is served while the decay
+        is off."""
+        if keep == 1.0:
+            return self._launch(p, g, m, v, group, step, grad_scale)
+        return self._launch(p, g, m, v, group, step, grad_scale, keep)
 
     # ---- rank-B mode -----------------------------------------------------------------------------------------------------------
     def fuse_linear_wgrad(self, module, min_numel=None):
@@ -228,6 +262,17 @@ class HipAdam(torch.optim.Optimizer):
                 raise RuntimeError("HipAdam: a Linear layer's weight and bias have taken different numbers of steps")
             self._now.early.add(bias)
         b1, b2 = group["betas"]
+        # decoupled decay: the rank-B kernels do not take the factor, so the tensor is pre-scaled on this stream directly in front of
+        # its pass -- behind the backward's last read of the weight by construction, and the bits of the fused form (dd_adamw.h).  8
+        # more bytes per element than the pass's 24: WINDOW_BYTES_PER_ROW / EARLY_BYTES_PER_ROW were tuned without them and are NOT
+        # changed (the measured effect: DESIGN.md 3.2d)
+        keep = self._keep(p, group)
+        if keep != 1.0:
+            adamw.decay(p.data, keep)
+        if bias is not None:
+            keep = self._keep(bias, group)
+            if keep != 1.0:
+                adamw.decay(bias.data, keep)
         ops.adam_step_rankb(p.data, st["exp_avg"], st["exp_avg_sq"], dy, x, None if bias is None else bias.data,
                             None if bst is None else bst["exp_avg"], None if bst is None else bst["exp_avg_sq"],
                             group["lr"], b1, b2, group["eps"], st["step"], grad_scale)
@@ -327,7 +372,7 @@ class HipAdam(torch.optim.Optimizer):
                 else:
                     mv = (torch.zeros_like(sh.param), torch.zeros_like(sh.param))
                 st["shards"][sh.index] = mv
-            self._launch(sh.param, sh.grad, mv[0], mv[1], group, st["step"], grad_scale)
+            self._pass(sh.param, sh.grad, mv[0], mv[1], group, st["step"], grad_scale, self._keep(p, group))
             self._sync.gather_shard(p, sh)
 
     # ---- checkpoints of the optimizer ------------------------------------------------------------------------------------------
@@ -380,7 +425,16 @@ class HipAdam(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, state_dict):
-        """Takes torch.optim.Adam's state (whole moments; ``step`` possibly a tensor) as well as this class's own."""
+        """Takes torch.optim.Adam's state (whole moments; ``step`` possibly a tensor) as well as this class's own, with or without a
+        ``weight_decay`` in its groups (absent: 0).  torch.optim.AdamW's state carries its decay over with the same meaning.  A
+        torch.optim.Adam state with a non-zero ``weight_decay`` is L2-COUPLED decay (added to the gradient, seen by the moments), another
+        algorithm: refused.  The two are told apart by ``decoupled_weight_decay``, which torch writes into both (False / True)."""
+        for group in state_dict["param_groups"]:
+            if group.get("weight_decay", 0.0) and group.get("decoupled_weight_decay") is False:
+                raise ValueError("HipAdam.load_state_dict: the state is torch.optim.Adam's with weight_decay = "
+                                 f"{group['weight_decay']}: L2-coupled decay, which this optimizer does not implement (its "
+                                 "weight_decay is torch.optim.AdamW's decoupled one)")
+            adamw.check_weight_decay(group.get("weight_decay", 0.0), "HipAdam.load_state_dict")
         super().load_state_dict(state_dict)
         for st in self.state.values():
             if "step" in st and isinstance(st["step"], torch.Tensor):
@@ -398,9 +452,10 @@ class HipAdam(torch.optim.Optimizer):
             st["step"] -= 1
             return self._update(p, group, grad_scale)
         pf, gf, mf, vf = p.data.view(-1), p.grad.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1)
+        keep = self._keep(p, group)
         for work, off, n in pieces:
             work.wait()
-            self._launch(pf[off:off + n], gf[off:off + n], mf[off:off + n], vf[off:off + n], group, st["step"], grad_scale)
+            self._pass(pf[off:off + n], gf[off:off + n], mf[off:off + n], vf[off:off + n], group, st["step"], grad_scale, keep)
 
     def _update(self, p, group, grad_scale):
         st = self._state_of(p)
@@ -413,7 +468,8 @@ class HipAdam(torch.optim.Optimizer):
             del st["shards"]
         st["step"] += 1
         g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-        self._launch(p.data.view(-1), g.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), group, st["step"], grad_scale)
+        self._pass(p.data.view(-1), g.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), group, st["step"], grad_scale,
+                   self._keep(p, group))
 
     def overlap_with_backward(self, big_numel=1 << 20, grad_scale=1.0, grad_sync=None):
         """Run the Adam pass of every parameter of >= ``big_numel`` elements on a side stream the moment autograd has
@@ -597,6 +653,7 @@ class HipAdam(torch.optim.Optimizer):
                 grad_scale = scale                # every update below reads grad_scale x coef from the device
         for group in self.param_groups:
             small = {}                            # step count -> [(p, g, m, v)]: one launch for all the small tensors
+            keeps = {}                            # step count -> [keep] of the same tensors
             for p in group["params"]:
                 if p in self._now.rankb_now and p not in self._now.early:      # rank-B mode without the side stream: here, after the backward
                     self._take_rankb(p, group, grad_scale)
@@ -617,7 +674,11 @@ class HipAdam(torch.optim.Optimizer):
                 st["step"] += 1
                 small.setdefault(st["step"], []).append((p.data.view(-1), p.grad.view(-1), st["exp_avg"].view(-1),
                                                           st["exp_avg_sq"].view(-1)))
+                keeps.setdefault(st["step"], []).append(self._keep(p, group))
             b1, b2 = group["betas"]
             for step, quads in small.items():
-                ops.adam_step_multi(quads, group["lr"], b1, b2, group["eps"], step, grad_scale)
+                if all(k == 1.0 for k in keeps[step]):
+                    ops.adam_step_multi(quads, group["lr"], b1, b2, group["eps"], step, grad_scale)
+                else:      # biases and BatchNorm vectors ride in the same launch with 1.0
+                    adamw.step_multi(quads, keeps[step], group["lr"], b1, b2, group["eps"], step, grad_scale)
         self.reset_step()                         # joins the side stream (every pass launched there is in the step's state)

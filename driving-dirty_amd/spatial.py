@@ -13,6 +13,7 @@ from torch import nn
 from . import gconv, ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
+from .adamw import add_weight_decay_args
 from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .heads import MergeFn, SpatialMapFn, _ORDER, as_nhwc, road_map_taps
@@ -578,4 +579,5 @@ class BBSpatialRoadMap(CalibratedBoxThreshold, LightningModule):
         add_augment_args(p)
         _tta.add_tta_args(p)
         add_ema_args(p)
+        add_weight_decay_args(p)
         return p

@@ -19,6 +19,8 @@ exactly that (torch.optim.Adam): a caller with its own loop keeps working.  This
     weight gradients and every rank forms the global-batch gradient itself (ddp.py);
   * ``ema_decay`` / ``ema_every`` / ``ema_warmup`` (``--ema_*``): an exponential moving average of the parameters kept on the device
     (``ema.WeightEMA``), updated after the optimizer step; ``averaged()`` evaluates it in place; one GPU only;
+  * ``weight_decay`` / ``weight_decay_all`` (``--weight_decay*``): torch.optim.AdamW's decoupled decay inside the same optimizer passes
+    (``adamw.py``); biases and BatchNorm vectors are left out unless ``weight_decay_all``; off by default, and off is the same calls;
   * frozen feature extractors (``self.ae.freeze()`` in the fine-tuning modules) are handled: both objects are built over the model
     as constructed and re-arm when ``training_step`` unfreezes it (lightning.on_unfreeze);
   * ``validation_epoch_end(val_loss)`` steps ``ReduceLROnPlateau`` the way Lightning does for a scheduler returned beside the
@@ -29,6 +31,7 @@ It is a helper, not a Trainer: no data loading, logging, checkpoint policy or CL
 import torch
 import torch.distributed as dist
 
+from .adamw import check_weight_decay
 from .ddp import GradSync
 from .optim import HipAdam
 
@@ -37,7 +40,14 @@ class TrainStep:
     def __init__(self, model, lr=None, adam_overlap="auto", shard_optimizer=False, reserve_cus=None, process_group=None,
                  force_collectives=False, simulate_world=0, scheduler="auto", big_numel=1 << 20, chunk_numel=1 << 25, factor_linear=False,
                  fuse_linear_wgrad=True, passes_last="auto", gradient_clip_val=None, track_grad_norm=False, ema_decay=None, ema_every=None,
-                 ema_warmup=None):
+                 ema_warmup=None, weight_decay=None, weight_decay_all=None):
+        """``weight_decay`` (None: ``hparams.weight_decay``, absent: 0): decoupled weight decay, torch.optim.AdamW's, with ``keep = 1 - lr
+        * weight_decay`` derived from the group's CURRENT lr at every step (ReduceLROnPlateau moves both).  Parameters of at most one
+        dimension -- biases, BatchNorm scale and shift -- are excluded unless ``weight_decay_all`` (None: ``hparams.weight_decay_all``,
+        absent: False), which decays everything as a bare ``torch.optim.AdamW(model.parameters())`` does.  It composes with
+        ``adam_overlap``, ``passes_last``, clipping (the norm is the gradients' alone), the EMA and the scheduler.  Under a live
+        ``GradSync`` the elementwise passes work by construction (every rank uses the same ``keep``); like every multi-GPU path here
+        that has not been run on more than one GPU."""
         self.model = model
         hp = getattr(model, "hparams", None)
         if lr is None:
@@ -87,6 +97,22 @@ class TrainStep:
             self.sync.remove()
             raise NotImplementedError("TrainStep: ema_decay under a live GradSync (all-reduce, sharded, factor gather) is not implemented: "
                                       "one GPU only (a sharded all-gather still writes parameters under the next forward)")
+        # --weight_decay / --weight_decay_all (adamw.add_weight_decay_args).  Off (0 or absent): the optimizer is built and steps as before.
+        if weight_decay is None:
+            weight_decay = getattr(hp, "weight_decay", 0.0)
+        if weight_decay_all is None:
+            weight_decay_all = getattr(hp, "weight_decay_all", False)
+        try:
+            self.weight_decay = check_weight_decay(weight_decay, "TrainStep")
+        except ValueError:
+            self.sync.remove()
+            raise
+        self.weight_decay_all = bool(weight_decay_all)
+        if self.weight_decay > 0:
+            for group in self.optimizer.param_groups:
+                group["weight_decay"] = self.weight_decay
+            if not self.weight_decay_all:
+                self.optimizer.exclude_from_decay(p for p in model.parameters() if p.ndim <= 1)
         self.ema = None
         if ema_decay > 0:
             from .ema import WeightEMA

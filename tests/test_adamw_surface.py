@@ -1,0 +1,332 @@
+"""Decoupled weight decay without a GPU: include/dd_adamw.h and the library built from it, the second table of build.py, the launchers'
+host-side refusals, the kernels' registers, the command line, TrainStep's and HipAdam's options and refusals, the exclusion rule, and
+the optimizer state's round trips."""
+import ctypes as C
+import os
+from argparse import ArgumentParser, Namespace
+
+import pytest
+import torch
+
+from _surface import ROOT, exported_symbols, header, kernel_resources
+
+FUNCTIONS = {"dd_adamw_step", "dd_adamw_step_multi", "dd_decay"}
+
+
+def models():
+    from driving_dirty_amd.autoencoder import BasicAE
+    from driving_dirty_amd.joint import JointRoadMapBBox
+    from driving_dirty_amd.roadmap import RoadMap, RoadMapBCE
+    from driving_dirty_amd.spatial import BBSpatialRoadMap
+    return BasicAE, RoadMapBCE, RoadMap, BBSpatialRoadMap, JointRoadMapBBox
+
+
+def tiny_roadmap(**hp):
+    from driving_dirty_amd.autoencoder import BasicAE
+    from driving_dirty_amd.roadmap import RoadMapBCE
+    ae = BasicAE(Namespace(hidden_dim=16, latent_dim=8, input_height=16, input_width=132))
+    return RoadMapBCE(Namespace(pretrained_ae=ae, unfreeze_epoch_no=0, learning_rate=1e-3, output_img_freq=500, **hp))
+
+
+# ---- the header, the library, the binder ---------------------------------------------------------------------------------------------
+def test_header_declares_the_three_launch_functions_and_the_library_exports_exactly_them():
+    from driving_dirty_amd import adamw, build
+    signatures, streamed = header("dd_adamw.h")
+    assert set(signatures) == FUNCTIONS and set(streamed) == FUNCTIONS, "all three are launch functions (void* stream last)"
+    assert adamw.SIGNATURES == signatures and adamw.STREAMED == streamed
+    assert adamw.OPERANDS == {"dd_adamw_step": 13, "dd_adamw_step_multi": 10, "dd_decay": 3}
+    entry = build.OPTIMIZER_EXTENSIONS["adamw"]
+    assert adamw.LIB == entry.lib and os.path.exists(entry.lib), "build the HIP libraries first (python __graft_entry__.py)"
+    assert {n for n in exported_symbols(entry.lib) if n.startswith("dd_")} == FUNCTIONS
+    for name in ("lib", "launch", "last_error"):
+        fn = vars(adamw)[name]      # module-level names, so that a monkeypatched ``launch`` takes effect
+        assert fn.__func__ is getattr(type(fn.__self__), name) and fn.__self__ is adamw.lib.__self__
+    assert "call" not in vars(adamw) and "size" not in vars(adamw)
+    with pytest.raises(adamw.HotpathError, match="operands given"):
+        adamw.launch("dd_decay", None, 4)
+    with pytest.raises(adamw.HotpathError, match="not a function of include/dd_adamw.h"):
+        adamw.launch("dd_adam_step", None, None, None, None, 4, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0)
+
+
+def test_the_three_functions_are_in_none_of_the_five_other_headers_and_no_struct_is_added():
+    from driving_dirty_amd import _lib, build
+    others = [build.HEADER] + [e.header for e in build.EXTENSIONS.values()]
+    assert len(others) == 5
+    for h in others:
+        assert not FUNCTIONS & set(header(os.path.basename(h))[0]), h
+    text = open(build.OPTIMIZER_EXTENSIONS["adamw"].header).read()
+    assert "typedef" not in text and "struct dd_" not in text
+    assert header("dd_adamw.h")[0]["dd_adamw_step_multi"][1][0] is C.POINTER(_lib.AdamTensor)      # dd_hotpath.h's struct, as parse_header maps it
+
+
+def test_the_second_table(monkeypatch):
+    """``OPTIMIZER_EXTENSIONS`` holds the one entry, made by the constructor of the other four; ``extensions()`` is both tables; the
+    build functions take a name of either; nothing is stale after a build and then no command is issued; forced, the library is one
+    compile with the main library's flags and one link against it."""
+    from driving_dirty_amd import build
+    assert list(build.OPTIMIZER_EXTENSIONS) == ["adamw"] and list(build.extensions()) == list(build.EXTENSIONS) + ["adamw"]
+    e = build.OPTIMIZER_EXTENSIONS["adamw"]
+    assert isinstance(e, build.Extension) and e.name == "adamw" and e.sources == ["adamw.hip"] and e.what
+    assert e.header == os.path.join(ROOT, "include", "dd_adamw.h") and e.lib == os.path.join(build.CSRC, "libdd_adamw.so")
+    assert os.path.join(build.CSRC, "dd_adam.h") in e.headers and build.HEADER in e.headers and e.header in e.headers
+    assert all(os.path.exists(h) for h in e.headers)
+    assert not build.needs_build() and not build.extension_needs_build("adamw"), "build the HIP libraries first (python __graft_entry__.py)"
+    commands = []
+    monkeypatch.setattr(build, "_run", lambda cmd, verbose: commands.append(cmd))
+    assert build.build(verbose=False) == build.LIB and commands == []
+    assert build.build_extension("adamw", verbose=False) == e.lib and commands == []
+    assert build.build_extension("adamw", force=True, verbose=False) == e.lib
+    compile_, link = commands
+    obj = os.path.join(build.OBJ, "adamw.o")
+    assert compile_[1:] == build.FLAGS + ["-c", os.path.join(build.CSRC, "adamw.hip"), "-o", obj]
+    assert link[1:] == ["--offload-arch=gfx950", "-shared", "-fPIC", "-o", e.lib, obj, "-L" + build.CSRC, "-l:libdd_hotpath.so", "-Wl,-rpath,$ORIGIN"]
+    # a newer shared Adam element makes it stale (and the main library, which includes it too)
+    monkeypatch.setattr(build, "_stale", lambda target, deps: target == e.lib and os.path.join(build.CSRC, "dd_adam.h") in deps)
+    assert build.extension_needs_build("adamw") and build.needs_build() and not build.extension_needs_build("ema")
+
+
+def test_the_entry_script_loads_every_library_of_both_tables():
+    text = open(os.path.join(ROOT, "__graft_entry__.py")).read()
+    assert "b.extensions().values()" in text and "b.EXTENSIONS" not in text
+
+
+def test_the_kernels_use_no_scratch_and_the_streaming_kernel_fits_beside_the_conv_kernels():
+    from driving_dirty_amd import build
+    ks = kernel_resources().kernels(build.OPTIMIZER_EXTENSIONS["adamw"].lib)
+    assert len(ks) == 5, [k[".name"] for k in ks]      # the streaming pass and the table launch in two scale forms each, the pre-scale
+    for k in ks:
+        assert k[".private_segment_fixed_size"] == 0 and k[".group_segment_fixed_size"] == 0, k[".name"]
+        assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, k[".name"]
+    by_value = [k for k in ks if "adamw_kernel" in k[".name"]]
+    assert len(by_value) == 1 and by_value[0][".vgpr_count"] + by_value[0].get(".agpr_count", 0) <= 48, by_value      # dd_adam_step's budget
+    main = [k for k in kernel_resources().kernels(build.LIB) if "11adam_kernel" in k[".name"]]
+    assert len(main) == 1 and by_value[0][".vgpr_count"] <= main[0][".vgpr_count"], "no more registers than the pass it is a mode of"
+
+
+# ---- the launchers' refusals ---------------------------------------------------------------------------------------------------------
+def test_launchers_refuse_bad_arguments_without_a_gpu():
+    from driving_dirty_amd import _lib, adamw
+    lib = adamw.lib()
+    P, G, M, V, S = 1 << 20, 2 << 20, 3 << 20, 4 << 20, 5 << 20      # never dereferenced: every call below is refused on the host
+    nan, inf = float("nan"), float("inf")
+
+    def refused(rc, *words):
+        msg = adamw.last_error()
+        assert rc != 0 and msg and all(w in msg for w in words), (rc, msg)
+
+    def step(p=P, g=G, m=M, v=V, n=1000, step=1, scale_dev=None, keep=0.99):
+        return lib.dd_adamw_step(p, g, m, v, n, 1e-3, 0.9, 0.999, 1e-8, step, 1.0, scale_dev, keep, None)
+
+    for name in "pgmv":
+        refused(step(**{name: None}), "adamw_step", name, "NULL")
+        refused(step(**{name: dict(p=P, g=G, m=M, v=V)[name] + 4}), "adamw_step", "16-byte")
+    for bad in (0, -5):
+        refused(step(n=bad), "adamw_step", "n =", str(bad))
+        refused(step(step=bad), "adamw_step", "step =", str(bad))
+    refused(step(scale_dev=S + 2), "adamw_step", "grad_scale_dev", "4-byte")
+    for bad in (nan, inf, -inf, -1e-3, 1.0001):
+        refused(step(keep=bad), "adamw_step", "keep", "[0, 1]")
+
+    def table(entries):
+        t = (_lib.AdamTensor * len(entries))()
+        for e, (p, g, m, v, n) in zip(t, entries):
+            e.p, e.g, e.m, e.v, e.n = p, g, m, v, n
+        return t
+
+    good = [(P, G, M, V, 5), (P + 4096, G + 4096, M + 4096, V + 4096, 300)]
+
+    def multi(entries=good, keeps=(1.0, 0.99), count=2, step=1, scale_dev=None):
+        return lib.dd_adamw_step_multi(entries and table(entries), keeps and (C.c_float * len(keeps))(*keeps), count, 1e-3, 0.9, 0.999,
+                                       1e-8, step, 1.0, scale_dev, None)
+
+    refused(multi(entries=None), "adamw_step_multi", "tensors", "NULL")
+    refused(multi(keeps=None), "adamw_step_multi", "keep", "NULL")
+    for bad in (0, -1):
+        refused(multi(count=bad), "adamw_step_multi", "count", str(bad))
+        refused(multi(step=bad), "adamw_step_multi", "step", str(bad))
+    refused(multi(scale_dev=S + 1), "adamw_step_multi", "grad_scale_dev", "4-byte")
+    for i in range(4):
+        entry = list(good[1])
+        entry[i] = None
+        refused(multi(entries=[good[0], tuple(entry)]), "adamw_step_multi", "tensor 1", "NULL")
+    for bad in (0, -3, 1 << 30):
+        refused(multi(entries=[(P, G, M, V, bad), good[1]]), "adamw_step_multi", "tensor 0", "2^30")
+    for bad in (nan, inf, -0.5, 1.5):
+        refused(multi(keeps=(1.0, bad)), "adamw_step_multi", "keep[1]", "[0, 1]")
+
+    def decay(p=P, n=1000, keep=0.99):
+        return lib.dd_decay(p, n, keep, None)
+
+    refused(decay(p=None), "decay", "NULL")
+    refused(decay(p=P + 8), "decay", "16-byte")
+    for bad in (0, -1):
+        refused(decay(n=bad), "decay", "n =", str(bad))
+    for bad in (nan, inf, -inf, -0.25, 2.0):
+        refused(decay(keep=bad), "decay", "keep", "[0, 1]")
+
+
+def test_every_launch_function_of_the_library_has_a_guard_case_in_both_scale_forms():
+    """The census of tests/test_guard_arena.py for this library: the case table imports without a GPU, names only launch functions of
+    dd_adamw.h, and every one of them is the subject of a case -- the two step functions once per scale form.  None picks a kernel by
+    alignment."""
+    import test_gpu_guard_adamw as guard
+    from driving_dirty_amd import adamw
+    assert guard.CASES and len({c.name for c in guard.CASES}) == len(guard.CASES)
+    assert {e for c in guard.CASES for e in c.entry} == set(adamw.STREAMED) == set(adamw.SIGNATURES)
+    assert not any(c.picks_kernel_by_alignment or c.crosses for c in guard.CASES)
+    for entry in ("dd_adamw_step", "dd_adamw_step_multi"):
+        names = [c.name for c in guard.CASES if c.entry == (entry,)]
+        assert len(names) == 2 and all(any(f"scale={form}" in n for n in names) for form in guard.SCALE_FORMS), names
+    assert sum(1 for c in guard.CASES if c.entry == ("dd_decay",)) == len(guard.DECAY_SIZES) == 2
+    assert len(guard.MULTI_SIZES) > 48 and guard.FLAT_N % 4 and 0 < guard.KEEP < 1
+
+
+# ---- the command line ----------------------------------------------------------------------------------------------------------------
+def test_the_parsers_take_the_two_flags_and_default_to_off():
+    parsed = {}
+    for cls in models():
+        args = cls.add_model_specific_args(ArgumentParser(add_help=False)).parse_args([])
+        assert (args.weight_decay, args.weight_decay_all) == (0.0, False) and isinstance(args.weight_decay, float), cls
+        args = cls.add_model_specific_args(ArgumentParser(add_help=False)).parse_args(["--weight_decay", "0.01", "--weight_decay_all"])
+        assert (args.weight_decay, args.weight_decay_all) == (0.01, True), cls
+        parsed[cls.__name__] = set(vars(args))
+    # the joint parser is still the union of the two single-task ones (tests/test_joint_surface.py)
+    assert parsed["JointRoadMapBBox"] == (parsed["BBSpatialRoadMap"] | parsed["RoadMapBCE"] | {"box_rm_input"}) - {"unfreeze_epoch_no", "mse_loss"}
+
+
+# ---- TrainStep and HipAdam -----------------------------------------------------------------------------------------------------------
+def test_train_step_reads_the_flags_and_is_off_by_default():
+    from driving_dirty_amd.train import TrainStep
+    for extra, want in (({}, (0.0, False)), ({"weight_decay": 0.0, "weight_decay_all": True}, (0.0, True)),
+                        ({"weight_decay": 0.05}, (0.05, False)), ({"weight_decay": 0.05, "weight_decay_all": True}, (0.05, True))):
+        model = tiny_roadmap(**extra)
+        step = TrainStep(model, scheduler=False, adam_overlap=False)
+        group = step.optimizer.param_groups[0]
+        assert (step.weight_decay, step.weight_decay_all) == want and group["weight_decay"] == want[0]
+        assert len(step.optimizer.param_groups) == 1
+        keeps = {name: step.optimizer._keep(p, group) for name, p in model.named_parameters()}
+        if want[0] == 0.0:
+            assert set(keeps.values()) == {1.0} and not step.optimizer._no_decay
+        else:
+            decayed = float(torch.tensor(1.0 - 1e-3 * 0.05, dtype=torch.float32))
+            for name, p in model.named_parameters():
+                assert keeps[name] == (decayed if p.ndim > 1 or want[1] else 1.0), name
+        step.close()
+    model = tiny_roadmap(weight_decay=0.05)
+    step = TrainStep(model, scheduler=False, adam_overlap=False, weight_decay=0.0)      # the argument wins over hparams
+    assert step.weight_decay == 0.0 and step.optimizer.param_groups[0]["weight_decay"] == 0.0
+    step.close()
+
+
+def test_keep_follows_the_groups_current_lr():
+    from driving_dirty_amd.train import TrainStep
+    model = tiny_roadmap()
+    step = TrainStep(model, scheduler=True, adam_overlap=False, weight_decay=0.1)
+    group, w = step.optimizer.param_groups[0], model.fc1.weight
+    assert step.optimizer._keep(w, group) == float(torch.tensor(1.0 - 1e-3 * 0.1, dtype=torch.float32))
+    group["lr"] = 1e-4      # what ReduceLROnPlateau does
+    assert step.optimizer._keep(w, group) == float(torch.tensor(1.0 - 1e-4 * 0.1, dtype=torch.float32))
+    step.close()
+
+
+def test_refusals_of_train_step_and_hipadam():
+    from driving_dirty_amd import ddp
+    from driving_dirty_amd.optim import HipAdam
+    from driving_dirty_amd.train import TrainStep
+    model = tiny_roadmap()
+    removed = []
+    real = ddp.GradSync.remove
+    try:
+        ddp.GradSync.remove = lambda self: (removed.append(self), real(self))[1]
+        for bad in (-0.01, float("nan"), float("inf")):
+            del removed[:]
+            with pytest.raises(ValueError, match="TrainStep: weight_decay"):
+                TrainStep(model, scheduler=False, adam_overlap=False, weight_decay=bad)
+            assert len(removed) == 1, "the GradSync is removed before the refusal"
+    finally:
+        ddp.GradSync.remove = real
+    w = torch.nn.Parameter(torch.zeros(4))
+    for bad in (-1e-3, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="HipAdam: weight_decay"):
+            HipAdam([w], weight_decay=bad)
+    opt = HipAdam([w], lr=0.5, weight_decay=4.0)
+    with pytest.raises(ValueError, match="keep"):      # lr * weight_decay > 1: not a decay
+        opt._keep(w, opt.param_groups[0])
+    assert HipAdam([w]).defaults["weight_decay"] == 0.0
+
+
+def test_the_exclusion_rule_on_a_model_with_batchnorm():
+    """components_v2.Encoder (Conv -> BatchNorm2d -> ReLU, BatchNorm1d in the dense blocks): by default the convolution and Linear
+    weights decay and every bias, BatchNorm scale and BatchNorm shift keeps its factor 1; ``weight_decay_all`` decays them too, as a
+    bare torch.optim.AdamW(model.parameters()) does; ``exclude_from_decay`` marks by identity."""
+    from driving_dirty_amd import components_v2
+    from driving_dirty_amd.optim import HipAdam
+    from driving_dirty_amd.train import TrainStep
+    model = components_v2.Encoder(16, 8, 3, 16, 132)
+    norm = {id(p) for m in model.modules() if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)) for p in m.parameters()}
+    assert len(norm) >= 6
+    keep = float(torch.tensor(1.0 - 1e-3 * 0.01, dtype=torch.float32))
+    for everything in (False, True):
+        step = TrainStep(model, lr=1e-3, scheduler=False, adam_overlap=False, weight_decay=0.01, weight_decay_all=everything)
+        group = step.optimizer.param_groups[0]
+        seen = set()
+        for name, p in model.named_parameters():
+            k = step.optimizer._keep(p, group)
+            left_out = id(p) in norm or name.endswith(".bias")
+            assert left_out == (p.ndim <= 1), name
+            assert k == (1.0 if left_out and not everything else keep), (name, k)
+            seen.add(k)
+        assert seen == ({keep} if everything else {1.0, keep})
+        step.close()
+    opt = HipAdam(model.parameters(), lr=1e-3, weight_decay=0.01)
+    opt.exclude_from_decay([model.c2.weight])
+    assert opt._keep(model.c2.weight, opt.param_groups[0]) == 1.0 and opt._keep(model.c1.weight, opt.param_groups[0]) == keep
+
+
+# ---- the optimizer state's round trips -----------------------------------------------------------------------------------------------
+def _moments(params, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {i: {"step": 7, "exp_avg": torch.randn(p.shape, generator=g), "exp_avg_sq": torch.rand(p.shape, generator=g)} for i, p in enumerate(params)}
+
+
+def test_the_optimizer_state_round_trips():
+    from driving_dirty_amd.optim import HipAdam
+    params = [torch.nn.Parameter(torch.zeros(5, 3)), torch.nn.Parameter(torch.zeros(3))]
+    # a state saved before the option existed: no weight_decay in its group
+    old = {"state": _moments(params, 1), "param_groups": [{"lr": 2e-3, "betas": (0.9, 0.999), "eps": 1e-8, "params": [0, 1]}]}
+    opt = HipAdam(params, lr=1e-3, weight_decay=0.01)
+    opt.load_state_dict(old)
+    group = opt.param_groups[0]
+    assert "weight_decay" not in group and group["lr"] == 2e-3
+    assert opt._keep(params[0], group) == 1.0, "absent means 0"
+    assert opt.state[params[0]]["step"] == 7 and torch.equal(opt.state[params[1]]["exp_avg"], old["state"][1]["exp_avg"])
+    # its own state: the layout is the parent's plus the one key, and comes back
+    opt = HipAdam(params, lr=1e-3, weight_decay=0.02)
+    own = opt.state_dict()
+    assert own["param_groups"] == [{"lr": 1e-3, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0.02, "params": [0, 1]}]
+    again = HipAdam(params, lr=5e-3)
+    again.load_state_dict(own)
+    assert again.param_groups[0]["weight_decay"] == 0.02 and again.param_groups[0]["lr"] == 1e-3
+    # torch.optim.AdamW's: the decay carries over with the same meaning
+    theirs = torch.optim.AdamW(params, lr=3e-3, weight_decay=0.05)
+    for p in params:
+        p.grad = torch.ones_like(p)
+    theirs.step()
+    opt = HipAdam(params, lr=1e-3)
+    opt.load_state_dict(theirs.state_dict())
+    group = opt.param_groups[0]
+    assert group["weight_decay"] == 0.05 and group["lr"] == 3e-3
+    assert opt._keep(params[0], group) == float(torch.tensor(1.0 - 3e-3 * 0.05, dtype=torch.float32))
+    st = opt.state[params[0]]
+    assert st["step"] == 1 and isinstance(st["step"], int) and torch.equal(st["exp_avg"], theirs.state[params[0]]["exp_avg"])
+    # torch.optim.Adam's without decay loads as before; with decay it is L2-coupled, another algorithm: refused by name
+    HipAdam(params).load_state_dict(torch.optim.Adam(params, lr=1e-3).state_dict())
+    coupled = torch.optim.Adam(params, lr=1e-3, weight_decay=0.05).state_dict()
+    opt = HipAdam(params, lr=7e-3)
+    with pytest.raises(ValueError, match="torch.optim.Adam's with weight_decay = 0.05: L2-coupled"):
+        opt.load_state_dict(coupled)
+    assert opt.param_groups[0]["lr"] == 7e-3, "a refused state changes nothing"
+    coupled["param_groups"][0]["weight_decay"] = -1.0
+    coupled["param_groups"][0]["decoupled_weight_decay"] = True
+    with pytest.raises(ValueError, match="weight_decay"):
+        opt.load_state_dict(coupled)
