@@ -60,24 +60,10 @@ def _items(x):
 def augment_views(sample, flags, color):
     """fp32 views ([B,6,3,H,W] or a tuple of [6,3,H,W]) or uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3]) on the GPU -> ONE
     stacked fp32 [B,6,3,H,W]: mirrored, jittered and blanked per sample as ``flags`` [B] and ``color`` [B,6,2] say (dd_augment.h)."""
-    if ops.is_u8_frames(sample):
-        table, b, h, w, dev, keep = ops.u8_table(sample, "augment_views")
-        name = "dd_aug_views_u8_ptrs"
-    else:
-        keep = [t if t.is_contiguous() else t.contiguous() for t in _items(sample)]
-        if not keep:
-            raise HotpathError("augment_views: empty batch")
-        shape = tuple(keep[0].shape)
-        if len(shape) != 4 or shape[:2] != (6, 3):
-            raise HotpathError(f"augment_views: expected fp32 views of [6,3,H,W] per sample, got {shape}")
-        for t in keep:
-            _lib.dev(t, "sample", shape)
-        b, (h, w), dev = len(keep), shape[2:], keep[0].device
-        table = (C.c_void_p * b)(*[t.data_ptr() for t in keep])
-        name = "dd_aug_views_ptrs"
+    table, b, h, w, dev, u8, _keep = ops.sample_table(sample, "augment_views")
     cflags, ccolor = _host_arrays(flags, color, b)
     out = torch.empty((b, 6, 3, h, w), device=dev, dtype=torch.float32)
-    launch(name, table, cflags, ccolor, out, b, h, w)
+    launch("dd_aug_views_u8_ptrs" if u8 else "dd_aug_views_ptrs", table, cflags, ccolor, out, b, h, w)
     return out
 
 

@@ -1,7 +1,7 @@
 // Train-time augmentation next to the 6-view gather (include/dd_augment.h; csrc/libdd_augment.so, a library of its own):
 //   dd_aug_views_u8_ptrs / dd_aug_views_ptrs   left/right mirror of the rig + per-view gain/bias + view blanking -> fp32 [B,6,3,H,W]
 //   dd_aug_masks_u8_ptrs                       the road masks under the same mirror (rows reversed)          -> bytes [B,h,w]
-// HBM-bound byte shuffling, as layout_pool.hip's gathers: every output byte is written once, 16 bytes per lane for the views.
+// HBM-bound byte shuffling, as camera_gather.hip's gathers: every output byte is written once, 16 bytes per lane for the views.
 // The output is cut into groups of four consecutive fp32, so the 16-byte store does not depend on W % 4 (the cameras' W = 306 is
 // no multiple of 4): a group may cross a row, and each of its four elements finds its own source.  Two kernels per input type,
 // picked by the SHAPE alone (never by an address), both through the one per-element function `augment_value`, so the same bits:
@@ -154,8 +154,6 @@ __global__ __launch_bounds__(256) void aug_masks_kernel(const MaskTable t, unsig
   }
 }
 
-int grid_for(long groups) { return (int)min((groups + 255) / 256, (long)DD_NUM_CU * 8); }
-
 int check_flags(const char* who, const uint32_t* flags, int batch) {
   for (int i = 0; i < batch; ++i)
     DD_REQUIRE((flags[i] & ~kFlagsKnown) == 0, DD_ERR_BAD_ARG, "%s: flags[%d] = 0x%x has a bit that means nothing (bit 0: mirror, bits 8..13: blank a view)",
@@ -191,7 +189,7 @@ int launch_views(const char* who, const SrcT* const* sample_ptrs, const uint32_t
       hipLaunchKernelGGL(aug_views_plane_kernel<SrcT>, dim3(min((groups + 255) / 256, 32), 18, nb), dim3(256), 0, (hipStream_t)stream,
                          tab, out + b0 * per_sample, height, width);
     } else {
-      hipLaunchKernelGGL(aug_views_kernel<SrcT>, dim3(grid_for((nb * per_sample + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tab,
+      hipLaunchKernelGGL(aug_views_kernel<SrcT>, dim3(dd_grid_for((nb * per_sample + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tab,
                          out + b0 * per_sample, nb, height, width);
     }
     DD_LAUNCH_CHECK(who);
@@ -231,7 +229,7 @@ int dd_aug_masks_u8_ptrs(const unsigned char* const* mask_ptrs, const uint32_t* 
       tab.p[i] = mask_ptrs[s];
       tab.flags[i] = flags[s];
     }
-    hipLaunchKernelGGL(aug_masks_kernel, dim3(grid_for((nb * per_sample + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tab,
+    hipLaunchKernelGGL(aug_masks_kernel, dim3(dd_grid_for((nb * per_sample + 3) / 4)), dim3(256), 0, (hipStream_t)stream, tab,
                        out + b0 * per_sample, nb, h, w);
     DD_LAUNCH_CHECK(who);
   }

@@ -245,8 +245,6 @@ __global__ __launch_bounds__(256) void pool4_bwd_quad_aff(const float* __restric
   }
 }
 
-int grid_for(long n) { return (int)min((n + 255) / 256, (long)DD_NUM_CU * 8); }
-
 }  // namespace
 
 extern "C" {
@@ -266,7 +264,7 @@ int dd_bn2d_stats(const float* u, float* stats, int64_t npix, void* stream) {
   DD_REQUIRE(u && stats && npix > 0, DD_ERR_BAD_ARG, "bn2d_stats: bad argument");
   DD_REQUIRE((uintptr_t)u % 16 == 0, DD_ERR_BAD_ARG, "bn2d_stats: buffer must be 16-byte aligned");
   const long n4 = npix * 8;
-  const int grid = (int)min((long)grid_for(n4), (long)kStatRows);
+  const int grid = (int)min((long)dd_grid_for(n4), (long)kStatRows);
   hipLaunchKernelGGL(bn2d_stats_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4*)u, stats, n4);
   DD_LAUNCH_CHECK("bn2d_stats");
   return 0;
@@ -275,7 +273,7 @@ int dd_bn2d_stats(const float* u, float* stats, int64_t npix, void* stream) {
 int dd_bn2d_apply_relu(const float* u, const float* affine, float* y, int64_t npix, void* stream) {
   DD_REQUIRE(u && affine && y && npix > 0, DD_ERR_BAD_ARG, "bn2d_apply_relu: bad argument");
   const long n4 = npix * 8;
-  hipLaunchKernelGGL(bn2d_apply_relu_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)u, affine,
+  hipLaunchKernelGGL(bn2d_apply_relu_kernel, dim3(dd_grid_for(n4)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)u, affine,
                      (f32x4*)y, n4);
   DD_LAUNCH_CHECK("bn2d_apply_relu");
   return 0;
@@ -289,7 +287,7 @@ int dd_bn2d_bwd(const float* g, const float* u, const float* gamma, const float*
              "bn2d_bwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
   const long n4 = npix * 8;
-  const int grid = grid_for(n4);
+  const int grid = dd_grid_for(n4);
   hipLaunchKernelGGL(bn2d_bwd_reduce_kernel, dim3(grid), dim3(256), 0, st, (const f32x4*)g, (const f32x4*)u, save_mean,
                      save_invstd, (double*)workspace, n4);
   DD_LAUNCH_CHECK("bn2d_bwd_reduce");
@@ -305,7 +303,7 @@ int dd_pool4_bn_fwd(const float* u, const float* affine, float* pooled, int32_t 
   DD_REQUIRE(u && affine && pooled && batch > 0 && h > 0 && w > 0, DD_ERR_BAD_ARG, "pool4_bn_fwd: bad argument");
   DD_REQUIRE(((long)h * w) % 4 == 0, DD_ERR_UNSUPPORTED, "pool4_bn: H*W must be a multiple of 4");
   const long HW = (long)h * w, total = (long)batch * (HW / 4) * 8;
-  hipLaunchKernelGGL(pool4_fwd_quad_aff, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)u, affine, pooled,
+  hipLaunchKernelGGL(pool4_fwd_quad_aff, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)u, affine, pooled,
                      batch, HW);
   DD_LAUNCH_CHECK("pool4_bn_fwd");
   return 0;
@@ -316,7 +314,7 @@ int dd_pool4_bn_bwd(const float* dpooled, const float* u, const float* affine, f
   DD_REQUIRE(dpooled && u && affine && dfeat && batch > 0 && h > 0 && w > 0, DD_ERR_BAD_ARG, "pool4_bn_bwd: bad argument");
   DD_REQUIRE(((long)h * w) % 4 == 0, DD_ERR_UNSUPPORTED, "pool4_bn: H*W must be a multiple of 4");
   const long HW = (long)h * w, total = (long)batch * (HW / 4) * 8;
-  hipLaunchKernelGGL(pool4_bwd_quad_aff, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, (const f32x4*)u, affine,
+  hipLaunchKernelGGL(pool4_bwd_quad_aff, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, (const f32x4*)u, affine,
                      (f32x4*)dfeat, batch, HW);
   DD_LAUNCH_CHECK("pool4_bn_bwd");
   return 0;

@@ -2393,7 +2393,7 @@ int dd_relu_bwd(const float* dy, const float* y, float* out, int64_t n, void* st
   DD_REQUIRE(dy && y && out && n > 0, DD_ERR_BAD_ARG, "relu_bwd: bad argument");
   DD_REQUIRE(n % 4 == 0, DD_ERR_UNSUPPORTED, "relu_bwd: n %% 4 != 0");
   const long n4 = n / 4;
-  const int grid = (int)min((n4 + 255) / 256, (long)DD_NUM_CU * 8);
+  const int grid = dd_grid_for(n4);
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const f32x4*)dy, (const f32x4*)y,
                      (f32x4*)out, n4);
   DD_LAUNCH_CHECK("relu_bwd");
@@ -2416,7 +2416,7 @@ int dd_relu_bwd_pad_bits(const float* dy, const uint32_t* bits_pad, float* out_p
              "relu_bwd_pad_bits: dy's 32 channels must be a 4-aligned slice of its %d stored ones (offset %d)", dy_cstore, dy_coff);
   DD_REQUIRE((((uintptr_t)dy | (uintptr_t)out_pad) & 15) == 0, DD_ERR_BAD_ARG, "relu_bwd_pad_bits: dy and out_pad must be 16-byte aligned");
   const long total = (long)batch * (h + 2) * (w + 2) * 8;
-  const int grid = (int)min((total + 255) / 256, (long)DD_NUM_CU * 8);
+  const int grid = dd_grid_for(total);
   hipLaunchKernelGGL(relu_bwd_pad_bits_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, bits_pad, (f32x4*)out_pad,
                      batch, h, w, dy_cstore, dy_coff);
   DD_LAUNCH_CHECK("relu_bwd_pad_bits");

@@ -619,92 +619,6 @@ __global__ void bf_pack_kernel(const float* __restrict__ w, unsigned short* __re
 // ------------------------------------------------------------------------------------------------
 // layout / pooling companions
 // ------------------------------------------------------------------------------------------------
-__constant__ int kViewOrderBf[6] = {0, 1, 2, 5, 4, 3};
-
-// masked-view task of BasicAE (autoencoder.py:59-73), as stitch6_kernel / stitch6_u8_ptrs_kernel do it for fp32: wide slot `mask_slot`
-// (-1: none) is blanked and its fp32 values -- the same expressions, so the same bits as the fp32 path's target -- go to `target` [B,3,H,W]
-__device__ __forceinline__ void bf_stitch_target(float* __restrict__ target, int b, int yy, int xx, int H, int W, float c0, float c1,
-                                                 float c2) {
-  if (!target) return;
-  const long plane = (long)H * W;
-  float* t = target + (long)b * 3 * plane + (long)yy * W + xx;
-  t[0] = c0; t[plane] = c1; t[2 * plane] = c2;
-}
-
-// [B,6,3,H,W] fp32 camera views -> wide NHWC4 bf16 (view order of wide_stitch_six_images, roadmap_bce_v2.py:53-64)
-__global__ __launch_bounds__(256) void stitch6_bf16_kernel(const float* __restrict__ views, u32x2* __restrict__ wide4, float* __restrict__ target,
-                                                               int B, int H, int W, int mask_slot) {
-  const long npx = (long)B * H * 6 * W;
-  const long plane = (long)H * W;
-  for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(px % (6 * W));
-    const int yy = (int)((px / (6 * W)) % H);
-    const int b = (int)(px / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const float* src = views + (((long)b * 6 + kViewOrderBf[slot]) * 3) * plane + (long)yy * W + xx;
-    u32x2 o;
-    o.x = dd_pack_bf16(src[0], src[plane]);
-    o.y = dd_pack_bf16(src[2 * plane], 0.f);
-    if (slot == mask_slot) {
-      bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
-      o.x = 0u; o.y = 0u;
-    }
-    wide4[px] = o;
-  }
-}
-
-// the same from a table of per-sample base pointers (the collate's tuple, helper.py:22-23: no torch.stack of the views)
-struct BfSamplePtrs {
-  const float* p[64];
-};
-__global__ __launch_bounds__(256) void stitch6_bf16_ptrs_kernel(const BfSamplePtrs samples, u32x2* __restrict__ wide4, float* __restrict__ target,
-                                                                    int B, int H, int W, int mask_slot) {
-  const long npx = (long)B * H * 6 * W;
-  const long plane = (long)H * W;
-  for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(px % (6 * W));
-    const int yy = (int)((px / (6 * W)) % H);
-    const int b = (int)(px / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const float* src = samples.p[b] + ((long)kViewOrderBf[slot] * 3) * plane + (long)yy * W + xx;
-    u32x2 o;
-    o.x = dd_pack_bf16(src[0], src[plane]);
-    o.y = dd_pack_bf16(src[2 * plane], 0.f);
-    if (slot == mask_slot) {
-      bf_stitch_target(target, b, yy, xx, H, W, src[0], src[plane], src[2 * plane]);
-      o.x = 0u; o.y = 0u;
-    }
-    wide4[px] = o;
-  }
-}
-
-// the same from uint8 HWC frames (per-sample [6,H,W,3], a JPEG decoder's output): ToTensor's /255 (a true division, as
-// torchvision does it) and the bf16 rounding of the quotient fused with the gather -- the values dd_stitch6_bf16 makes of
-// frames.float() / 255
-struct BfSamplePtrsU8 {
-  const unsigned char* p[64];
-};
-__global__ __launch_bounds__(256) void stitch6_bf16_u8_ptrs_kernel(const BfSamplePtrsU8 samples, u32x2* __restrict__ wide4, float* __restrict__ target,
-                                                                       int B, int H, int W, int mask_slot) {
-  const long npx = (long)B * H * 6 * W;
-  for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < npx; px += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(px % (6 * W));
-    const int yy = (int)((px / (6 * W)) % H);
-    const int b = (int)(px / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const unsigned char* src = samples.p[b] + (((long)kViewOrderBf[slot] * H + yy) * W + xx) * 3;
-    const float c0 = (float)src[0] / 255.0f, c1 = (float)src[1] / 255.0f, c2 = (float)src[2] / 255.0f;
-    u32x2 o;
-    o.x = dd_pack_bf16(c0, c1);
-    o.y = dd_pack_bf16(c2, 0.f);
-    if (slot == mask_slot) {
-      bf_stitch_target(target, b, yy, xx, H, W, c0, c1, c2);
-      o.x = 0u; o.y = 0u;
-    }
-    wide4[px] = o;
-  }
-}
-
 // max_pool1d(4) over the NCHW-flattened feature (components.py:46-47) from an NHWC bf16 tensor, H*W % 4 == 0:
 // thread = (4 consecutive flat pixels, 4 channels)
 __global__ __launch_bounds__(256) void pool4_bf16_fwd(const u32x2* __restrict__ feat, float* __restrict__ pooled, int B, long HW, int C) {
@@ -1049,72 +963,11 @@ int dd_conv_bf16_wgrad(const uint16_t* x, const uint16_t* dy, float* dweight, fl
   return launch_wgrad<32, 2>(x, dy, dweight, dbias, g, workspace, workspace_bytes, st);
 }
 
-int dd_stitch6_bf16_masked(const float* views, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height, int32_t width,
-                           int32_t mask_slot, void* stream) {
-  DD_REQUIRE(views && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16: bad argument");
-  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16: mask_slot %d", mask_slot);
-  const long npx = (long)batch * height * 6 * width;
-  hipLaunchKernelGGL(stitch6_bf16_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                     (hipStream_t)stream, views, (u32x2*)wide_nhwc4, target, batch, height, width, mask_slot);
-  DD_LAUNCH_CHECK("stitch6_bf16");
-  return 0;
-}
-
-int dd_stitch6_bf16(const float* views, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width, void* stream) {
-  return dd_stitch6_bf16_masked(views, wide_nhwc4, nullptr, batch, height, width, -1, stream);
-}
-
-int dd_stitch6_bf16_ptrs_masked(const float* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch, int32_t height,
-                                int32_t width, int32_t mask_slot, void* stream) {
-  DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: bad argument");
-  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: mask_slot %d", mask_slot);
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    BfSamplePtrs tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_bf16_ptrs: null sample pointer");
-    const long npx = (long)nb * height * 6 * width;
-    hipLaunchKernelGGL(stitch6_bf16_ptrs_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width,
-                       target ? target + (long)b0 * 3 * height * width : nullptr, nb, height, width, mask_slot);
-    DD_LAUNCH_CHECK("stitch6_bf16_ptrs");
-  }
-  return 0;
-}
-
-int dd_stitch6_bf16_ptrs(const float* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
-                         void* stream) {
-  return dd_stitch6_bf16_ptrs_masked(sample_ptrs, wide_nhwc4, nullptr, batch, height, width, -1, stream);
-}
-
-int dd_stitch6_bf16_u8_ptrs_masked(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, float* target, int32_t batch,
-                                   int32_t height, int32_t width, int32_t mask_slot, void* stream) {
-  DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: bad argument");
-  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: mask_slot %d", mask_slot);
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    BfSamplePtrsU8 tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_bf16_u8_ptrs: null sample pointer");
-    const long npx = (long)nb * height * 6 * width;
-    hipLaunchKernelGGL(stitch6_bf16_u8_ptrs_kernel, dim3((unsigned)min((npx + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (u32x2*)wide_nhwc4 + (long)b0 * height * 6 * width,
-                       target ? target + (long)b0 * 3 * height * width : nullptr, nb, height, width, mask_slot);
-    DD_LAUNCH_CHECK("stitch6_bf16_u8_ptrs");
-  }
-  return 0;
-}
-
-int dd_stitch6_bf16_u8_ptrs(const unsigned char* const* sample_ptrs, uint16_t* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
-                            void* stream) {
-  return dd_stitch6_bf16_u8_ptrs_masked(sample_ptrs, wide_nhwc4, nullptr, batch, height, width, -1, stream);
-}
-
 int dd_pool4_bf16_fwd(const uint16_t* feat, float* pooled, int32_t batch, int32_t h, int32_t w, int32_t c, void* stream) {
   DD_REQUIRE(feat && pooled && batch > 0 && h > 0 && w > 0 && c > 0, DD_ERR_BAD_ARG, "pool4_bf16_fwd: bad argument");
   DD_REQUIRE(((long)h * w) % 4 == 0 && c % 4 == 0, DD_ERR_UNSUPPORTED, "pool4_bf16: H*W and C must be multiples of 4 (got %dx%d, C %d)", h, w, c);
   const long total = (long)batch * ((long)h * w / 4) * (c / 4);
-  hipLaunchKernelGGL(pool4_bf16_fwd, dim3((unsigned)min((total + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(pool4_bf16_fwd, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                      (const u32x2*)feat, pooled, batch, (long)h * w, c);
   DD_LAUNCH_CHECK("pool4_bf16_fwd");
   return 0;
@@ -1125,7 +978,7 @@ int dd_pool4_relu_bf16_bwd(const float* dpooled, const uint16_t* feat, uint16_t*
   DD_REQUIRE(dpooled && feat && dfeat && batch > 0 && h > 0 && w > 0 && c > 0, DD_ERR_BAD_ARG, "pool4_bf16_bwd: bad argument");
   DD_REQUIRE(((long)h * w) % 4 == 0 && c % 4 == 0, DD_ERR_UNSUPPORTED, "pool4_bf16: H*W and C must be multiples of 4 (got %dx%d, C %d)", h, w, c);
   const long total = (long)batch * ((long)h * w / 4) * (c / 4);
-  hipLaunchKernelGGL(pool4_bf16_bwd, dim3((unsigned)min((total + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(pool4_bf16_bwd, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream,
                      dpooled, (const u32x2*)feat, (u32x2*)dfeat, batch, (long)h * w, c);
   DD_LAUNCH_CHECK("pool4_bf16_bwd");
   return 0;
@@ -1168,7 +1021,7 @@ int dd_pool4_idx_relu_bf16_bwd(const float* dpooled, const uint16_t* idx, uint16
 
 int dd_f32_to_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
   DD_REQUIRE(src && dst && n > 0 && n % 4 == 0, DD_ERR_BAD_ARG, "f32_to_bf16: bad argument (n must be a multiple of 4)");
-  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)min((n / 4 + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3(dd_grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream,
                      (const f32x4*)src, (u32x2*)dst, (long)(n / 4));
   DD_LAUNCH_CHECK("f32_to_bf16");
   return 0;
@@ -1176,7 +1029,7 @@ int dd_f32_to_bf16(const float* src, uint16_t* dst, int64_t n, void* stream) {
 
 int dd_bf16_to_f32(const uint16_t* src, float* dst, int64_t n, void* stream) {
   DD_REQUIRE(src && dst && n > 0 && n % 4 == 0, DD_ERR_BAD_ARG, "bf16_to_f32: bad argument (n must be a multiple of 4)");
-  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)min((n / 4 + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(dd_grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream,
                      (const u32x2*)src, (f32x4*)dst, (long)(n / 4));
   DD_LAUNCH_CHECK("bf16_to_f32");
   return 0;

@@ -29,6 +29,34 @@ int dd_allow_lds(const void* kernel, size_t bytes);
 
 static inline int dd_conv_out(int in, int stride) { return (in + 2 - 3) / stride + 1; }
 
+// grid of a grid-stride kernel of 256 lanes over n items: one lane per item, at most 8 workgroups per compute unit
+static inline int dd_grid_for(long n) { return (int)min((n + 255) / 256, (long)DD_NUM_CU * 8); }
+
+// The collate hands a batch over as a TUPLE of per-sample tensors (collate_fn = tuple(zip(*batch)), helper.py:22-23).  Kernels read
+// them where they lie through a table of base pointers passed BY VALUE in the kernel arguments (no device-side table, no torch.stack
+// copy), 64 samples per launch.
+template <typename T>
+struct DdPtrTable {
+  const T* p[64];
+  __device__ const T* sample(int b) const { return p[b]; }
+  __device__ long first(int) const { return 0; }      // an entry points at its sample's first element (camera_gather.hip: view)
+};
+
+// Walks `batch` pointers in chunks of 64: each chunk's table is filled (unused entries null), its entries checked for null on the
+// host ("<who>: null <what> pointer"), and `launch(table, b0, nb)` called for samples b0 .. b0 + nb - 1 (it offsets its outputs by b0 samples), then checked.
+template <typename T, typename Launch>
+int dd_for_each_chunk(const char* who, const char* what, const T* const* ptrs, int batch, Launch launch) {
+  for (int b0 = 0; b0 < batch; b0 += 64) {
+    const int nb = min(64, batch - b0);
+    DdPtrTable<T> tab;
+    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? ptrs[b0 + i] : nullptr;
+    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "%s: null %s pointer", who, what);
+    launch(tab, b0, nb);
+    DD_LAUNCH_CHECK(who);
+  }
+  return 0;
+}
+
 // s += p[0] + p[stride] + ... (n terms), left to right -- the order, and so the bits, of the plain loop -- with SIXTEEN loads in flight:
 // the second stages of the weight / bias gradients add a few hundred per-workgroup partials per output element, and written as
 // `for (w...) s += part[w * stride]` each add waited for its own load: 50-60 us of memory latency per launch for a few KB of output

@@ -426,67 +426,6 @@ __global__ __launch_bounds__(1024) void gconv_wgrad_reduce(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------- small helpers
-__global__ __launch_bounds__(256) void view_to_nhwc4_kernel(const float* __restrict__ views, f32x4* __restrict__ out, int B,
-                                                            int H, int W, int view, int tf) {
-  const int Ho = (tf == 1 || tf == 2) ? W : H, Wo = (tf == 1 || tf == 2) ? H : W;
-  const long total = (long)B * Ho * Wo, plane = (long)H * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho);
-    const int b = (int)(p / ((long)Wo * Ho));
-    int ys, xs;
-    if (tf == 0) { ys = i; xs = j; }
-    else if (tf == 1) { ys = j; xs = W - 1 - i; }         // rot90(k=1, dims [2,3]): out[i][j] = in[j][W-1-i]
-    else if (tf == 2) { ys = H - 1 - j; xs = i; }         // rot90(k=1, dims [3,2]): out[i][j] = in[H-1-j][i]
-    else { ys = H - 1 - i; xs = W - 1 - j; }              // flip([2,3])
-    const float* src = views + (((long)b * 6 + view) * 3) * plane + (long)ys * W + xs;
-    out[p] = f32x4{src[0], src[plane], src[2 * plane], 0.f};
-  }
-}
-
-// the same from a table of per-sample base pointers (each [6,3,H,W]): the collate's tuple (helper.py:22-23) without torch.stack
-struct ViewSamplePtrs {
-  const float* p[64];
-};
-
-__global__ __launch_bounds__(256) void view_to_nhwc4_ptrs_kernel(const ViewSamplePtrs samples, f32x4* __restrict__ out, int B,
-                                                                 int H, int W, int view, int tf) {
-  const int Ho = (tf == 1 || tf == 2) ? W : H, Wo = (tf == 1 || tf == 2) ? H : W;
-  const long total = (long)B * Ho * Wo, plane = (long)H * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho);
-    const int b = (int)(p / ((long)Wo * Ho));
-    int ys, xs;
-    if (tf == 0) { ys = i; xs = j; }
-    else if (tf == 1) { ys = j; xs = W - 1 - i; }
-    else if (tf == 2) { ys = H - 1 - j; xs = i; }
-    else { ys = H - 1 - i; xs = W - 1 - j; }
-    const float* src = samples.p[b] + ((long)view * 3) * plane + (long)ys * W + xs;
-    out[p] = f32x4{src[0], src[plane], src[2 * plane], 0.f};
-  }
-}
-
-// the same from uint8 HWC frames (per-sample [6,H,W,3]): ToTensor's /255 (true division) fused with the re-layout
-struct ViewSamplePtrsU8 {
-  const unsigned char* p[64];
-};
-
-__global__ __launch_bounds__(256) void view_to_nhwc4_u8_ptrs_kernel(const ViewSamplePtrsU8 samples, f32x4* __restrict__ out, int B,
-                                                                    int H, int W, int view, int tf) {
-  const int Ho = (tf == 1 || tf == 2) ? W : H, Wo = (tf == 1 || tf == 2) ? H : W;
-  const long total = (long)B * Ho * Wo;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(p % Wo), i = (int)((p / Wo) % Ho);
-    const int b = (int)(p / ((long)Wo * Ho));
-    int ys, xs;
-    if (tf == 0) { ys = i; xs = j; }
-    else if (tf == 1) { ys = j; xs = W - 1 - i; }
-    else if (tf == 2) { ys = H - 1 - j; xs = i; }
-    else { ys = H - 1 - i; xs = W - 1 - j; }
-    const unsigned char* src = samples.p[b] + (((long)view * H + ys) * W + xs) * 3;
-    out[p] = f32x4{(float)src[0] / 255.0f, (float)src[1] / 255.0f, (float)src[2] / 255.0f, 0.f};
-  }
-}
-
 __global__ __launch_bounds__(256) void add_kernel(const f32x4* __restrict__ a, const f32x4* __restrict__ b,
                                                   f32x4* __restrict__ out, long n4) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) out[i] = a[i] + b[i];
@@ -1160,7 +1099,7 @@ int dd_deconv2x2_c1_fwd(const float* x, const float* wt, const float* bias, floa
   DD_REQUIRE(x && wt && bias && probs && batch > 0 && h > 0 && w > 0, DD_ERR_BAD_ARG, "deconv2x2_c1_fwd: bad argument");
   DD_REQUIRE(c == 8, DD_ERR_UNSUPPORTED, "deconv2x2_c1: Cin %d (the box heads end in 8 -> 1)", c);
   const long npix = (long)batch * h * w;
-  hipLaunchKernelGGL(deconv2x2_c1_fwd_kernel<8>, dim3((unsigned)min((npix + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
+  hipLaunchKernelGGL(deconv2x2_c1_fwd_kernel<8>, dim3(dd_grid_for(npix)), dim3(256), 0,
                      (hipStream_t)stream, x, wt, bias, probs, npix, w);
   DD_LAUNCH_CHECK("deconv2x2_c1_fwd");
   return 0;
@@ -1179,51 +1118,6 @@ int dd_deconv2x2_c1_bwd(const float* x, const float* wt, const float* probs, con
   hipLaunchKernelGGL(deconv2x2_c1_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, dwt, dbias, grid,
                      c * 4 + 1);
   DD_LAUNCH_CHECK("deconv2x2_c1_reduce");
-  return 0;
-}
-
-int dd_view_to_nhwc4(const float* views, float* out, int32_t batch, int32_t height, int32_t width, int32_t view,
-                     int32_t transform, void* stream) {
-  DD_REQUIRE(views && out && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "view_to_nhwc4: bad argument");
-  DD_REQUIRE(view >= 0 && view < 6 && transform >= 0 && transform <= 3, DD_ERR_BAD_ARG, "view_to_nhwc4: view %d transform %d", view, transform);
-  const long total = (long)batch * height * width;
-  hipLaunchKernelGGL(view_to_nhwc4_kernel, dim3((unsigned)min((total + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                     (hipStream_t)stream, views, (f32x4*)out, batch, height, width, view, transform);
-  DD_LAUNCH_CHECK("view_to_nhwc4");
-  return 0;
-}
-
-int dd_view_to_nhwc4_ptrs(const float* const* sample_ptrs, float* out, int32_t batch, int32_t height, int32_t width, int32_t view,
-                          int32_t transform, void* stream) {
-  DD_REQUIRE(sample_ptrs && out && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "view_to_nhwc4_ptrs: bad argument");
-  DD_REQUIRE(view >= 0 && view < 6 && transform >= 0 && transform <= 3, DD_ERR_BAD_ARG, "view_to_nhwc4_ptrs: view %d transform %d", view, transform);
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    ViewSamplePtrs tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "view_to_nhwc4_ptrs: null sample pointer");
-    const long total = (long)nb * height * width;
-    hipLaunchKernelGGL(view_to_nhwc4_ptrs_kernel, dim3((unsigned)min((total + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (f32x4*)out + (long)b0 * height * width, nb, height, width, view, transform);
-    DD_LAUNCH_CHECK("view_to_nhwc4_ptrs");
-  }
-  return 0;
-}
-
-int dd_view_to_nhwc4_u8_ptrs(const unsigned char* const* sample_ptrs, float* out, int32_t batch, int32_t height, int32_t width,
-                             int32_t view, int32_t transform, void* stream) {
-  DD_REQUIRE(sample_ptrs && out && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "view_to_nhwc4_u8_ptrs: bad argument");
-  DD_REQUIRE(view >= 0 && view < 6 && transform >= 0 && transform <= 3, DD_ERR_BAD_ARG, "view_to_nhwc4_u8_ptrs: view %d transform %d", view, transform);
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    ViewSamplePtrsU8 tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "view_to_nhwc4_u8_ptrs: null sample pointer");
-    const long total = (long)nb * height * width;
-    hipLaunchKernelGGL(view_to_nhwc4_u8_ptrs_kernel, dim3((unsigned)min((total + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0,
-                       (hipStream_t)stream, tab, (f32x4*)out + (long)b0 * height * width, nb, height, width, view, transform);
-    DD_LAUNCH_CHECK("view_to_nhwc4_u8_ptrs");
-  }
   return 0;
 }
 
@@ -1261,7 +1155,7 @@ int dd_copy_channels_window(const float* src, float* dst, int32_t batch, int32_t
 int dd_add(const float* a, const float* b, float* out, int64_t n, void* stream) {
   DD_REQUIRE(a && b && out && n > 0 && n % 4 == 0, DD_ERR_BAD_ARG, "add: bad argument");
   const long n4 = n / 4;
-  hipLaunchKernelGGL(add_kernel, dim3((unsigned)min((n4 + 255) / 256, (long)DD_NUM_CU * 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(add_kernel, dim3(dd_grid_for(n4)), dim3(256), 0, (hipStream_t)stream,
                      (const f32x4*)a, (const f32x4*)b, (f32x4*)out, n4);
   DD_LAUNCH_CHECK("add");
   return 0;

@@ -1,108 +1,12 @@
 // Layout glue of the hot path, fused with the NCHW<->NHWC conversion the MFMA kernels want:
-//   dd_stitch6        6-view reorder + wide stitch (+ masked-view task)   reference roadmap_bce_v2.py:53-64, autoencoder.py:53-73
 //   dd_nchw_to_nhwc / dd_nhwc_to_nchw                                     API edges of Encoder.forward (components.py:40)
 //   dd_pool4_*        max_pool1d(4) over the NCHW-flattened c3 feature    components.py:46-47
+//   dd_subsample_nhwc4*   the taps of rm_conv_1 as an NHWC4 image
 // All of it is HBM-bound byte shuffling: every kernel reads and writes each byte once, 16 bytes per lane
-// on the NHWC side.
+// on the NHWC side.  (The camera images' gather, dd_stitch6* and dd_view_to_nhwc4*: camera_gather.hip.)
 #include "dd_common.h"
 
 namespace {
-
-__constant__ int kViewOrder[6] = {0, 1, 2, 5, 4, 3};
-
-// one thread per wide-image pixel: reads 3 planes (coalesced along x), writes one 16-byte NHWC4 pixel
-__global__ __launch_bounds__(256) void stitch6_kernel(const float* __restrict__ views, f32x4* __restrict__ wide4,
-                                                      float* __restrict__ wide_nchw, float* __restrict__ target,
-                                                      int B, int H, int W, int mask_slot) {
-  const long npx = (long)B * H * 6 * W;
-  const long plane = (long)H * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(p % (6 * W));
-    const int yy = (int)((p / (6 * W)) % H);
-    const int b = (int)(p / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const float* src = views + (((long)b * 6 + kViewOrder[slot]) * 3) * plane + (long)yy * W + xx;
-    float c0 = src[0], c1 = src[plane], c2 = src[2 * plane];
-    if (slot == mask_slot) {
-      if (target) {
-        float* t = target + ((long)b * 3) * plane + (long)yy * W + xx;
-        t[0] = c0; t[plane] = c1; t[2 * plane] = c2;
-      }
-      c0 = c1 = c2 = 0.f;
-    }
-    if (wide4) wide4[p] = f32x4{c0, c1, c2, 0.f};
-    if (wide_nchw) {
-      float* o = wide_nchw + ((long)b * 3) * H * 6 * W + (long)yy * 6 * W + xw;
-      o[0] = c0; o[(long)H * 6 * W] = c1; o[2L * H * 6 * W] = c2;
-    }
-  }
-}
-
-// The reference hands the batch over as a TUPLE of per-sample tensors (collate_fn = tuple(zip(*batch)), helper.py:22-23)
-// and stacks them first (roadmap_bce_v2.py:55).  Reading through a table of per-sample base pointers skips that copy.
-struct SamplePtrs {
-  const float* p[64];      // passed by value in the kernel arguments: no device-side table, no extra copy
-};
-
-__global__ __launch_bounds__(256) void stitch6_ptrs_kernel(const SamplePtrs samples, f32x4* __restrict__ wide4,
-                                                           int B, int H, int W) {
-  const long npx = (long)B * H * 6 * W;
-  const long plane = (long)H * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(p % (6 * W));
-    const int yy = (int)((p / (6 * W)) % H);
-    const int b = (int)(p / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const float* src = samples.p[b] + ((long)kViewOrder[slot] * 3) * plane + (long)yy * W + xx;
-    wide4[p] = f32x4{src[0], src[plane], src[2 * plane], 0.f};
-  }
-}
-
-// uint8 HWC camera frames (what a JPEG decoder emits) -> the same wide NHWC4 fp32 image: ToTensor's /255
-// (reference autoencoder.py:133 torchvision.transforms.ToTensor) fused with the gather; 3 bytes in, 16 bytes out.
-__global__ __launch_bounds__(256) void stitch6_u8_kernel(const unsigned char* __restrict__ frames, f32x4* __restrict__ wide4,
-                                                         int B, int H, int W) {
-  const long npx = (long)B * H * 6 * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(p % (6 * W));
-    const int yy = (int)((p / (6 * W)) % H);
-    const int b = (int)(p / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const unsigned char* src = frames + ((((long)b * 6 + kViewOrder[slot]) * H + yy) * W + xx) * 3;
-    // a true division, correctly rounded: bit for bit ToTensor's img.float().div(255) (x * (1/255.f) differs in the last place for
-    // some of the 256 values)
-    wide4[p] = f32x4{(float)src[0] / 255.0f, (float)src[1] / 255.0f, (float)src[2] / 255.0f, 0.f};
-  }
-}
-
-// The same from a table of per-sample base pointers (each [6,H,W,3] uint8: the collate's tuple of decoded frames), with the
-// masked-view task of BasicAE.six_to_one_task (autoencoder.py:59-73) optional: view slot `mask_slot` of the wide image is
-// blanked and written, as fp32 NCHW, to `target`.
-struct SamplePtrsU8 {
-  const unsigned char* p[64];
-};
-
-__global__ __launch_bounds__(256) void stitch6_u8_ptrs_kernel(const SamplePtrsU8 samples, f32x4* __restrict__ wide4,
-                                                              float* __restrict__ target, int B, int H, int W, int mask_slot) {
-  const long npx = (long)B * H * 6 * W;
-  const long plane = (long)H * W;
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += (long)gridDim.x * blockDim.x) {
-    const int xw = (int)(p % (6 * W));
-    const int yy = (int)((p / (6 * W)) % H);
-    const int b = (int)(p / ((long)6 * W * H));
-    const int slot = xw / W, xx = xw - slot * W;
-    const unsigned char* src = samples.p[b] + (((long)kViewOrder[slot] * H + yy) * W + xx) * 3;
-    float c0 = (float)src[0] / 255.0f, c1 = (float)src[1] / 255.0f, c2 = (float)src[2] / 255.0f;
-    if (slot == mask_slot) {
-      if (target) {
-        float* t = target + ((long)b * 3) * plane + (long)yy * W + xx;
-        t[0] = c0; t[plane] = c1; t[2 * plane] = c2;
-      }
-      c0 = c1 = c2 = 0.f;
-    }
-    wide4[p] = f32x4{c0, c1, c2, 0.f};
-  }
-}
 
 // NCHW -> NHWC(Cs): one thread per (pixel, 4-channel group)
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ src, f32x4* __restrict__ dst,
@@ -441,8 +345,6 @@ __global__ __launch_bounds__(256) void pool4_bwd_any(const float* __restrict__ d
   }
 }
 
-int grid_for(long n) { return (int)min((n + 255) / 256, (long)DD_NUM_CU * 8); }
-
 // dst[b][u][v] = (src[b][stride*u + offset][stride*v + offset], 0, 0, 0), zero outside the image: the pixels a strided, equally
 // dilated, single-channel convolution ever reads (rm_conv_1: k7 stride 3 dilation 3 pad 1 touches only rows / columns
 // 3u - 1), as an NHWC4 image on which that convolution is dense
@@ -461,12 +363,8 @@ __global__ __launch_bounds__(256) void subsample_nhwc4_kernel(const float* __res
 
 // the same from the collate's per-sample masks where they lie: bool / uint8 [h,w] tensors (data_helper.py:137-139 hands the
 // road image over as a bool tensor), read through a pointer table -- no torch.stack, no .float() copy (spatial_w_rm.py:105)
-struct MaskPtrs {
-  const unsigned char* p[64];
-};
-
-__global__ __launch_bounds__(256) void subsample_nhwc4_u8_ptrs_kernel(const MaskPtrs masks, f32x4* __restrict__ dst, int h, int w,
-                                                                      int oh, int ow, int stride, int offset, long total) {
+__global__ __launch_bounds__(256) void subsample_nhwc4_u8_ptrs_kernel(const DdPtrTable<unsigned char> masks, f32x4* __restrict__ dst,
+                                                                      int h, int w, int oh, int ow, int stride, int offset, long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int v = (int)(i % ow);
@@ -482,76 +380,15 @@ __global__ __launch_bounds__(256) void subsample_nhwc4_u8_ptrs_kernel(const Mask
 
 extern "C" {
 
-int dd_stitch6(const float* views, float* wide_nhwc4, float* wide_nchw, float* target, int32_t batch, int32_t height,
-               int32_t width, int32_t mask_slot, void* stream) {
-  DD_REQUIRE(views && (wide_nhwc4 || wide_nchw), DD_ERR_BAD_ARG, "stitch6: NULL pointer");
-  DD_REQUIRE(batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6: non-positive size");
-  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6: mask_slot %d", mask_slot);
-  const long npx = (long)batch * height * 6 * width;
-  hipLaunchKernelGGL(stitch6_kernel, dim3(grid_for(npx)), dim3(256), 0, (hipStream_t)stream, views, (f32x4*)wide_nhwc4,
-                     wide_nchw, target, batch, height, width, mask_slot);
-  DD_LAUNCH_CHECK("stitch6");
-  return 0;
-}
-
-int dd_stitch6_ptrs(const float* const* sample_ptrs, float* wide_nhwc4, int32_t batch, int32_t height, int32_t width,
-                    void* stream) {
-  DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_ptrs: bad argument");
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    SamplePtrs tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_ptrs: null sample pointer");
-    const long npx = (long)nb * height * 6 * width;
-    hipLaunchKernelGGL(stitch6_ptrs_kernel, dim3(grid_for(npx)), dim3(256), 0, (hipStream_t)stream, tab,
-                       (f32x4*)wide_nhwc4 + (long)b0 * height * 6 * width, nb, height, width);
-    DD_LAUNCH_CHECK("stitch6_ptrs");
-  }
-  return 0;
-}
-
-int dd_stitch6_u8(const unsigned char* frames, float* wide_nhwc4, int32_t batch, int32_t height, int32_t width, void* stream) {
-  DD_REQUIRE(frames && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_u8: bad argument");
-  const long npx = (long)batch * height * 6 * width;
-  hipLaunchKernelGGL(stitch6_u8_kernel, dim3(grid_for(npx)), dim3(256), 0, (hipStream_t)stream, frames, (f32x4*)wide_nhwc4,
-                     batch, height, width);
-  DD_LAUNCH_CHECK("stitch6_u8");
-  return 0;
-}
-
-int dd_stitch6_u8_ptrs(const unsigned char* const* sample_ptrs, float* wide_nhwc4, float* target, int32_t batch, int32_t height,
-                       int32_t width, int32_t mask_slot, void* stream) {
-  DD_REQUIRE(sample_ptrs && wide_nhwc4 && batch > 0 && height > 0 && width > 0, DD_ERR_BAD_ARG, "stitch6_u8_ptrs: bad argument");
-  DD_REQUIRE(mask_slot >= -1 && mask_slot < 6, DD_ERR_BAD_ARG, "stitch6_u8_ptrs: mask_slot %d", mask_slot);
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    SamplePtrsU8 tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? sample_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "stitch6_u8_ptrs: null sample pointer");
-    const long npx = (long)nb * height * 6 * width;
-    hipLaunchKernelGGL(stitch6_u8_ptrs_kernel, dim3(grid_for(npx)), dim3(256), 0, (hipStream_t)stream, tab,
-                       (f32x4*)wide_nhwc4 + (long)b0 * height * 6 * width, target ? target + (long)b0 * 3 * height * width : nullptr, nb,
-                       height, width, mask_slot);
-    DD_LAUNCH_CHECK("stitch6_u8_ptrs");
-  }
-  return 0;
-}
-
 int dd_subsample_nhwc4_u8_ptrs(const unsigned char* const* mask_ptrs, float* dst, int32_t batch, int32_t h, int32_t w, int32_t oh,
                                int32_t ow, int32_t stride, int32_t offset, void* stream) {
   DD_REQUIRE(mask_ptrs && dst && batch > 0 && h > 0 && w > 0 && oh > 0 && ow > 0 && stride > 0, DD_ERR_BAD_ARG,
              "subsample_nhwc4_u8_ptrs: bad argument");
-  for (int b0 = 0; b0 < batch; b0 += 64) {
-    const int nb = min(64, batch - b0);
-    MaskPtrs tab;
-    for (int i = 0; i < 64; ++i) tab.p[i] = i < nb ? mask_ptrs[b0 + i] : nullptr;
-    for (int i = 0; i < nb; ++i) DD_REQUIRE(tab.p[i] != nullptr, DD_ERR_BAD_ARG, "subsample_nhwc4_u8_ptrs: null mask pointer");
+  return dd_for_each_chunk("subsample_nhwc4_u8_ptrs", "mask", mask_ptrs, batch, [&](const DdPtrTable<unsigned char>& tab, int b0, int nb) {
     const long total = (long)nb * oh * ow;
     hipLaunchKernelGGL(subsample_nhwc4_u8_ptrs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tab,
                        (f32x4*)dst + (long)b0 * oh * ow, h, w, oh, ow, stride, offset, total);
-    DD_LAUNCH_CHECK("subsample_nhwc4_u8_ptrs");
-  }
-  return 0;
+  });
 }
 
 int dd_subsample_nhwc4(const float* src, float* dst, int32_t batch, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t stride,
@@ -576,7 +413,7 @@ int dd_nchw_to_nhwc(const float* src, float* dst, int32_t batch, int32_t c, int3
     return 0;
   }
   const long total = (long)batch * h * w * (c_store / 4);
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, (f32x4*)dst,
+  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, (f32x4*)dst,
                      batch, c, h, w, c_store);
   DD_LAUNCH_CHECK("nchw_to_nhwc");
   return 0;
@@ -593,7 +430,7 @@ int dd_nhwc_to_nchw(const float* src, float* dst, int32_t batch, int32_t c, int3
     return 0;
   }
   const long total = (long)batch * c * h * w;
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, dst, batch, c,
+  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, dst, batch, c,
                      h, w, c_store);
   DD_LAUNCH_CHECK("nhwc_to_nchw");
   return 0;
@@ -605,11 +442,11 @@ int dd_pool4_fwd(const float* feat, float* pooled, int32_t batch, int32_t h, int
   DD_REQUIRE(((long)c * HW) / 4 > 0, DD_ERR_UNSUPPORTED, "pool4_fwd: fewer than 4 elements");
   if (HW % 4 == 0 && c % 4 == 0) {
     const long total = (long)batch * (HW / 4) * (c / 4);
-    hipLaunchKernelGGL(pool4_fwd_quad<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat,
+    hipLaunchKernelGGL(pool4_fwd_quad<false>, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat,
                        pooled, (unsigned short*)nullptr, batch, HW, c);
   } else {
     const long total = (long)batch * (((long)c * HW) / 4);
-    hipLaunchKernelGGL(pool4_fwd_any, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, feat, pooled, batch, HW,
+    hipLaunchKernelGGL(pool4_fwd_any, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, feat, pooled, batch, HW,
                        c);
   }
   DD_LAUNCH_CHECK("pool4_fwd");
@@ -622,11 +459,11 @@ int dd_pool4_relu_bwd(const float* dpooled, const float* feat, float* dfeat, int
   const long HW = (long)h * w;
   if (HW % 4 == 0 && c % 4 == 0) {
     const long total = (long)batch * (HW / 4) * (c / 4);
-    hipLaunchKernelGGL(pool4_bwd_quad, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled,
+    hipLaunchKernelGGL(pool4_bwd_quad, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled,
                        (const f32x4*)feat, (f32x4*)dfeat, batch, HW, c);
   } else {
     const long total = (long)batch * HW * c;
-    hipLaunchKernelGGL(pool4_bwd_any, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, feat, dfeat,
+    hipLaunchKernelGGL(pool4_bwd_any, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, feat, dfeat,
                        batch, HW, c);
   }
   DD_LAUNCH_CHECK("pool4_bwd");
@@ -664,7 +501,7 @@ int dd_pool4_fwd_idx(const float* feat, float* pooled, uint16_t* idx, int32_t ba
     hipLaunchKernelGGL(pool4_fwd_tile32, dim3((unsigned)(batch * qblocks)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat, pooled,
                        (unsigned*)idx, quads, (int)qblocks);
   else
-    hipLaunchKernelGGL(pool4_fwd_quad<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat, pooled,
+    hipLaunchKernelGGL(pool4_fwd_quad<true>, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)feat, pooled,
                        (unsigned short*)idx, batch, (long)h * w, c);
   DD_LAUNCH_CHECK("pool4_fwd_idx");
   return 0;
@@ -680,7 +517,7 @@ int dd_pool4_idx_relu_bwd(const float* dpooled, const uint16_t* idx, float* dfea
     hipLaunchKernelGGL(pool4_bwd_tile32, dim3((unsigned)(batch * qblocks)), dim3(256), 0, (hipStream_t)stream, dpooled, (const unsigned*)idx,
                        (f32x4*)dfeat, quads, (int)qblocks);
   else
-    hipLaunchKernelGGL(pool4_bwd_idx_quad, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, (const unsigned short*)idx,
+    hipLaunchKernelGGL(pool4_bwd_idx_quad, dim3(dd_grid_for(total)), dim3(256), 0, (hipStream_t)stream, dpooled, (const unsigned short*)idx,
                        (f32x4*)dfeat, batch, (long)h * w, c);
   DD_LAUNCH_CHECK("pool4_idx_bwd");
   return 0;

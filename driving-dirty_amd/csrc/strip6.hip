@@ -80,7 +80,7 @@ struct S6Row {
       const bool ok = rowok && x < a.W;
       if (U8) {
         const unsigned char* src = (const unsigned char*)a.samples.p[b] + (((long)view * a.H + (rowok ? ys : 0)) * a.W + (ok ? x : 0)) * 3;
-        // a true division, correctly rounded: bit for bit ToTensor's img.float().div(255) (layout_pool.hip)
+        // a true division, correctly rounded: bit for bit ToTensor's img.float().div(255) (camera_gather.hip)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c][i] = ok ? (float)src[c] / 255.0f : 0.f;
       } else {

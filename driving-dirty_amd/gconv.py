@@ -402,49 +402,17 @@ def channel_sum(view, out, accumulate=False):
     call("dd_channel_sum", view.buf, out, b * mh * mw, cs, view.coff, view.chans, int(accumulate), ws)
 
 
+_VIEW_ENTRIES = {"views": "dd_view_to_nhwc4", "samples": "dd_view_to_nhwc4_ptrs", "frames": "dd_view_to_nhwc4_u8_ptrs"}      # by ops.camera_source's form
+
+
 def view_to_nhwc4(views, view, transform):
     """views [B,6,3,H,W] -- or the collate's tuple / list of B per-sample [6,3,H,W] tensors, read through a pointer table
     (no torch.stack) -- -> one view as NHWC4 with SpatialMappingCNN's rot90/flip applied (see dd_view_to_nhwc4).  uint8 frames
     ([B,6,H,W,3] or a tuple of [6,H,W,3]) are read as they are, ToTensor's /255 fused (dd_view_to_nhwc4_u8_ptrs)."""
-    def out(b, h, w, dev):
-        return torch.empty((b, w, h, 4) if transform in (1, 2) else (b, h, w, 4), device=dev, dtype=torch.float32)
-    if _ops().is_u8_frames(views):
-        table, b, h, w, dev, _keep = _ops().u8_table(views, "view_to_nhwc4")
-        y = out(b, h, w, dev)
-        call("dd_view_to_nhwc4_u8_ptrs", table, y, b, h, w, view, transform)
-    elif isinstance(views, (tuple, list)):
-        b = len(views)
-        _, _, h, w = views[0].shape
-        for t in views:
-            if not (_chk(t, "sample").dim() == 4 and tuple(t.shape) == (6, 3, h, w)):
-                raise _lib.HotpathError(f"view_to_nhwc4: expected samples of [6,3,{h},{w}], got {tuple(t.shape)}")
-        y = out(b, h, w, views[0].device)
-        call("dd_view_to_nhwc4_ptrs", (C.c_void_p * b)(*[t.data_ptr() for t in views]), y, b, h, w, view, transform)
-    else:
-        b, _, _, h, w = views.shape
-        y = out(b, h, w, views.device)
-        call("dd_view_to_nhwc4", _chk(views, "views"), y, b, h, w, view, transform)
+    form, src, b, h, w, dev, _keep = _ops().camera_source(views, "view_to_nhwc4")
+    y = torch.empty((b, w, h, 4) if transform in (1, 2) else (b, h, w, 4), device=dev, dtype=torch.float32)
+    call(_VIEW_ENTRIES[form], src, y, b, h, w, view, transform)
     return y
-
-
-def _sample_table(views, who):
-    """-> (ctypes table of per-sample device pointers, B, H, W, device, u8 flag, keepalive) for every form the data pipeline hands over:
-    fp32 [B,6,3,H,W], the collate's tuple of fp32 [6,3,H,W], uint8 [B,6,H,W,3] frames or a tuple of uint8 [6,H,W,3]."""
-    from . import ops
-    if ops.is_u8_frames(views):
-        table, b, h, w, dev, keep = ops.u8_table(views, who)
-        return table, b, h, w, dev, 1, keep
-    items = [views[i] for i in range(views.shape[0])] if isinstance(views, torch.Tensor) else list(views)
-    if not items:
-        raise _lib.HotpathError(f"{who}: empty batch")
-    _, _, h, w = items[0].shape
-    keep = []
-    for t in items:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (6, 3, h, w)):
-            raise _lib.HotpathError(f"{who}: expected fp32 [6,3,{h},{w}] samples on the GPU, got {tuple(getattr(t, 'shape', ()))}")
-        keep.append(t if t.is_contiguous() else t.contiguous())
-    table = (C.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-    return table, len(keep), h, w, keep[0].device, 0, keep
 
 
 def strip6_supported(h, w):
@@ -466,7 +434,7 @@ def strip6_fwd(views, weights, biases, want_bits=False):
     """The six strip convs of SpatialMappingCNN (+ bias + ReLU) in one launch, written into their tiles of the 3 x 2 mosaic
     (dd_strip6_fwd; spatial_bb/components.py:34-73).  ``weights`` / ``biases``: bl, fl, b, f, br, fr.  -> mosaic [B, 3 th, 2 tw, 32];
     with ``want_bits`` also its sign words, int32 [B, 3 th, 2 tw] (the ReLU mask of out_conv's data gradient on the Winograd kernels)."""
-    table, b, h, w, dev, u8, _keep = _sample_table(views, "strip6_fwd")
+    table, b, h, w, dev, u8, _keep = _ops().sample_table(views, "strip6_fwd")
     th, tw = (h - 1) // 3 + 1, (w - 50) // 2 + 1
     weights = [x.contiguous() for x in weights]
     mosaic = torch.empty((b, 3 * th, 2 * tw, 32), device=dev, dtype=torch.float32)
@@ -479,7 +447,7 @@ def strip6_fwd(views, weights, biases, want_bits=False):
 def strip6_wgrad(views, g):
     """Weight and bias gradients of the six strip convs from dL/d(mosaic) (ReLU-masked) in one launch + a fixed-order reduce
     (dd_strip6_wgrad).  -> ([dw] * 6, [db] * 6) in the order bl, fl, b, f, br, fr."""
-    table, b, h, w, dev, u8, _keep = _sample_table(views, "strip6_wgrad")
+    table, b, h, w, dev, u8, _keep = _ops().sample_table(views, "strip6_wgrad")
     th, tw = (h - 1) // 3 + 1, (w - 50) // 2 + 1
     _chk(g, "g")
     if tuple(g.shape) != (b, 3 * th, 2 * tw, 32):

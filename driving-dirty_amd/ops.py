@@ -29,32 +29,146 @@ def conv_desc(batch, h, w, cin_real, stride, rows_per_task=0):
 
 
 # ------------------------------------------------------------------------------------------------ layout
+def is_u8_frames(sample):
+    """uint8 camera frames as a decoder emits them: a [B,6,H,W,3] tensor or the collate's tuple / list of B [6,H,W,3] tensors."""
+    if isinstance(sample, torch.Tensor):
+        return sample.dtype == torch.uint8 and sample.dim() == 5
+    return isinstance(sample, (tuple, list)) and len(sample) > 0 and all(
+        isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 4 for t in sample)
+
+
+def sample_table(sample, who):
+    """-> (ctypes table of per-sample device pointers, B, H, W, device, u8 flag, keepalive) for every form the data pipeline hands over:
+    fp32 [B,6,3,H,W], the collate's tuple / list of fp32 [6,3,H,W], uint8 [B,6,H,W,3] frames or a tuple / list of uint8 [6,H,W,3].  A
+    stacked tensor is a table of its B slices: one code path for both forms.  Validated on the HOST, before anything is launched (a
+    faulting kernel can reset the GPU): an empty batch, and per sample its device, its dtype -- the first sample's, so a tuple that
+    mixes the forms is refused -- and its shape.  The keepalive holds the tensors the table points into (contiguous copies included)."""
+    stacked = isinstance(sample, torch.Tensor)
+    if not (stacked and sample.dim() == 5 or isinstance(sample, (tuple, list))):
+        raise _lib.HotpathError(f"{who}: expected a stacked 5-d tensor or a tuple / list of per-sample tensors, got {type(sample).__name__}")
+    items = [sample[i] for i in range(sample.shape[0])] if stacked else list(sample)
+    if not items:
+        raise _lib.HotpathError(f"{who}: empty batch")
+    first = items[0]
+    if not (isinstance(first, torch.Tensor) and first.dim() == 4):
+        raise _lib.HotpathError(f"{who}: expected fp32 [6,3,H,W] views or uint8 [6,H,W,3] frames per sample, got {tuple(getattr(first, 'shape', ()))}")
+    u8 = first.dtype == torch.uint8
+    h, w = first.shape[1:3] if u8 else first.shape[2:4]
+    dtype, shape = (torch.uint8, (6, h, w, 3)) if u8 else (torch.float32, (6, 3, h, w))
+    keep = []
+    for t in items:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == first.device and t.dtype == dtype and tuple(t.shape) == shape):
+            raise _lib.HotpathError(f"{who}: expected {'uint8' if u8 else 'fp32'} {list(shape)} samples on one GPU, got "
+                                    f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+        keep.append(t if t.is_contiguous() else t.contiguous())
+    table = (C.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+    return table, len(keep), h, w, first.device, int(u8), keep
+
+
+def u8_table(sample, who):
+    """``sample_table`` for a caller that takes uint8 frames only -> (table, B, H, W, device, keepalive)."""
+    table, b, h, w, dev, u8, keep = sample_table(sample, who)
+    if not u8:
+        raise _lib.HotpathError(f"{who}: expected uint8 frames of [6,H,W,3] per sample, got fp32 views")
+    return table, b, h, w, dev, keep
+
+
+def stacked_views(views, who):
+    """The operand of the entry points that read a stacked batch: contiguous fp32 [B,6,3,H,W] on the GPU -> (B, H, W)."""
+    if not (isinstance(views, torch.Tensor) and views.dim() == 5 and views.shape[0] > 0 and tuple(views.shape[1:3]) == (6, 3)):
+        raise _lib.HotpathError(f"{who}: expected [B,6,3,H,W], got {tuple(getattr(views, 'shape', ()))}")
+    _dev(views, "views")
+    return views.shape[0], views.shape[3], views.shape[4]
+
+
+# The wide-image entry points by (output precision, input form) -> (without, with a masked view).  Forms: "views" a stacked fp32
+# [B,6,3,H,W]; "samples" the collate's tuple of fp32 [6,3,H,W], read through a pointer table (no stack copy); "frames" uint8, stacked or
+# a tuple, always through the table.  fp32 has no entry that reads fp32 samples WITH a masked view: wide_image stacks them for dd_stitch6.
+WIDE_ENTRIES = {("fp32", "views"): ("dd_stitch6", "dd_stitch6"),
+                ("fp32", "samples"): ("dd_stitch6_ptrs", None),
+                ("fp32", "frames"): ("dd_stitch6_u8_ptrs", "dd_stitch6_u8_ptrs"),
+                ("bf16", "views"): ("dd_stitch6_bf16", "dd_stitch6_bf16_masked"),
+                ("bf16", "samples"): ("dd_stitch6_bf16_ptrs", "dd_stitch6_bf16_ptrs_masked"),
+                ("bf16", "frames"): ("dd_stitch6_bf16_u8_ptrs", "dd_stitch6_bf16_u8_ptrs_masked")}
+_TAKES_MASK = frozenset(masked for _, masked in WIDE_ENTRIES.values() if masked)      # their operands: ..., target, B, H, W, mask_slot
+
+
+def camera_source(sample, who):
+    """-> (form of WIDE_ENTRIES, the entry point's first operand, B, H, W, device, keepalive) for any of the four input forms.  A stacked
+    tensor or a sample that is not contiguous is COPIED (``.contiguous()``; the keepalive holds the copy), as ``wide_image`` has always
+    done; through this function that now also holds for ``stitch6_samples``, ``stitch6_bf16_samples`` and ``gconv.view_to_nhwc4``,
+    which used to refuse such input."""
+    if isinstance(sample, torch.Tensor) and sample.dtype != torch.uint8:
+        views = sample.contiguous()
+        return ("views", views, *stacked_views(views, who), views.device, views)
+    table, b, h, w, dev, u8, keep = sample_table(sample, who)
+    return "frames" if u8 else "samples", table, b, h, w, dev, keep
+
+
+def mask_arg(mask_slot, who):
+    """``mask_slot`` as the int the ABI takes: -1 (no masked view) or a wide slot 0 .. 5, checked on the host."""
+    if not -1 <= int(mask_slot) <= 5:
+        raise _lib.HotpathError(f"{who}: mask_slot {mask_slot} outside [-1, 5]")
+    return int(mask_slot)
+
+
+def wide_call(entry, src, b, h, w, dev, mask_slot=-1, want_target=False, want_nhwc4=True, want_nchw=False):
+    """The one body behind every wide-image shim: allocates what ``entry`` (a dd_stitch6* function) writes for ``src`` (a stacked
+    tensor or a pointer table, already validated) and calls it.  -> (wide NHWC4 [B,H,6W,4] fp32 or bf16, wide NCHW [B,3,H,6W], target
+    [B,3,H,W] fp32), None for what was not asked for."""
+    slot = mask_arg(mask_slot, entry)
+    masked, both = entry in _TAKES_MASK, entry == "dd_stitch6"      # dd_stitch6 alone has the NCHW output
+    if (slot >= 0 or want_target) and not masked or want_nchw and not both:
+        raise _lib.HotpathError(f"{entry}: has no {'NCHW output' if want_nchw and not both else 'masked view'}")
+    wide4 = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.bfloat16 if "bf16" in entry else torch.float32) if want_nhwc4 else None
+    wide = torch.empty((b, 3, h, 6 * w), device=dev, dtype=torch.float32) if want_nchw else None
+    tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
+    call(entry, src, wide4, *((wide,) if both else ()), *((tgt,) if masked else ()), b, h, w, *((slot,) if masked else ()))
+    return wide4, wide, tgt
+
+
 def stitch6(views, mask_slot=-1, want_nhwc4=True, want_nchw=False, want_target=False):
     """[B,6,3,H,W] -> wide image (view order [0,1,2,5,4,3]); see dd_stitch6 in dd_hotpath.h."""
-    b, n, c, h, w = views.shape
-    if n != 6 or c != 3:
-        raise _lib.HotpathError(f"stitch6: expected [B,6,3,H,W], got {tuple(views.shape)}")
-    _dev(views, "views")
-    wide4 = torch.empty((b, h, 6 * w, 4), device=views.device, dtype=torch.float32) if want_nhwc4 else None
-    wide = torch.empty((b, 3, h, 6 * w), device=views.device, dtype=torch.float32) if want_nchw else None
-    tgt = torch.empty((b, 3, h, w), device=views.device, dtype=torch.float32) if want_target else None
-    call("dd_stitch6", views, wide4, wide, tgt, b, h, w, int(mask_slot))
-    return wide4, wide, tgt
+    return wide_call("dd_stitch6", views, *stacked_views(views, "stitch6"), views.device, mask_slot, want_target, want_nhwc4, want_nchw)
 
 
 def stitch6_samples(samples):
     """Tuple of B per-sample [6,3,H,W] tensors (the reference's collate, helper.py:22-23) -> wide NHWC4, no stack copy."""
-    import ctypes
-    b = len(samples)
-    n, c, h, w = samples[0].shape
-    for t in samples:
-        _dev(t, "sample", (6, 3, h, w))
-    if n != 6 or c != 3:
-        raise _lib.HotpathError(f"stitch6_samples: expected samples of [6,3,H,W], got {tuple(samples[0].shape)}")
-    table = (ctypes.c_void_p * b)(*[t.data_ptr() for t in samples])
-    wide4 = torch.empty((b, h, 6 * w, 4), device=samples[0].device, dtype=torch.float32)
-    call("dd_stitch6_ptrs", table, wide4, b, h, w)
-    return wide4
+    return wide_image(tuple(samples))
+
+
+def stitch6_u8(frames):
+    """frames [B,6,H,W,3] uint8 -> wide NHWC4 fp32 in [0,1] (ToTensor's /255 fused with the 6-view gather), read as ONE stacked batch."""
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 5 and frames.shape[0] > 0 and frames.shape[1] == 6 and frames.shape[4] == 3
+            and frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()):
+        raise _lib.HotpathError(f"stitch6_u8: expected contiguous uint8 [B,6,H,W,3] on the GPU, got {tuple(frames.shape)} {frames.dtype}")
+    return wide_call("dd_stitch6_u8", frames, frames.shape[0], frames.shape[2], frames.shape[3], frames.device)[0]
+
+
+def stitch6_u8_samples(sample, mask_slot=-1, want_target=False):
+    """uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3]) -> wide NHWC4 fp32 in [0,1] (ToTensor's /255, data_helper.py:63-68, fused
+    with the 6-view gather), optionally with BasicAE's masked-view task (-> (wide4, target [B,3,H,W]))."""
+    table, b, h, w, dev, _keep = u8_table(sample, "stitch6_u8_samples")
+    wide4, _, tgt = wide_call("dd_stitch6_u8_ptrs", table, b, h, w, dev, mask_slot, want_target)
+    return (wide4, tgt) if want_target else wide4
+
+
+def wide_image(sample, precision="fp32", mask_slot=-1, want_target=False):
+    """Whatever the data pipeline hands over -> the wide NHWC4 image the conv stack reads (view order [0,1,2,5,4,3],
+    roadmap_bce_v2.py:53-64), fp32 or bf16, in ONE pass:
+      * fp32 [B,6,3,H,W] (autoencoder.py:53-57) or the collate's tuple of B fp32 [6,3,H,W] tensors (helper.py:22-23);
+      * uint8 [B,6,H,W,3] or a tuple of B uint8 [6,H,W,3] decoded frames: ToTensor's /255 (data_helper.py:63-68) fused in.
+    ``mask_slot`` / ``want_target``: the masked-view task of BasicAE.six_to_one_task -> (wide4, target); the target is the fp32 view
+    [B,3,H,W] in both precisions (bit for bit the same), the wide image fp32 or bf16."""
+    if precision not in ("fp32", "bf16"):
+        raise _lib.HotpathError(f"wide_image: precision {precision!r} is neither 'fp32' nor 'bf16'")
+    slot = mask_arg(mask_slot, "wide_image")
+    form, src, b, h, w, dev, keep = camera_source(sample, "wide_image")
+    entry = WIDE_ENTRIES[precision, form][slot >= 0 or want_target]
+    if entry is None:
+        entry, src = "dd_stitch6", torch.stack(keep, dim=0)
+    wide4, _, tgt = wide_call(entry, src, b, h, w, dev, slot, want_target)
+    return (wide4, tgt) if want_target else wide4
 
 
 def boxes_to_binary_map(box_sets, device=None):
@@ -80,77 +194,6 @@ def boxes_to_binary_map(box_sets, device=None):
     maps = torch.empty((b, 800, 800), device=device, dtype=torch.float32)
     call("dd_boxes_to_binary_map", flat if flat.numel() else None, 0 if dtype == torch.float64 else 1, offsets, maps, b)
     return maps
-
-
-def stitch6_u8(frames):
-    """frames [B,6,H,W,3] uint8 -> wide NHWC4 fp32 in [0,1] (ToTensor's /255 fused with the 6-view gather)."""
-    b, n, h, w, c = frames.shape
-    if n != 6 or c != 3 or frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous():
-        raise _lib.HotpathError(f"stitch6_u8: expected contiguous uint8 [B,6,H,W,3] on the GPU, got {tuple(frames.shape)} {frames.dtype}")
-    out = torch.empty((b, h, 6 * w, 4), device=frames.device, dtype=torch.float32)
-    call("dd_stitch6_u8", frames, out, b, h, w)
-    return out
-
-
-def is_u8_frames(sample):
-    """uint8 camera frames as a decoder emits them: a [B,6,H,W,3] tensor or the collate's tuple / list of B [6,H,W,3] tensors."""
-    if isinstance(sample, torch.Tensor):
-        return sample.dtype == torch.uint8 and sample.dim() == 5
-    return isinstance(sample, (tuple, list)) and len(sample) > 0 and all(
-        isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 4 for t in sample)
-
-
-def u8_table(sample, who):
-    """-> (ctypes pointer table, B, H, W, device, keepalive) for uint8 frames, validated on the host (a faulting kernel can reset
-    the GPU).  A [B,6,H,W,3] tensor is a table of its B slices: one code path for both forms."""
-    import ctypes
-    items = [sample[i] for i in range(sample.shape[0])] if isinstance(sample, torch.Tensor) else list(sample)
-    if not items:
-        raise _lib.HotpathError(f"{who}: empty batch")
-    n, h, w, c = items[0].shape
-    if n != 6 or c != 3:
-        raise _lib.HotpathError(f"{who}: expected uint8 frames of [6,H,W,3] per sample, got {tuple(items[0].shape)}")
-    keep = []
-    for t in items:
-        if not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (6, h, w, 3)):
-            raise _lib.HotpathError(f"{who}: expected uint8 [6,{h},{w},3] frames on the GPU, got {tuple(t.shape)} {t.dtype} on {t.device}")
-        keep.append(t if t.is_contiguous() else t.contiguous())
-    table = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-    return table, len(keep), h, w, keep[0].device, keep
-
-
-def stitch6_u8_samples(sample, mask_slot=-1, want_target=False):
-    """uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3]) -> wide NHWC4 fp32 in [0,1] (ToTensor's /255, data_helper.py:63-68, fused
-    with the 6-view gather), optionally with BasicAE's masked-view task (-> (wide4, target [B,3,H,W]))."""
-    table, b, h, w, dev, _keep = u8_table(sample, "stitch6_u8_samples")
-    wide4 = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.float32)
-    tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
-    call("dd_stitch6_u8_ptrs", table, wide4, tgt, b, h, w, int(mask_slot))
-    return (wide4, tgt) if want_target else wide4
-
-
-def wide_image(sample, precision="fp32", mask_slot=-1, want_target=False):
-    """Whatever the data pipeline hands over -> the wide NHWC4 image the conv stack reads (view order [0,1,2,5,4,3],
-    roadmap_bce_v2.py:53-64), fp32 or bf16, in ONE pass:
-      * fp32 [B,6,3,H,W] (autoencoder.py:53-57) or the collate's tuple of B fp32 [6,3,H,W] tensors (helper.py:22-23);
-      * uint8 [B,6,H,W,3] or a tuple of B uint8 [6,H,W,3] decoded frames: ToTensor's /255 (data_helper.py:63-68) fused in.
-    ``mask_slot`` / ``want_target``: the masked-view task of BasicAE.six_to_one_task -> (wide4, target); the target is the fp32 view
-    [B,3,H,W] in both precisions (bit for bit the same), the wide image fp32 or bf16."""
-    per_sample = isinstance(sample, (tuple, list))
-    if precision == "bf16":
-        from . import ops_bf16
-        if mask_slot >= 0 or want_target:
-            return ops_bf16.stitch6_bf16_masked(sample, mask_slot, want_target)
-        if is_u8_frames(sample):
-            return ops_bf16.stitch6_bf16_u8(sample)
-        return ops_bf16.stitch6_bf16_samples([t.contiguous() for t in sample]) if per_sample else ops_bf16.stitch6_bf16(sample.contiguous())
-    if is_u8_frames(sample):
-        return stitch6_u8_samples(sample, mask_slot, want_target)
-    if per_sample and mask_slot < 0 and not want_target:
-        return stitch6_samples([t.contiguous() for t in sample])      # gather straight from the samples: no stack copy
-    x = torch.stack(tuple(sample), dim=0) if per_sample else sample
-    wide4, _, tgt = stitch6(x.contiguous(), mask_slot=mask_slot, want_target=want_target)
-    return (wide4, tgt) if want_target else wide4
 
 
 def threat_score(a, b, round_b=False):

@@ -3,8 +3,6 @@
 Activations / activation gradients: NHWC ``torch.bfloat16`` tensors (the ABI sees their raw uint16 storage);
 weights, biases and their gradients: fp32.  Rounding happens exactly once, in the kernel that writes a tensor.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib, ops
@@ -18,36 +16,19 @@ def _bf(t, name, shape=None):
 
 def stitch6_bf16(views):
     """[B,6,3,H,W] fp32 -> wide NHWC4 bf16 [B,H,6W,4] (view order [0,1,2,5,4,3], channel 3 zero)."""
-    b, n, c, h, w = views.shape
-    if n != 6 or c != 3:
-        raise _lib.HotpathError(f"stitch6_bf16: expected [B,6,3,H,W], got {tuple(views.shape)}")
-    ops._dev(views, "views")
-    out = torch.empty((b, h, 6 * w, 4), device=views.device, dtype=torch.bfloat16)
-    call("dd_stitch6_bf16", views, out, b, h, w)
-    return out
+    return ops.wide_call("dd_stitch6_bf16", views, *ops.stacked_views(views, "stitch6_bf16"), views.device)[0]
 
 
 def stitch6_bf16_samples(samples):
     """Tuple of B per-sample [6,3,H,W] fp32 tensors (the reference's collate, helper.py:22-23) -> wide NHWC4 bf16, no stack copy."""
-    b = len(samples)
-    n, c, h, w = samples[0].shape
-    if n != 6 or c != 3:
-        raise _lib.HotpathError(f"stitch6_bf16_samples: expected samples of [6,3,H,W], got {tuple(samples[0].shape)}")
-    for t in samples:
-        ops._dev(t, "sample", (6, 3, h, w))
-    table = (C.c_void_p * b)(*[t.data_ptr() for t in samples])
-    out = torch.empty((b, h, 6 * w, 4), device=samples[0].device, dtype=torch.bfloat16)
-    call("dd_stitch6_bf16_ptrs", table, out, b, h, w)
-    return out
+    return ops.wide_image(tuple(samples), "bf16")
 
 
 def stitch6_bf16_u8(sample):
     """uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3]) -> wide NHWC4 bf16: /255 (true division) and the bf16 rounding fused with
     the gather -- the values ``stitch6_bf16(frames.permute(..).float() / 255)`` gives."""
     table, b, h, w, dev, _keep = ops.u8_table(sample, "stitch6_bf16_u8")
-    out = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.bfloat16)
-    call("dd_stitch6_bf16_u8_ptrs", table, out, b, h, w)
-    return out
+    return ops.wide_call("dd_stitch6_bf16_u8_ptrs", table, b, h, w, dev)[0]
 
 
 def to_bf16(t):
@@ -202,48 +183,14 @@ def encoder_conv_stack(x4, c1, c2, c3, pool=True):
 
 
 # ------------------------------------------------------------------------------------------------ BasicAE pre-training in bf16
-def _masked_out(b, h, w, dev, want_target):
-    out = torch.empty((b, h, 6 * w, 4), device=dev, dtype=torch.bfloat16)
-    tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
-    return out, tgt
-
-
-def _mask_arg(mask_slot):
-    if not -1 <= int(mask_slot) <= 5:
-        raise _lib.HotpathError(f"stitch6_bf16: mask_slot {mask_slot} outside [-1, 5]")
-    return int(mask_slot)
-
-
 def stitch6_bf16_masked(sample, mask_slot=-1, want_target=False):
     """The masked-view task of BasicAE (autoencoder.py:59-73) on the bf16 image, in one pass: wide NHWC4 bf16 with wide slot
     ``mask_slot`` blanked and, with ``want_target``, that view as fp32 [B,3,H,W] (the fp32 path's target bit for bit).  ``sample``:
-    fp32 [B,6,3,H,W], the collate's tuple of fp32 [6,3,H,W], or uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3])."""
-    slot = _mask_arg(mask_slot)
-    if ops.is_u8_frames(sample):
-        table, b, h, w, dev, _keep = ops.u8_table(sample, "stitch6_bf16_u8_masked")
-        out, tgt = _masked_out(b, h, w, dev, want_target)
-        call("dd_stitch6_bf16_u8_ptrs_masked", table, out, tgt, b, h, w, slot)
-    elif isinstance(sample, (tuple, list)):
-        samples = [t.contiguous() for t in sample]
-        if not samples:
-            raise _lib.HotpathError("stitch6_bf16_masked: empty batch")
-        n, c, h, w = samples[0].shape
-        if n != 6 or c != 3:
-            raise _lib.HotpathError(f"stitch6_bf16_masked: expected samples of [6,3,H,W], got {tuple(samples[0].shape)}")
-        for t in samples:
-            ops._dev(t, "sample", (6, 3, h, w))
-        b = len(samples)
-        table = (C.c_void_p * b)(*[t.data_ptr() for t in samples])
-        out, tgt = _masked_out(b, h, w, samples[0].device, want_target)
-        call("dd_stitch6_bf16_ptrs_masked", table, out, tgt, b, h, w, slot)
-    else:
-        if sample.dim() != 5 or sample.shape[1] != 6 or sample.shape[2] != 3:
-            raise _lib.HotpathError(f"stitch6_bf16_masked: expected [B,6,3,H,W], got {tuple(sample.shape)}")
-        views = sample.contiguous()
-        ops._dev(views, "views")
-        b, _, _, h, w = views.shape
-        out, tgt = _masked_out(b, h, w, views.device, want_target)
-        call("dd_stitch6_bf16_masked", views, out, tgt, b, h, w, slot)
+    fp32 [B,6,3,H,W], the collate's tuple of fp32 [6,3,H,W], or uint8 frames ([B,6,H,W,3] or a tuple of [6,H,W,3]).  Always the
+    ``_masked`` entry point of the form, also for ``mask_slot`` -1."""
+    slot = ops.mask_arg(mask_slot, "stitch6_bf16_masked")
+    form, src, b, h, w, dev, _keep = ops.camera_source(sample, "stitch6_bf16_masked")
+    out, _, tgt = ops.wide_call(ops.WIDE_ENTRIES["bf16", form][1], src, b, h, w, dev, slot, want_target)
     return (out, tgt) if want_target else out
 
 

@@ -140,7 +140,8 @@ SIZES = [(5, 7), (16, 22)]                               # widths that are not m
 @pytest.mark.parametrize("h,w", SIZES)
 @pytest.mark.parametrize("batch", BATCHES)
 def test_fp32_sample_gathers(dev, batch, h, w):
-    """dd_stitch6_ptrs, dd_stitch6_bf16_ptrs (+ _masked), dd_view_to_nhwc4_ptrs."""
+    """dd_stitch6_ptrs, dd_stitch6_bf16_ptrs (+ _masked), dd_view_to_nhwc4_ptrs; and the same samples stacked through dd_stitch6 with its
+    NHWC4, NCHW and target outputs together."""
     from driving_dirty_amd.ops import _p
     views = synth.camera_batch(batch, h, w, seed=batch + h)
     assert distinct(views)
@@ -171,13 +172,24 @@ def test_fp32_sample_gathers(dev, batch, h, w):
         call("dd_view_to_nhwc4_ptrs", tab, _p(buf), batch, h, w, view, tf)
         assert torch.equal(take(buf, tuple(want.shape)), want), (view, tf)
 
+    # the same samples as ONE stacked batch: dd_stitch6 with all three outputs at once -- NHWC4, NCHW and the masked view's target
+    stacked = views.to(dev)
+    m4, target = masked_ref(views, 4)
+    nchw = wide_ref(views)[1].clone()
+    nchw[..., 4 * w:5 * w] = 0.0
+    buf, buf_nchw, tgt = guarded(n, dev), guarded(batch * 3 * h * 6 * w, dev), guarded(batch * 3 * h * w, dev)
+    call("dd_stitch6", _p(stacked), _p(buf), _p(buf_nchw), _p(tgt), batch, h, w, 4)
+    assert torch.equal(take(buf, shape), m4)
+    assert torch.equal(take(buf_nchw, (batch, 3, h, 6 * w)), nchw)
+    assert torch.equal(take(tgt, (batch, 3, h, w)), target)
+
 
 # ------------------------------------------------------------------------------------------------ 1b. uint8 frames
 @pytest.mark.parametrize("h,w", SIZES)
 @pytest.mark.parametrize("batch", BATCHES)
 def test_uint8_frame_gathers(dev, batch, h, w):
-    """dd_stitch6_u8_ptrs (target non-null, mask_slot -1 and 2), dd_stitch6_bf16_u8_ptrs (+ _masked), dd_view_to_nhwc4_u8_ptrs; the
-    reference is ToTensor's frames.float().div(255) on the CPU and torch indexing."""
+    """dd_stitch6_u8_ptrs (target non-null, mask_slot -1 and 2), dd_stitch6_bf16_u8_ptrs (+ _masked), dd_view_to_nhwc4_u8_ptrs, and the
+    same frames stacked through dd_stitch6_u8; the reference is ToTensor's frames.float().div(255) on the CPU and torch indexing."""
     from driving_dirty_amd.ops import _p
     frames = torch.randint(0, 256, (batch, 6, h, w, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(batch * 100 + w))
     assert distinct(frames)
@@ -213,6 +225,11 @@ def test_uint8_frame_gathers(dev, batch, h, w):
         buf = guarded(want.numel(), dev)
         call("dd_view_to_nhwc4_u8_ptrs", tab, _p(buf), batch, h, w, view, tf)
         assert torch.equal(take(buf, tuple(want.shape)), want), (view, tf)
+
+    # the same frames as ONE stacked batch (dd_stitch6_u8): the same division, bit for bit
+    buf = guarded(n, dev)
+    call("dd_stitch6_u8", _p(frames.to(dev)), _p(buf), batch, h, w)
+    assert torch.equal(take(buf, shape), ref4)
 
 
 # ------------------------------------------------------------------------------------------------ 1c. road-mask taps

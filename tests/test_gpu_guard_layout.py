@@ -1,5 +1,5 @@
-"""Guard-band cases (tests/_guard.py) for the layout, gather, pooling, copy and BatchNorm2d entry points: csrc/layout_pool.hip (the
-stacked-batch 6-view gathers, dd_view_to_nhwc4 and dd_subsample_nhwc4 included), dd_pool4_bn_fwd / _bwd of csrc/bn2d.hip, the helpers
+"""Guard-band cases (tests/_guard.py) for the layout, gather, pooling, copy and BatchNorm2d entry points: csrc/layout_pool.hip and the
+stacked-batch gathers of csrc/camera_gather.hip (dd_stitch6*, dd_view_to_nhwc4; dd_subsample_nhwc4 included), dd_pool4_bn_fwd / _bwd of csrc/bn2d.hip, the helpers
 of csrc/conv3x3.hip (sign words, padded ReLU backward), csrc/gconv.hip's channel copies and sums, the fp32 <-> bf16 converters of
 csrc/conv3x3_bf16.hip and csrc/bn2d.hip's stand-alone kernels.  What a case asserts: tests/test_gpu_guard_dense.py.
 
@@ -23,9 +23,9 @@ f32, f64, i32, i16, bf16 = torch.float32, torch.float64, torch.int32, torch.int1
 
 # Launchers of these files that pick a kernel by the alignment of an operand:
 ALIGNMENT_PICKS = {
-    "dd_channel_sum": "csrc/gconv.hip:1090  cstore % 4 == 0 && cstore <= 256 && buf % 16 == 0 -> channel_sum_stream, else channel_sum_partial",
-    "dd_pool4_fwd_idx": "csrc/layout_pool.hip:663  c == 32 && feat % 16 == 0 && idx % 4 == 0 -> pool4_fwd_tile32, else pool4_fwd_quad<true>",
-    "dd_pool4_idx_relu_bwd": "csrc/layout_pool.hip:679  c == 32 && dfeat % 16 == 0 && idx % 4 == 0 -> pool4_bwd_tile32, else pool4_bwd_idx_quad",
+    "dd_channel_sum": "csrc/gconv.hip:1029  cstore % 4 == 0 && cstore <= 256 && buf % 16 == 0 -> channel_sum_stream, else channel_sum_partial",
+    "dd_pool4_fwd_idx": "csrc/layout_pool.hip:500  c == 32 && feat % 16 == 0 && idx % 4 == 0 -> pool4_fwd_tile32, else pool4_fwd_quad<true>",
+    "dd_pool4_idx_relu_bwd": "csrc/layout_pool.hip:516  c == 32 && dfeat % 16 == 0 && idx % 4 == 0 -> pool4_bwd_tile32, else pool4_bwd_idx_quad",
 }
 # The two pool kernels' other side still reads feat / writes dfeat as 16-byte vectors, so only idx (uint16 codes) may be less
 # aligned: the crossing cases put idx on 2 bytes.  Both sides route the same values, so these cases keep the bit-for-bit comparison
@@ -222,7 +222,7 @@ def _pool4_idx(b, c, h, w, cross):
         pooled = arena.out(tuple(ref.shape), f32, 16, "pooled")
         idx = arena.out((n,), i16, 2 if (cross and mode == "minimal") else 16, "idx")
         if cross:
-            assert c == 32 and (idx.data_ptr() % 4 == 0) == (mode == "natural"), "one mode per kernel of csrc/layout_pool.hip:663 / :679"
+            assert c == 32 and (idx.data_ptr() % 4 == 0) == (mode == "natural"), "one mode per kernel of csrc/layout_pool.hip:500 / :516"
         call("dd_pool4_fwd_idx", feat, pooled, idx, b, h, w, c)
         gp = arena.put(gp0, 16, "dpooled")
         dfeat = arena.out((b, h, w, c), f32, 16, "dfeat")
@@ -308,7 +308,7 @@ def _channel_sum(shape, coff, chans, accumulate):
         crosses = cstore % 4 == 0 and cstore <= 256
         buf = arena.put(b0, 4 if mode == "minimal" else 16, "buf")      # the header: any alignment a float can have
         if crosses:
-            assert (buf.data_ptr() % 16 == 0) == (mode == "natural"), "one mode per kernel of csrc/gconv.hip:1090"
+            assert (buf.data_ptr() % 16 == 0) == (mode == "natural"), "one mode per kernel of csrc/gconv.hip:1029"
         o0 = hu((chans,), "chso")
         out = arena.inout(o0, 16, "out") if accumulate else arena.out((chans,), f32, 16, "out")
         ws = arena.workspace(size("dd_channel_sum_workspace_bytes"), 16)

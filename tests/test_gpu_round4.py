@@ -452,6 +452,70 @@ def test_box_and_joint_steps_on_uint8_frames_equal_the_fp32_steps(dev, cls):
     _same(out["fp32"][1], out["u8"][1])
 
 
+# what ops.wide_image enters by (precision, input form): (without, with a masked view); fp32 samples with a masked view are stacked
+_FRONT_DOOR = {("fp32", "views"): ("dd_stitch6", "dd_stitch6"),
+               ("fp32", "samples"): ("dd_stitch6_ptrs", "dd_stitch6"),
+               ("fp32", "frames"): ("dd_stitch6_u8_ptrs", "dd_stitch6_u8_ptrs"),
+               ("bf16", "views"): ("dd_stitch6_bf16", "dd_stitch6_bf16_masked"),
+               ("bf16", "samples"): ("dd_stitch6_bf16_ptrs", "dd_stitch6_bf16_ptrs_masked"),
+               ("bf16", "frames"): ("dd_stitch6_bf16_u8_ptrs", "dd_stitch6_bf16_u8_ptrs_masked")}
+_FRONT_DOOR_MASKED = {"dd_stitch6", "dd_stitch6_u8_ptrs", "dd_stitch6_bf16_masked", "dd_stitch6_bf16_ptrs_masked", "dd_stitch6_bf16_u8_ptrs_masked"}
+
+
+def test_wide_image_front_door(dev, monkeypatch):
+    """ops.wide_image at B = 3, H = 5, W = 7 over the four input forms, both precisions, mask_slot -1 and 2 with and without the target:
+    it enters the one entry point of _FRONT_DOOR and returns bit for bit what that entry point gives when called directly.  A wrong
+    mask_slot, an empty tuple and a tuple with one sample of another shape or dtype raise HotpathError before ANY entry point is
+    entered: every function of the library object is wrapped by a counter, the way tools/record_abi_call_trace.py's Recorder wraps
+    them."""
+    import ctypes as C
+    from driving_dirty_amd import _lib, ops
+    from driving_dirty_amd.ops import _p, _stream
+    b, h, w = 3, 5, 7
+    frames = _frames(b, h, w, 11).to(dev)
+    views = _as_views(frames)
+    inputs = {"views": ("views", views), "samples": ("samples", tuple(views)), "stacked frames": ("frames", frames),
+              "frame samples": ("frames", tuple(frames))}
+    entered, lib = [], _lib.lib()
+    for symbol in _lib.SIGNATURES:
+        monkeypatch.setattr(lib, symbol, lambda *a, _inner=getattr(lib, symbol), _symbol=symbol: entered.append(_symbol) or _inner(*a))
+
+    def direct(name, form, dtype, slot, want_target):
+        tab = lambda ts: (C.c_void_p * b)(*[t.data_ptr() for t in ts])
+        src = _p(views) if form == "views" or name == "dd_stitch6" else tab(views) if form == "samples" else tab(frames)
+        out = torch.empty((b, h, 6 * w, 4), device=dev, dtype=dtype)
+        tgt = torch.empty((b, 3, h, w), device=dev, dtype=torch.float32) if want_target else None
+        masked = name in _FRONT_DOOR_MASKED
+        args = [src, _p(out)] + ([None] if name == "dd_stitch6" else []) + ([_p(tgt)] if masked else []) + [b, h, w] + ([slot] if masked else [])
+        _lib.check(getattr(lib, name)(*args, _stream()), name)
+        return out, tgt
+
+    for precision, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        for what, (form, sample) in inputs.items():
+            for slot in (-1, 2):
+                for want_target in (False, True):
+                    name = _FRONT_DOOR[precision, form][slot >= 0 or want_target]
+                    case = (precision, what, slot, want_target)
+                    del entered[:]
+                    got = ops.wide_image(sample, precision, mask_slot=slot, want_target=want_target)
+                    assert entered == [name], case
+                    want, want_tgt = direct(name, form, dtype, slot, want_target)
+                    wide = got[0] if want_target else got
+                    assert wide.dtype == dtype and torch.equal(wide.view(torch.int16), want.view(torch.int16)), case
+                    if want_target:
+                        assert isinstance(got, tuple) and tuple(got[1].shape) == (b, 3, h, w) and got[1].dtype == torch.float32, case
+                        if slot >= 0:      # with mask_slot -1 nothing writes the target
+                            assert torch.equal(got[1], want_tgt) and torch.equal(got[1], views[:, (0, 1, 2, 5, 4, 3)[slot]]), case
+    del entered[:]
+    refused = [(sample, 6) for _, sample in inputs.values()] + [(bad, slot) for slot in (-1, 2) for bad in (
+        (), (views[0], views[1][..., :6]), (frames[0], frames[1][:, :4]), (views[0], frames[1]), (frames[0], views[1]))]
+    for precision in ("fp32", "bf16"):
+        for sample, slot in refused:
+            with pytest.raises(_lib.HotpathError):
+                ops.wide_image(sample, precision, mask_slot=slot, want_target=slot >= 0)
+    assert entered == []
+
+
 def test_uint8_wide_images_are_bit_identical_to_totensor(dev):
     """The three uint8 entry points against torch on frames / 255 (a true division, as ToTensor's): fp32 wide image, bf16 wide image,
     every (view, transform) SpatialMappingCNN uses -- ragged size, B > 64 (two launches of the pointer table)."""
