@@ -155,8 +155,7 @@ int rankb_launch(float* p, float* m, float* v, const float* dy, const float* x, 
              "adam_rankb: bias, its exp_avg and exp_avg_sq come together or not at all");
   DD_REQUIRE((int64_t)(rows + 4) * n < ((int64_t)1 << 29) && (int64_t)(rows + 4) * k < ((int64_t)1 << 29) && (int64_t)16 * k < ((int64_t)1 << 29),
              DD_ERR_UNSUPPORTED, "adam_rankb: factors of 2 GB or more");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const AdamBias bc = adam_bias(beta1, beta2, step);
   RankbArgs a;
   a.p = p; a.m = m; a.v = v; a.dy = dy; a.x = x; a.bp = bias_p; a.bm = bias_m; a.bv = bias_v;
   a.M = rows; a.N = n; a.K = k;
@@ -164,8 +163,8 @@ int rankb_launch(float* p, float* m, float* v, const float* dy, const float* x, 
   a.ntile_k = (k + 63) / 64;
   a.b1 = beta1; a.b2 = beta2; a.eps = eps;
   a.omb1 = 1.f - beta1; a.omb2 = 1.f - beta2;
-  a.step_size = lr / (float)bc1;
-  a.bc2_sqrt = (float)sqrt(bc2);
+  a.step_size = lr / bc.bc1;
+  a.bc2_sqrt = bc.bc2_sqrt;
   a.inv_bc2 = 1.f / a.bc2_sqrt;
   a.gscale = grad_scale;
   const bool short_rows = rows <= 32 && a.ntile_k == 1;      // adam_rankb_short_kernel: its work list is of n-groups
@@ -174,7 +173,7 @@ int rankb_launch(float* p, float* m, float* v, const float* dy, const float* x, 
   const long total = wide ? (long)a.ntile_n * ((k + 255) / 256) : (long)((a.ntile_n + 3) / 4) * (short_rows ? 1 : a.ntile_k);
   DD_REQUIRE(total < ((long)1 << 31), DD_ERR_UNSUPPORTED, "adam_rankb: too many tiles");
   a.total = (int)total;
-  // one persistent workgroup per CU, as dd_adam_step (dense.hip): nothing of this launch is ever queued ahead of a conv kernel
+  // one persistent workgroup per CU, as dd_adam_step (adam_stream_grid, dd_adam.h): nothing of this launch is ever queued ahead of a conv kernel
   const int per_cu = dd_adam_blocks_internal();
   const int grid = (int)min(total, (long)max(DD_NUM_CU - dd_adam_spare_internal(), 1) * per_cu);
   a.per = (int)((total + grid - 1) / grid);

@@ -2180,7 +2180,7 @@ int launch_wino2(const float* x, const float* up, const float* bias, const unsig
   constexpr int WPB = 4;
   const int nstrips = (d->width + 31) / 32;
   // Register-row kernels by default.  DD_WINO2_RING=1: the LDS-ring form everywhere, DD_WINO2_RING_W1=1: for the fused data
-  // gradient only (A/B; DESIGN.md 3.1c: beside the optimizer pass the choice depends on how that pass is launched -- csrc/dense.hip).
+  // gradient only (A/B; DESIGN.md 3.1c: beside the optimizer pass the choice depends on how that pass is launched -- adam_stream_grid, csrc/dd_adam.h).
   static const bool ring_env = getenv("DD_WINO2_RING") != nullptr;
   static const bool ring_w1 = getenv("DD_WINO2_RING_W1") != nullptr;
   const bool ring = ring_env || (EPI == EPI_RELU_BITS_W1 && ring_w1);

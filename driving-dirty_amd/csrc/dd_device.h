@@ -86,6 +86,15 @@ __device__ __forceinline__ void dd_range(long total, int i, int n, long& idx, lo
   if (idx > end) idx = end;
 }
 
+// The entry t of a launch table that this workgroup works on: first[t] <= blockIdx.x < first[t + 1], where first[] holds the running
+// sum of the entries' workgroup counts (the multi-tensor launches: dd_adam.h, gradnorm.hip).  A linear walk: a table has 48 entries.
+template <int N>
+__device__ __forceinline__ int dd_table_entry(const int (&first)[N], int count) {
+  int t = 0;
+  while (t + 1 < count && (int)blockIdx.x >= first[t + 1]) ++t;
+  return t;
+}
+
 // bf16 <-> fp32.  Every kernel rounds through dd_pack_bf16 (v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN), which is
 // what the bf16 contract of the oracle assumes.
 __device__ __forceinline__ unsigned dd_pack_bf16(float lo, float hi) {      // two bf16 in one word, `lo` in the low half

@@ -1,13 +1,13 @@
-// Dense-head pieces of the hot path (all HBM- or latency-bound, no matrix work):
-//   dd_bn_relu_drop_*   BatchNorm1d -> ReLU -> dropout(mask)   reference components.py:104-109 (DenseBlock.forward)
-//   dd_bce_logits       mean BCE-with-logits fwd + bwd + sigmoid in ONE pass over the 640000-wide maps
-//                       (roadmap_bce_v2.py:81,106)
-//   dd_mse              mean squared error fwd + bwd (autoencoder.py:91, roadmap_pretrain_ae.py:100)
-//   dd_adam_step        torch.optim.Adam over one flat buffer (autoencoder.py:119-120)
+// Dense-head pieces of the hot path (all HBM- or latency-bound, no matrix work; the optimizer is adam.hip):
+//   dd_bn_relu_drop_*           BatchNorm1d -> ReLU -> dropout(mask)   reference components.py:104-109 (DenseBlock.forward)
+//   dd_bce_logits               mean BCE-with-logits fwd + bwd + sigmoid in ONE pass over the 640000-wide maps
+//                               (roadmap_bce_v2.py:81,106)
+//   dd_mse                      mean squared error fwd + bwd (autoencoder.py:91, roadmap_pretrain_ae.py:100)
+//   dd_scale_by_device_scalar   a buffer times one fp32 read from device memory
+//   dd_sigmoid, dd_threat_score the probabilities of a map of logits; the threat score of two maps
 #include <stdlib.h>
 
 #include "dd_common.h"
-#include "dd_adam.h"
 
 namespace {
 
@@ -454,173 +454,7 @@ __global__ __launch_bounds__(64) void threat_final_kernel(const double* __restri
   if (k == 0) out[0] = (float)(tp / (sa + sb - tp));
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                   float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                   float gscale) {
-  const long n4 = n / 4;
-  const float step_size = lr / bc1;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    // streaming accesses: this pass runs beside the conv backward and should not push its 4.5 GB through the caches
-    f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i),
-          vv = __builtin_nontemporal_load((f32x4*)v + i);
-    const f32x4 gv = __builtin_nontemporal_load((const f32x4*)g + i);
-    const float inv_bc2 = 1.f / bc2_sqrt;
-#pragma unroll
-    for (int k = 0; k < 4; k += 2) {
-      f32x2 pe = {pv[k], pv[k + 1]}, me = {mv[k], mv[k + 1]}, ve = {vv[k], vv[k + 1]};
-      adam_elem2(pe, me, ve, f32x2{gv[k], gv[k + 1]}, gscale, b1, b2, eps, step_size, inv_bc2);
-      pv[k] = pe.x; pv[k + 1] = pe.y; mv[k] = me.x; mv[k + 1] = me.y; vv[k] = ve.x; vv[k + 1] = ve.y;
-    }
-    __builtin_nontemporal_store(pv, (f32x4*)p + i);
-    __builtin_nontemporal_store(mv, (f32x4*)m + i);
-    __builtin_nontemporal_store(vv, (f32x4*)v + i);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {
-    const long i = 4 * n4 + threadIdx.x;
-    float pe = p[i], me = m[i], ve = v[i];
-    adam_elem(pe, me, ve, g[i], gscale, b1, b2, eps, step_size, bc2_sqrt);
-    p[i] = pe; m[i] = me; v[i] = ve;
-  }
-}
-
-// dd_adam_step_dev: adam_kernel with the gradient scale read from device memory (one uniform load: what dd_clip_scale wrote earlier on
-// the stream).  The loop is written out a second time -- called from both kernels as one function, adam_kernel comes out of the compiler
-// with another schedule, and it is the kernel tuned to run beside the conv backward; the ARITHMETIC is adam_elem2 / adam_elem either
-// way, so the same scale gives the same bits.
-__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                       float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                       const float* __restrict__ gscale_dev) {
-  const float gscale = gscale_dev[0];
-  const long n4 = n / 4;
-  const float step_size = lr / bc1;
-  const float inv_bc2 = 1.f / bc2_sqrt;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i),
-          vv = __builtin_nontemporal_load((f32x4*)v + i);
-    const f32x4 gv = __builtin_nontemporal_load((const f32x4*)g + i);
-#pragma unroll
-    for (int k = 0; k < 4; k += 2) {
-      f32x2 pe = {pv[k], pv[k + 1]}, me = {mv[k], mv[k + 1]}, ve = {vv[k], vv[k + 1]};
-      adam_elem2(pe, me, ve, f32x2{gv[k], gv[k + 1]}, gscale, b1, b2, eps, step_size, inv_bc2);
-      pv[k] = pe.x; pv[k + 1] = pe.y; mv[k] = me.x; mv[k + 1] = me.y; vv[k] = ve.x; vv[k + 1] = ve.y;
-    }
-    __builtin_nontemporal_store(pv, (f32x4*)p + i);
-    __builtin_nontemporal_store(mv, (f32x4*)m + i);
-    __builtin_nontemporal_store(vv, (f32x4*)v + i);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {
-    const long i = 4 * n4 + threadIdx.x;
-    float pe = p[i], me = m[i], ve = v[i];
-    adam_elem(pe, me, ve, g[i], gscale, b1, b2, eps, step_size, bc2_sqrt);
-    p[i] = pe; m[i] = me; v[i] = ve;
-  }
-}
-
-// The small tensors of a model (biases, BatchNorm vectors, 3x3 filters) in ONE launch: sixteen 6-us launches at the very
-// end of the step are 0.1 ms nothing overlaps.  Block b works on tensor t with first[t] <= b < first[t+1].
-constexpr int ADAM_MULTI_MAX = 48;
-struct AdamTable {
-  float* p[ADAM_MULTI_MAX];
-  const float* g[ADAM_MULTI_MAX];
-  float* m[ADAM_MULTI_MAX];
-  float* v[ADAM_MULTI_MAX];
-  int n[ADAM_MULTI_MAX];
-  int first[ADAM_MULTI_MAX + 1];
-  int count;
-};
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamTable tab, float lr, float b1, float b2, float eps, float bc1,
-                                                         float bc2_sqrt, float gscale) {
-  int t = 0;
-  while (t + 1 < tab.count && (int)blockIdx.x >= tab.first[t + 1]) ++t;
-  float* __restrict__ p = tab.p[t];
-  const float* __restrict__ g = tab.g[t];
-  float* __restrict__ m = tab.m[t];
-  float* __restrict__ v = tab.v[t];
-  const int i = ((int)blockIdx.x - tab.first[t]) * 256 + threadIdx.x;
-  if (i >= tab.n[t]) return;
-  const float step_size = lr / bc1;
-  float pe = p[i], me = m[i], ve = v[i];
-  adam_elem(pe, me, ve, g[i], gscale, b1, b2, eps, step_size, bc2_sqrt);
-  p[i] = pe; m[i] = me; v[i] = ve;
-}
-
-// dd_adam_step_multi_dev: the same with the scale read from device memory (see adam_dev_kernel)
-__global__ __launch_bounds__(256) void adam_multi_dev_kernel(AdamTable tab, float lr, float b1, float b2, float eps, float bc1,
-                                                             float bc2_sqrt, const float* __restrict__ gscale_dev) {
-  int t = 0;
-  while (t + 1 < tab.count && (int)blockIdx.x >= tab.first[t + 1]) ++t;
-  float* __restrict__ p = tab.p[t];
-  const float* __restrict__ g = tab.g[t];
-  float* __restrict__ m = tab.m[t];
-  float* __restrict__ v = tab.v[t];
-  const int i = ((int)blockIdx.x - tab.first[t]) * 256 + threadIdx.x;
-  if (i >= tab.n[t]) return;
-  const float step_size = lr / bc1;
-  float pe = p[i], me = m[i], ve = v[i];
-  adam_elem(pe, me, ve, g[i], gscale_dev[0], b1, b2, eps, step_size, bc2_sqrt);
-  p[i] = pe; m[i] = me; v[i] = ve;
-}
-
 constexpr int kLossBlocks = DD_NUM_CU * 8;
-
-// dd_adam_step / dd_adam_step_dev: one host path, the scale by value or -- gscale_dev -- read by the kernel
-int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                int32_t step, float grad_scale, const float* gscale_dev, void* stream) {
-  DD_REQUIRE(p && g && m && v && n > 0 && step >= 1, DD_ERR_BAD_ARG, "adam: bad argument");
-  DD_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, DD_ERR_BAD_ARG, "adam: buffers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  // ONE persistent block per CU.  This pass usually runs BESIDE the conv backward (optim.HipAdam.overlap_with_backward), whose
-  // one-wave-per-SIMD kernels take 440-464 of a SIMD's 512 registers: one Adam wave (48) fits beside them, and -- the point --
-  // nothing of this launch is ever left QUEUED: blocks that wait for a CU are dispatched ahead of the next conv kernel when the
-  // current one ends, and a kernel of >= 456 registers then waits until they have all drained (tools/ubench/residency.hip; in the
-  // step: the c2 data gradient 2.2 ms from dispatch to end instead of 1.6).  Alone the pass is also fastest this way (0.536 ms for
-  // fc1's 481 MB = 6.3 TB/s; 4 blocks per CU: 0.586, 8: 0.595).
-  const int per_cu = dd_adam_blocks_internal();
-  const int grid = (int)min((n / 4 + 255) / 256 + 1, (long)DD_NUM_CU * per_cu);
-  if (gscale_dev)
-    hipLaunchKernelGGL(adam_dev_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2,
-                       eps, (float)bc1, (float)sqrt(bc2), gscale_dev);
-  else
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr, beta1, beta2,
-                       eps, (float)bc1, (float)sqrt(bc2), grad_scale);
-  DD_LAUNCH_CHECK("adam");
-  return 0;
-}
-
-int adam_multi_launch(const dd_adam_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, int32_t step,
-                      float grad_scale, const float* gscale_dev, void* stream) {
-  DD_REQUIRE(tensors && count > 0 && step >= 1, DD_ERR_BAD_ARG, "adam_multi: bad argument");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  for (int32_t base = 0; base < count; base += ADAM_MULTI_MAX) {
-    AdamTable tab;
-    tab.count = min(ADAM_MULTI_MAX, count - base);
-    int blocks = 0;
-    for (int i = 0; i < tab.count; ++i) {
-      const dd_adam_tensor& t = tensors[base + i];
-      DD_REQUIRE(t.p && t.g && t.m && t.v && t.n > 0 && t.n < (1 << 30), DD_ERR_BAD_ARG, "adam_multi: tensor %d: NULL pointer or bad size", base + i);
-      tab.p[i] = t.p;
-      tab.g[i] = t.g;
-      tab.m[i] = t.m;
-      tab.v[i] = t.v;
-      tab.n[i] = (int)t.n;
-      tab.first[i] = blocks;
-      blocks += (int)((t.n + 255) / 256);
-    }
-    tab.first[tab.count] = blocks;
-    if (gscale_dev)
-      hipLaunchKernelGGL(adam_multi_dev_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tab, lr, beta1, beta2, eps, (float)bc1,
-                         (float)sqrt(bc2), gscale_dev);
-    else
-      hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, tab, lr, beta1, beta2, eps, (float)bc1,
-                         (float)sqrt(bc2), grad_scale);
-    DD_LAUNCH_CHECK("adam_multi");
-  }
-  return 0;
-}
 
 }  // namespace
 
@@ -793,28 +627,6 @@ int dd_threat_score(const float* a, const float* b, float* out, int64_t n, int32
   hipLaunchKernelGGL(threat_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, grid, out);
   DD_LAUNCH_CHECK("threat_score final");
   return 0;
-}
-
-int dd_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                 int32_t step, float grad_scale, void* stream) {
-  return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, nullptr, stream);
-}
-
-int dd_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
-                     int32_t step, const float* grad_scale_dev, void* stream) {
-  DD_REQUIRE(grad_scale_dev && (uintptr_t)grad_scale_dev % 4 == 0, DD_ERR_BAD_ARG, "adam_dev: bad argument");
-  return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, 0.f, grad_scale_dev, stream);
-}
-
-int dd_adam_step_multi(const dd_adam_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, int32_t step,
-                       float grad_scale, void* stream) {
-  return adam_multi_launch(tensors, count, lr, beta1, beta2, eps, step, grad_scale, nullptr, stream);
-}
-
-int dd_adam_step_multi_dev(const dd_adam_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, int32_t step,
-                           const float* grad_scale_dev, void* stream) {
-  DD_REQUIRE(grad_scale_dev && (uintptr_t)grad_scale_dev % 4 == 0, DD_ERR_BAD_ARG, "adam_multi_dev: bad argument");
-  return adam_multi_launch(tensors, count, lr, beta1, beta2, eps, step, 0.f, grad_scale_dev, stream);
 }
 
 }  // extern "C"

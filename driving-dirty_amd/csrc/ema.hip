@@ -2,7 +2,7 @@
 //   dd_ema_update_ptrs   e' = fmaf(alpha, w - e, e) over a table of (average, parameter) tensors
 //   dd_ema_swap_ptrs     a <-> b as 32-bit words over a table of tensor pairs
 // Pure streaming, ONE kernel family for the whole table: the table (a slice of at most kTableMax tensors) travels in the kernel
-// arguments with a prefix `first[]` of piece counts, the way dense.hip passes ADAM_MULTI_MAX quadruples.  The work is the flat list of
+// arguments with a prefix `first[]` of piece counts, the way dd_adam.h passes ADAM_TABLE_MAX quadruples.  The work is the flat list of
 // kChunk-element pieces of all tensors of the slice; workgroup b takes pieces b, b + grid, ... of a grid capped at 8 workgroups per
 // CU.  The piece index depends on the workgroup alone, so the table is read with scalar loads from the kernel arguments and the
 // search for a piece's tensor costs no vector work: a binary search for the first piece, then a step forward only when a piece
@@ -10,7 +10,7 @@
 // A piece inside a tensor's whole 16-byte vectors is four 16-byte loads per lane from each buffer, all issued before the first use,
 // and four 16-byte stores; a tensor's last piece guards each vector and ends with the scalar tail of its n % 4 elements.  Both
 // paths compute an element by the one function `ema_elem`.  No LDS, no atomics.
-// Loads and stores are the non-temporal form, as dd_adam_step's (dense.hip): every byte is touched once per call, a plain or a
+// Loads and stores are the non-temporal form, as dd_adam_step's (dd_adam.h): every byte is touched once per call, a plain or a
 // non-temporal store both leave the XCD's L2 at the same rate (neither is a write-through), and nothing reads e' again before the
 // next step's 1.3 GB have gone through the caches.
 #include <algorithm>

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __rest
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
-// The small tensors of a model in one launch, as adam_multi_kernel (dense.hip): block b works on tensor t with first[t] <= b < first[t+1].
+// The small tensors of a model in one launch, as adam_multi_kernel (dd_adam.h): block b works on tensor t with first[t] <= b < first[t+1].
 constexpr int SQ_MULTI_MAX = 48;
 struct SqTable {
   const float* g[SQ_MULTI_MAX];
@@ -61,8 +61,7 @@ struct SqTable {
 };
 __global__ __launch_bounds__(256) void sqnorm_multi_kernel(SqTable tab, double* __restrict__ partial) {
   __shared__ double red[256];
-  int t = 0;
-  while (t + 1 < tab.count && (int)blockIdx.x >= tab.first[t + 1]) ++t;
+  const int t = dd_table_entry(tab.first, tab.count);
   const float* __restrict__ g = tab.g[t];
   const int base = ((int)blockIdx.x - tab.first[t]) * kMultiPerBlock + threadIdx.x;
   double s = 0.0;

@@ -115,7 +115,7 @@ def model_sigmoid_softplus(z):
 
 
 def model_adam(p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0):
-    """adam_elem2 in numpy float32 with the host's parameter preparation (dense.hip adam_launch / adam_kernel) -> (p, m, v).  m and v use
+    """adam_elem2 in numpy float32 with the host's parameter preparation (dd_adam.h adam_bias / adam_kernel) -> (p, m, v).  m and v use
     multiplies and fused multiply-adds only, which are IEEE on the device: they are what the kernels must give bit for bit."""
     q = adam_params(lr, b1, b2, eps, step, grad_scale)
     p, g, m, v = (np.asarray(t, dtype=F) for t in (p, g, m, v))

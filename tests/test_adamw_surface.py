@@ -97,9 +97,9 @@ def test_the_kernels_use_no_scratch_and_the_streaming_kernel_fits_beside_the_con
     for k in ks:
         assert k[".private_segment_fixed_size"] == 0 and k[".group_segment_fixed_size"] == 0, k[".name"]
         assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, k[".name"]
-    by_value = [k for k in ks if "adamw_kernel" in k[".name"]]
+    by_value = [k for k in ks if "11adam_kernelILb0ELb1E" in k[".name"]]      # adam_kernel<DEV = false, DECAY = true>
     assert len(by_value) == 1 and by_value[0][".vgpr_count"] + by_value[0].get(".agpr_count", 0) <= 48, by_value      # dd_adam_step's budget
-    main = [k for k in kernel_resources().kernels(build.LIB) if "11adam_kernel" in k[".name"]]
+    main = [k for k in kernel_resources().kernels(build.LIB) if "11adam_kernelILb0ELb0E" in k[".name"]]
     assert len(main) == 1 and by_value[0][".vgpr_count"] <= main[0][".vgpr_count"], "no more registers than the pass it is a mode of"
 
 

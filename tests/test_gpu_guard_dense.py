@@ -1,4 +1,4 @@
-"""Guard-band cases (tests/_guard.py) for the dense part of the C ABI: csrc/dense.hip (losses, BatchNorm1d + ReLU + dropout, Adam),
+"""Guard-band cases (tests/_guard.py) for the dense part of the C ABI: csrc/dense.hip (losses, BatchNorm1d + ReLU + dropout), csrc/adam.hip,
 csrc/mlp_tail.hip, csrc/adam_rankb.hip, csrc/gradnorm.hip, csrc/linear.hip, csrc/box_loss.hip.
 
 Every case calls the entry point itself (``_lib.call``) on operands that are views into one 0xFF-filled arena, 64 KiB of guard on
@@ -35,8 +35,8 @@ f32, f64, u8, i64 = torch.float32, torch.float64, torch.uint8, torch.int64
 # Launchers that pick a kernel by the alignment of their operands (found by reading every launcher of the files above):
 ALIGNMENT_PICKS = {
     "dd_linear_wgrad": "csrc/linear.hip:554  k >= 512 && k % 4 == 0 && x % 16 == 0 && dw % 16 == 0 -> linear_wgrad_wide_kernel, else the scalar tiles",
-    "dd_bn_relu_drop_fwd": "csrc/dense.hip:637  rows <= 32 && feat >= 65536 && feat % 4 == 0 && every operand % 16 == 0 -> bn_relu_drop_fwd_vec4",
-    "dd_bn_relu_drop_bwd": "csrc/dense.hip:660  rows <= 32 && feat >= 65536 && feat % 2 == 0 && every operand % 8 == 0 -> bn_relu_drop_bwd_vec2",
+    "dd_bn_relu_drop_fwd": "csrc/dense.hip dd_bn_relu_drop_fwd  rows <= 32 && feat >= 65536 && feat % 4 == 0 && every operand % 16 == 0 -> bn_relu_drop_fwd_vec4",
+    "dd_bn_relu_drop_bwd": "csrc/dense.hip dd_bn_relu_drop_bwd  rows <= 32 && feat >= 65536 && feat % 2 == 0 && every operand % 8 == 0 -> bn_relu_drop_bwd_vec2",
 }
 # dd_column_sum (csrc/linear.hip:543) does not pick by address: n % 4 == 0 demands 16 bytes and n % 4 != 0 takes any; the kernel's
 # branch is on n alone.  The two forms of the BatchNorm kernels sum over the rows in the same order, but the running statistics
@@ -508,7 +508,7 @@ def _bn_relu_drop(rows, feat, training, wide_pick=False):
         if wide_pick:
             al = lambda t, a: t.data_ptr() % a == 0
             assert rows <= 32 and feat >= (1 << 16) and feat % 4 == 0
-            assert al(x, 16) == (mode == "natural") and al(dy, 8) == (mode == "natural"), "one mode per kernel of csrc/dense.hip:637 / :660"
+            assert al(x, 16) == (mode == "natural") and al(dy, 8) == (mode == "natural"), "one mode per kernel of dd_bn_relu_drop_fwd / dd_bn_relu_drop_bwd (csrc/dense.hip)"
         call("dd_bn_relu_drop_fwd", x, gamma, beta, rm, rv, None, y, sm, si, rows, feat, eps, mom, 1.0, int(training), nbt)
         call("dd_bn_relu_drop_bwd", dy, x, y, gamma, None, sm, si, rm, rv, dx, dg, db, rows, feat, eps, 1.0, int(training))
         outs = arena.verify()

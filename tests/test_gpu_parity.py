@@ -451,6 +451,24 @@ def test_adam_multi_tensor_matches_torch(dev):
         assert rel_err(q[0], r) < 1e-6
 
 
+@pytest.mark.parametrize("scale_on_device", (False, True))
+def test_adam_multi_checks_the_whole_table_before_the_first_launch(dev, scale_on_device):
+    """49 tensors, one more than a table holds, the last one empty: refused on the host, and the 48 tensors of the first table keep
+    their bits -- parameters, moments and gradients.  (Checked table by table, the first 48 were updated before the refusal.)"""
+    from driving_dirty_amd import ops
+    from driving_dirty_amd._lib import HotpathError
+    host = [tuple(hu((4,), f"{k}{i}", lo, hi) for k, lo, hi in (("p", -1.0, 1.0), ("g", -0.1, 0.1), ("m", -0.05, 0.05), ("v", 1e-4, 1e-2)))
+            for i in range(48)]
+    quads = [tuple(t.to(dev) for t in quad) for quad in host] + [tuple(torch.empty(0, device=dev) for _ in "pgmv")]
+    scale = torch.tensor([0.5], device=dev) if scale_on_device else 0.5
+    with pytest.raises(HotpathError, match="adam_multi: tensor 48: NULL pointer or bad size"):
+        ops.adam_step_multi(quads, 1e-3, 0.9, 0.999, 1e-8, 1, grad_scale=scale)
+    torch.cuda.synchronize()
+    for before, after in zip(host, quads):
+        for b, a in zip(before, after):
+            assert torch.equal(a.cpu().view(torch.int32), b.view(torch.int32))
+
+
 def _grad_floor(g, key):
     """A Linear bias in front of a train-mode BatchNorm has an exactly-zero gradient; in fp32 (the reference's
     own fp32 run included: 3.6e-5 in the fixture) it is rounding noise of the layer's gradient scale, so it is
