@@ -7,9 +7,10 @@ hipcc cross-compiles without a GPU.  The libraries are built IN-TREE so that the
 (a JIT cache under ~/.cache would not).  Each source is compiled to its own object (in parallel, re-done only when the source or a
 header is newer) and the objects are linked into their library.  An extension library holds launch functions that are not part of
 ``include/dd_hotpath.h`` (its set of functions is pinned): a header and sources of its own, the main library's flags, linked against
-the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS`` or -- a library of
-the optimizer -- of ``OPTIMIZER_EXTENSIONS``; the module that binds it holds a ``_lib.Extension`` of that entry.  ``extensions()`` is both
-tables as one mapping: what is built, and what every function here that takes an extension's name looks it up in.
+the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS``, or -- a library of
+the optimizer -- of ``OPTIMIZER_EXTENSIONS``, or -- a library of the prediction path -- of ``PREDICTION_EXTENSIONS``; the module that binds it
+holds a ``_lib.Extension`` of that entry.  ``extensions()`` is the first two tables as one mapping, ``libraries()`` all three: what is built,
+and what every function here that takes an extension's name looks it up in.
 """
 import os
 import subprocess
@@ -42,7 +43,7 @@ def _extension(name, sources, what, internal=()):
     return Extension(name, os.path.join(CSRC, f"libdd_{name}.so"), sources, header, _COMMON + list(internal) + [HEADER, header], what)
 
 
-# To add an extension: a header, a source, one entry here, a module that holds a ``_lib.Extension`` of the entry.
+# To add an extension: a header, a source, one entry in one of the three tables below, a module that holds a ``_lib.Extension`` of the entry.
 EXTENSIONS = {e.name: e for e in (
     _extension("augment", ["augment.hip"], "the augmentation"),                      # augment.py: the train-time augmentation
     _extension("tta", ["tta.hip"], "mirror test-time averaging"),                    # tta.py
@@ -55,9 +56,20 @@ OPTIMIZER_EXTENSIONS = {e.name: e for e in (
 )}
 
 
+# The prediction path's extension libraries: the same kind of entry, the same rules, a table of their own.
+PREDICTION_EXTENSIONS = {e.name: e for e in (
+    _extension("head_mean", ["head_mean.hip"], "the sampled road-map head"),      # mc.py: the head's mean over S dropout draws
+)}
+
+
 def extensions():
-    """Every extension library by name: ``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS``."""
+    """``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS`` by name."""
     return {**EXTENSIONS, **OPTIMIZER_EXTENSIONS}
+
+
+def libraries():
+    """Every extension library by name: ``extensions()`` and then ``PREDICTION_EXTENSIONS``."""
+    return {**extensions(), **PREDICTION_EXTENSIONS}
 
 
 def _stale(target, deps):
@@ -72,12 +84,12 @@ def _library_stale(lib, sources, headers):
 
 
 def extension_needs_build(name):
-    e = extensions()[name]
+    e = libraries()[name]
     return _library_stale(e.lib, e.sources, e.headers)
 
 
 def needs_build():
-    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in extensions())
+    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in libraries())
 
 
 def _run(cmd, verbose):
@@ -119,9 +131,9 @@ def build_diag(verbose=True):
 
 
 def build_extension(name, force=False, verbose=True):
-    """``extensions()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
+    """``libraries()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
     beside it at load time, $ORIGIN), which therefore has to exist."""
-    e = extensions()[name]
+    e = libraries()[name]
     if not force and not extension_needs_build(name):
         return e.lib
     return _library(e.lib, e.sources, OBJ, e.headers, [], ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], force, verbose)
@@ -131,7 +143,7 @@ def build(force=False, verbose=True):
     """The main library and every extension library, each only when it is stale; returns the main library's path."""
     if force or _library_stale(LIB, SOURCES, HEADERS):
         _build_main(force, verbose)
-    for name in extensions():
+    for name in libraries():
         build_extension(name, force, verbose)
     return LIB
 

@@ -133,6 +133,55 @@ class Encoder(nn.Module):
         return ops.EncoderTail.apply(lin1, bn1.weight, bn1.bias, fc2.fc1.weight, fc2.fc1.bias, bn2.weight, bn2.bias, fcz.weight,
                                      fcz.bias, ks[0], ks[1], bn1, bn2, scales[0], scales[1])
 
+    def latent_samples(self, pooled, samples, keeps=None, generator=None):
+        """``samples`` dropout draws of the tail per row of ``pooled`` [B, .] -> z [B * samples, latent], scene-major: row
+        ``b * samples + s`` is draw ``s`` of scene ``b`` (mc.py).  ``fc1``'s Linear -- the one big GEMM of the tail -- runs
+        ONCE on the B rows; its rows are repeated, and BatchNorm -> ReLU -> dropout -> the fc2 block -> ``fc_z_out`` run over the
+        ``B * samples`` rows: one fused launch where its sizes allow (ops.EncoderTail), the separate kernels otherwise.  Both
+        BatchNorms have to be in eval mode (running statistics: the rows are then independent of each other); outside autograd.
+        ``keeps=(k1, k2)``, 0/1 tensors of ``[B * samples, hidden]``, injects the masks; otherwise they are drawn with ``generator``, a
+        device ``torch.Generator`` the caller owns (None: torch's global one)."""
+        fc1, fc2, fcz = self.fc1, self.fc2, self.fc_z_out
+        bn1, bn2 = fc1.fc_bn, fc2.fc_bn
+        for name, bn in (("fc1.fc_bn", bn1), ("fc2.fc_bn", bn2)):
+            if bn.training or bn.running_mean is None:
+                raise RuntimeError(f"Encoder.latent_samples: {name} is in training mode (or keeps no running statistics): the draws of a "
+                                   "scene would enter the batch statistics; call it in eval() mode")
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise ValueError(f"Encoder.latent_samples: samples must be a positive integer, got {samples!r}")
+        keeps = (None, None) if keeps is None else keeps
+        with torch.no_grad():
+            lin1 = ops.linear(pooled, fc1.fc1.weight, fc1.fc1.bias).repeat_interleave(samples, dim=0)
+            m, h1, h2, l = lin1.shape[0], fc1.fc1.out_features, fc2.fc1.out_features, fcz.out_features
+            ks, scales = [], []
+            for blk, keep, width in ((fc1, keeps[0], h1), (fc2, keeps[1], h2)):
+                p = float(blk.drop_p)
+                if keep is None and p > 0.0:      # F.dropout(training=True): always on (components.py:108)
+                    keep = torch.empty((m, width), device=lin1.device, dtype=torch.float32).bernoulli_(1.0 - p, generator=generator)
+                ks.append(keep)
+                scales.append(1.0 / (1.0 - p) if p < 1.0 else 0.0)
+            if ops.mlp_tail_supported(m, h1, h2, l):
+                return ops.EncoderTail.apply(lin1, bn1.weight, bn1.bias, fc2.fc1.weight, fc2.fc1.bias, bn2.weight, bn2.bias, fcz.weight,
+                                             fcz.bias, ks[0], ks[1], bn1, bn2, scales[0], scales[1])
+            h = lin1
+            for blk, keep, scale, lin in ((fc1, ks[0], scales[0], None), (fc2, ks[1], scales[1], fc2.fc1)):
+                if lin is not None:
+                    h = ops.linear(h, lin.weight, lin.bias)
+                bn = blk.fc_bn
+                h = ops.BnReluDrop.apply(h, bn.weight, bn.bias, bn.running_mean, bn.running_var, keep, False, bn.eps,
+                                         0.1 if bn.momentum is None else bn.momentum, scale, None)
+            return ops.linear(h, fcz.weight, fcz.bias)
+
+    def pooled_nhwc4(self, x4):
+        """x4 as ``forward_nhwc4`` takes it -> the pooled vector ``_tail`` / ``latent_samples`` read: the conv stack (fp32, or bf16 for a
+        bf16 image) and the pool, fp32 either way."""
+        if self.c3_only:
+            raise RuntimeError("Encoder.pooled_nhwc4: a c3_only encoder has no dense tail")
+        if x4.dtype == torch.bfloat16:
+            from . import ops_bf16
+            return ops_bf16.encoder_conv_stack(x4, self.c1, self.c2, self.c3)
+        return ops.encoder_conv_stack(x4, self.c1, self.c2, self.c3, True, self.rows_per_task)
+
     def forward_nhwc4(self, x4, keeps=(None, None)):
         """x4: [B,H,W,4] NHWC image (channel 3 zero), e.g. straight from ``ops.stitch6`` (fp32) or
         ``ops_bf16.stitch6_bf16`` (bf16: selects the mixed-precision conv stack)."""

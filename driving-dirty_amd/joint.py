@@ -19,6 +19,7 @@ from collections import namedtuple
 import torch
 from torch import nn
 
+from . import mc as _mc
 from . import ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
@@ -26,8 +27,9 @@ from .adamw import add_weight_decay_args
 from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
-from .roadmap import (RM_LOSS_KEYS, TTA_ROAD_KEYS, CalibratedThreshold, add_rm_loss_args, eval_no_grad, predict_map, predict_map_tta,
-                      prediction_threshold, rm_loss_config, road_map_loss_parts, road_map_scores, tta_road_map_scores)
+from .roadmap import (MC_ROAD_KEYS, RM_LOSS_KEYS, TTA_ROAD_KEYS, CalibratedThreshold, add_rm_loss_args, eval_no_grad, mc_validation_probs,
+                      predict_map, predict_map_mc, predict_map_tta, prediction_threshold, rm_loss_config, road_map_loss_parts, road_map_scores,
+                      tta_road_map_scores)
 from .spatial import (HALF_UNLESS_CALIBRATED, ONE_UNLESS_CONFIGURED, CalibratedBoxThreshold, RoadMapBoxesMergingCNN, SpatialMappingCNN,
                       add_box_args, bb_coord_to_map, box_decode_point, box_loss_config, boxes_from_map, decoded_box_ats, mean_logs,
                       per_sample_inputs, require_bounding_boxes)
@@ -56,6 +58,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
             self.box_merge.precision = precision
         self.box_loss = box_loss_config(hparams)      # None: BCE on probabilities as the reference's box model (spatial_w_rm.py:131)
         self.rm_loss = rm_loss_config(hparams)        # None: mean BCE-with-logits (roadmap_bce_v2.py:106)
+        _mc.check_hparams(hparams)                    # mc_samples / mc_seed: the road map from S dropout draws of the tail (mc.py)
         self.box_rm_input = hparam(hparams, "box_rm_input", "target")
         if self.box_rm_input not in ("target", "predicted"):
             raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")
@@ -110,14 +113,15 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         return self._road_logits(pooled), boxes
 
     # ------------------------------------------------------------------------------------------------ prediction
-    def _tta_maps(self, scene, mirrored, tau):
+    def _tta_maps(self, scene, mirrored, tau, from_logits=True):
         """Mirror test-time averaging of the camera-only construction (tta.py), from the parts of the two passes: ``scene`` and
-        ``mirrored`` are each ``(feat, space_rep, road logits)``.  -> (road map torch.bool [B,800,800], averaged box map fp32
+        ``mirrored`` are each ``(feat, space_rep, road logits)`` -- or, with ``from_logits=False``, ``(feat, space_rep, road probabilities)``:
+        the S-draw means of mc.py.  -> (road map torch.bool [B,800,800], averaged box map fp32
         [B,800,800]).  The road map is ``tta.mean_gt`` of the two logits at ``tau``; the scene's box branch reads it, the mirrored
         box branch reads ``tta.mirror_masks`` of it -- the map a mirrored training sample's box head was given -- and ``tta.mean_prob``
         brings the two box maps together."""
         (feat, space_rep, logits), (feat_m, space_rep_m, logits_m) = scene, mirrored
-        road = _tta.mean_gt(logits.detach().contiguous(), logits_m.detach().contiguous(), tau, True)
+        road = _tta.mean_gt(logits.detach().contiguous(), logits_m.detach().contiguous(), tau, from_logits)
         probs = self._box_branch(feat, space_rep, tuple(road.unbind(0)))
         probs_m = self._box_branch(feat_m, space_rep_m, _tta.mirror_masks(road))
         return road, _tta.mean_prob(probs.detach().contiguous(), probs_m.detach().contiguous(), False)
@@ -138,8 +142,9 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         whatever ``forward`` takes.  The same kernels on the same inputs as ``predict_road_map(x)`` followed by
         ``predict_boxes(x, masks)``, minus the second encoder conv pass.
 
-        Under ``hparams.tta_mirror`` (default off) the prediction is made with mirror test-time averaging.  This method's signature is
-        pinned, so it follows the hparams; ``predict_mode`` is the same method with the mode as an argument.
+        Under ``hparams.tta_mirror`` (default off) the prediction is made with mirror test-time averaging, under ``hparams.mc_samples``
+        > 1 from the mean of that many dropout draws per scene, which the box head then reads thresholded (``_predict_mc``).  This
+        method's signature is pinned, so it follows the hparams; ``predict_mode`` is the same method with both as arguments.
 
         Mirror test-time averaging (``_tta_maps``): two passes at B -- the scene, and the same code on ``tta.mirror_views(x)`` -- the
         road map from the mean of the two heads' probabilities, the box map the mean of the two box branches' maps, each fed the road
@@ -149,12 +154,45 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         on the averaged maps, and ``tta=False`` on such a checkpoint reuses them as they are."""
         return self.predict_mode(x, None, threshold, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
+    def _pooled(self, x):
+        """The encoder's pooled vector alone (no box-branch inputs): what ``Encoder.latent_samples`` reads."""
+        x = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
+        return self.ae.encoder.pooled_nhwc4(ops.wide_image(x))
+
+    def _mc_probs(self, x, samples, gen):
+        """Road-map probabilities [B,800,800] averaged over ``samples`` dropout draws per scene, masks from ``gen``; for ``eval_no_grad``."""
+        return _mc.head_mean_prob(self, self.ae.encoder, self._pooled(x), samples, gen)
+
+    def _predict_mc(self, x, mode, tau, samples):
+        """``predict_mode``'s two maps under ``samples`` > 1 dropout draws per scene (mc.py) -> (road map, box map): the road map is the
+        S-draw mean of the head's probabilities ``> tau`` -- one pass of the conv stack and of ``fc1``, S draws of the tail from the
+        module's own generator, the mean inside the head's kernel -- and the box branch reads that averaged map.  Under the mirror
+        ``mode`` each pass yields its S-draw mean and ``_tta_maps`` goes on from the two as it does from two logits."""
+        gen = _mc.generator(self, self.fc1.weight.device)
+        enc = self.ae.encoder
+        feat, pooled, space_rep = self._features(x)
+        if mode is None:
+            road = _mc.head_mean_gt(self, enc, pooled, samples, gen, tau)
+            return road, self._box_branch(feat, space_rep, tuple(road.unbind(0)))
+        probs = _mc.head_mean_prob(self, enc, pooled, samples, gen)
+        feat_m, pooled_m, space_rep_m = self._features(_tta.mirror_views(x))
+        probs_m = _mc.head_mean_prob(self, enc, pooled_m, samples, gen)
+        return self._tta_maps((feat, space_rep, probs), (feat_m, space_rep_m, probs_m), tau, from_logits=False)
+
     def predict_mode(self, x, tta=None, threshold=None, box_threshold=HALF_UNLESS_CALIBRATED, min_pixels=ONE_UNLESS_CONFIGURED, max_boxes=256,
-                     fit="extent", pad_px=0.5, split_px=0, grow_iters=None):
+                     fit="extent", pad_px=0.5, split_px=0, grow_iters=None, mc_samples=None):
         """``predict`` with the averaging mode as an argument: ``tta`` None = ``hparams.tta_mirror`` (what ``predict`` does), False = off,
-        True / "mirror" = mirror test-time averaging.  Everything else as ``predict``'s."""
+        True / "mirror" = mirror test-time averaging; ``mc_samples`` None = ``hparams.mc_samples`` (what ``predict`` does), else the number
+        of dropout draws per scene the road map is averaged over (``_predict_mc``; 1 = a single draw, the calls below).  Everything else
+        as ``predict``'s."""
         tau = prediction_threshold(self, threshold)
         box_threshold, min_pixels = box_decode_point(self.hparams, box_threshold, min_pixels)
+        samples = _mc.resolve(self, mc_samples)
+        if samples > 1:
+            with eval_no_grad(self):
+                road, probs = self._predict_mc(x, _tta.resolve(self, tta), tau, samples)
+                boxes = boxes_from_map(probs, box_threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
+            return Prediction(road, boxes)
         if _tta.resolve(self, tta) is not None:
             with eval_no_grad(self):
                 feat, pooled, space_rep = self._features(x)
@@ -187,10 +225,13 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         with torch.no_grad():
             return boxes_from_map(self(x, rm)[1], threshold, min_pixels, max_boxes, fit, pad_px, split_px, grow_iters)
 
-    def predict_road_map(self, x, threshold=None, tta=None):
-        """The road-map branch as a boolean map, as ``RoadMapBCE.predict_road_map`` (``tta`` included): torch.bool [B,800,800]; the box
-        branch is not run."""
+    def predict_road_map(self, x, threshold=None, mc_samples=None, tta=None):
+        """The road-map branch as a boolean map, as ``RoadMapBCE.predict_road_map`` (``tta`` and ``mc_samples`` included): torch.bool
+        [B,800,800]; the box branch is not run."""
         views = tuple(t.contiguous() for t in x) if isinstance(x, (tuple, list)) else x.contiguous()
+        samples = _mc.resolve(self, mc_samples)
+        if samples > 1:
+            return predict_map_mc(self, self._pooled, views, threshold, _tta.resolve(self, tta), samples)
         if _tta.resolve(self, tta) is not None:
             return predict_map_tta(self, lambda v: self.ae.encoder.forward_nhwc4(ops.wide_image(v)), views, threshold)
         return predict_map(self, lambda: self.ae.encoder.forward_nhwc4(ops.wide_image(views)), threshold)
@@ -289,7 +330,12 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         Under ``hparams.tta_mirror`` also one pass over the mirrored batch (``no_grad``): the road map's ``val_ts_tta`` /
         ``val_ts_rounded_tta`` from the averaged probabilities, which ``ts_hist`` is then taken from; under ``hparams.box_metrics``
         ``val_ats_tta``, camera-only, the construction of ``predict`` in this mode (``_tta_maps``) with the features of both passes
-        reused; and ``box_ats_sweep`` reads that averaged box map.  Every other key keeps its meaning."""
+        reused; and ``box_ats_sweep`` reads that averaged box map.  Every other key keeps its meaning.
+
+        Under ``hparams.mc_samples`` > 1 also one encoder pass in ``eval()`` mode whose tail is drawn S times per scene: ``val_ts_mc`` /
+        ``val_ts_rounded_mc`` from the S-draw mean (with the mirror, ``val_ts_tta`` / ``val_ts_rounded_tta`` from the mean of the two
+        passes' S-draw means), and ``ts_hist`` from the most-averaged probabilities, so ``rm_threshold`` is calibrated in the mode
+        ``predict`` runs in.  The box keys (``val_ats*``, ``box_ats_sweep``) go on reading the single-draw pass's road map."""
         sample, target, road_image = batch
         s = self._run_step(batch, False, True)
         out = {"val_loss": s["loss_rm"] + s["loss_bb"], "val_roadmap_loss": s["loss_rm"], "val_bbox_loss": s["loss_bb"]}
@@ -299,10 +345,15 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
             out["val_rm_bce"], out["val_rm_soft_ts"] = s["rm_parts"]
         target_rm = torch.stack(tuple(road_image), dim=0).float()
         out.update(road_map_scores(target_rm, s["probs"]))
-        averaged = _tta.resolve(self, None) is not None
+        mode, samples = _tta.resolve(self, None), _mc.resolve(self, None)
+        averaged = mode is not None
         if averaged:
             with torch.no_grad():
                 mirrored = self._mirrored_parts(s["sample"])
+        if samples > 1:      # val_ts_mc / val_ts_rounded_mc; under the mirror the _tta keys from the two S-draw means; ts_hist from the most-averaged
+            self._with_ts_hist(out, mc_validation_probs(self, out, target_rm, self._mc_probs, s["sample"], samples, mode), target_rm)
+        elif averaged:
+            with torch.no_grad():
                 avg = _tta.mean_prob(s["logits"].detach().contiguous(), mirrored[2].detach().contiguous(), True)
             self._with_ts_hist(tta_road_map_scores(out, target_rm, avg), avg, target_rm)
         else:
@@ -328,7 +379,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         """The mean of every per-batch value as ``avg_*``; ``val_loss`` is the monitored value; under ``hparams.calibrate_threshold``
         ``rm_threshold`` is set from the epoch's summed histogram, as in ``RoadMapBCE``."""
         keys = ("val_loss", "val_roadmap_loss", "val_bbox_loss", "val_bce", "val_soft_ts", "val_ts", "val_ts_rounded", "val_ats_gt_rm",
-                "val_ats", "val_box_ts", "val_ats_tta") + TTA_ROAD_KEYS + RM_LOSS_KEYS
+                "val_ats", "val_box_ts", "val_ats_tta") + TTA_ROAD_KEYS + MC_ROAD_KEYS + RM_LOSS_KEYS
         logs = mean_logs(outputs, keys)
         self._calibrate(outputs, logs)
         if self._wants_box_sweep():
@@ -356,6 +407,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
                        help="fp32: the reference's arithmetic; fp32x3: the box head's dilated up-convs as six bf16 products per fp32 product")
         add_augment_args(p)
         _tta.add_tta_args(p)
+        _mc.add_mc_args(p)
         add_ema_args(p)
         add_weight_decay_args(p)
         add_rm_loss_args(p)

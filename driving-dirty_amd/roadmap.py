@@ -12,6 +12,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from . import mc as _mc
 from . import ops
 from . import tta as _tta
 from .augment import Augmenter, add_augment_args, current_rank
@@ -67,6 +68,33 @@ def predict_map_tta(module, encode, x, threshold):
         return _tta.mean_gt(logits, logits_m, tau, True)
 
 
+def predict_map_mc(module, pooled, x, threshold, tta, samples):
+    """``predict_map`` / ``predict_map_tta`` from the mean of ``samples`` > 1 dropout draws per scene (mc.py): ``pooled(x)`` is the conv
+    stack up to the encoder's pooled vector, run ONCE per pass; ``Encoder.latent_samples`` draws the tail ``samples`` times per scene
+    from the module's own generator, reseeded from ``hparams.mc_seed`` here; ``mc.mean_gt`` with ``module.fc1`` is the head, the mean of a
+    scene's probabilities and the comparison in one kernel.  Under the mirror mode ``tta`` each of the two passes yields its mean
+    through ``mc.mean_prob`` (the mirrored pass goes on drawing from the same generator) and ``tta.mean_gt`` brings the two together.
+    Same mode handling as ``predict_map``."""
+    tau = prediction_threshold(module, threshold)
+    with eval_no_grad(module):
+        enc = module.ae.encoder
+        gen = _mc.generator(module, module.fc1.weight.device)
+        if tta is None:
+            return _mc.head_mean_gt(module, enc, pooled(x), samples, gen, tau)
+        probs = _mc.head_mean_prob(module, enc, pooled(x), samples, gen)
+        probs_m = _mc.head_mean_prob(module, enc, pooled(_tta.mirror_views(x)), samples, gen)
+        return _tta.mean_gt(probs, probs_m, tau, False)
+
+
+def mc_road_map_scores(out, target_rm, avg_probs):
+    """``out`` <- ``val_ts_mc`` / ``val_ts_rounded_mc``: ``road_map_scores`` of the probabilities averaged over the draws (hparams.mc_samples)."""
+    out.update({k + "_mc": v for k, v in road_map_scores(target_rm, avg_probs).items()})
+    return out
+
+
+MC_ROAD_KEYS = ("val_ts_mc", "val_ts_rounded_mc")
+
+
 def tta_road_map_scores(out, target_rm, avg_probs):
     """``out`` <- ``val_ts_tta`` / ``val_ts_rounded_tta``: ``road_map_scores`` of the averaged probabilities (hparams.tta_mirror)."""
     out.update({k + "_tta": v for k, v in road_map_scores(target_rm, avg_probs).items()})
@@ -74,6 +102,21 @@ def tta_road_map_scores(out, target_rm, avg_probs):
 
 
 TTA_ROAD_KEYS = ("val_ts_tta", "val_ts_rounded_tta")
+
+
+def mc_validation_probs(module, out, target_rm, mc_probs, sample, samples, mode):
+    """The validation step's extra pass under ``hparams.mc_samples`` > 1: ``mc_probs(sample, samples, gen)`` in ``eval()`` mode under
+    ``no_grad`` -> ``out`` gains ``val_ts_mc`` / ``val_ts_rounded_mc``; under the mirror ``mode`` the same on the mirrored batch, and
+    ``val_ts_tta`` / ``val_ts_rounded_tta`` from ``tta.mean_prob`` of the two means.  Returns the most-averaged probabilities, which
+    ``ts_hist`` is taken from."""
+    with eval_no_grad(module):
+        gen = _mc.generator(module, module.fc1.weight.device)
+        avg = mc_probs(sample, samples, gen)
+        mc_road_map_scores(out, target_rm, avg)
+        if mode is not None:
+            avg = _tta.mean_prob(avg, mc_probs(_tta.mirror_views(sample), samples, gen), False)
+            tta_road_map_scores(out, target_rm, avg)
+    return avg
 
 
 def compute_ts_road_map(road_map1, road_map2):
@@ -180,6 +223,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         super().__init__()
         self.hparams = hparams
         self.rm_loss = rm_loss_config(hparams)
+        _mc.check_hparams(hparams)
         self.output_dim = 800 * 800
         # pretrained feature extractor (roadmap_bce_v2.py:43-47); ``pretrained_ae`` lets callers hand in
         # an already-built BasicAE when no checkpoint file exists (the reference's paths are NYU-local)
@@ -216,7 +260,15 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         y = self._logits(x, keeps)
         return y, ops.sigmoid(y.detach())
 
-    def predict_road_map(self, x, threshold=None, tta=None):
+    def _pooled(self, sample):
+        """``_encode`` up to the encoder's pooled vector: what ``Encoder.latent_samples`` reads."""
+        return self.ae.encoder.pooled_nhwc4(ops.wide_image(sample, self.ae.encoder.precision))
+
+    def _mc_probs(self, sample, samples, gen):
+        """Probabilities [B,800,800] averaged over ``samples`` dropout draws per scene, masks from ``gen``; for ``eval_no_grad``."""
+        return _mc.head_mean_prob(self, self.ae.encoder, self._pooled(sample), samples, gen)
+
+    def predict_road_map(self, x, threshold=None, mc_samples=None, tta=None):
         """The reference's "Predicting test images" step (run_test.py) for one batch: torch.bool [B,800,800], equal to ``forward``'s
         probabilities ``> threshold`` in eval mode.  ``x``: whatever ``forward`` takes.  Encoder, then the head, the sigmoid and the
         comparison in one kernel: neither logits nor probabilities are written.  (The dense blocks' dropout is on in eval mode too, as
@@ -226,8 +278,16 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         (``predict_map_tta``): the scene and its mirror, each through encoder and head, the mean of the two probabilities
         ``> threshold``.  With dropout on the two passes draw two masks.  ``threshold=None`` is the one calibrated ``rm_threshold`` in
         either mode: under ``hparams.tta_mirror`` validation calibrates it on the averaged probabilities, and ``tta=False`` on such a
-        checkpoint reuses it as it is."""
-        if _tta.resolve(self, tta) is None:
+        checkpoint reuses it as it is.
+
+        ``mc_samples``: None = ``hparams.mc_samples`` (default 1), else S in 1 .. 64.  S > 1 (``predict_map_mc``): the conv stack and
+        ``fc1``'s Linear once, S dropout draws of the tail per scene from the module's own generator (reseeded from ``hparams.mc_seed``
+        at every call: the same call gives the same map), and the mean of the S probabilities ``> threshold`` inside the head's
+        kernel; with ``tta`` the mean of the two passes' S-draw means.  S = 1 is the single draw described above, call for call."""
+        samples, mode = _mc.resolve(self, mc_samples), _tta.resolve(self, tta)
+        if samples > 1:
+            return predict_map_mc(self, self._pooled, x, threshold, mode, samples)
+        if mode is None:
             return predict_map(self, lambda: self._encode(x), threshold)
         return predict_map_tta(self, self._encode, x, threshold)
 
@@ -288,12 +348,21 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         averaged probabilities; ``ts_hist`` (``hparams.calibrate_threshold``) is then taken from those, so ``rm_threshold`` is
         calibrated in the mode the checkpoint predicts in.  ``val_loss``, ``val_ts`` and ``val_ts_rounded`` keep their meaning.  Under an
         ``rm_*`` setting ``val_loss`` is the composite loss and ``val_rm_bce`` / ``val_rm_soft_ts`` its two components; the scores and
-        ``ts_hist`` read the loss pass's probabilities as before."""
+        ``ts_hist`` read the loss pass's probabilities as before.
+
+        Under ``hparams.mc_samples`` > 1 also one encoder pass in ``eval()`` mode (``no_grad``) whose tail is drawn S times per scene
+        (generator reseeded from ``hparams.mc_seed``), and ``val_ts_mc`` / ``val_ts_rounded_mc``, the scores of the S-draw mean.  With
+        ``hparams.tta_mirror`` as well, a mirrored pass of the same kind joins it and ``val_ts_tta`` / ``val_ts_rounded_tta`` are taken
+        from the mean of the two S-draw means: what ``predict_road_map`` thresholds in that mode.  ``ts_hist`` reads the most-averaged
+        probabilities."""
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, **road_map_scores(target_rm, pred_logit_rm)}
         if self.rm_loss is not None:
             out["val_rm_bce"], out["val_rm_soft_ts"] = self._rm_parts
-        if _tta.resolve(self, None) is None:
+        samples, mode = _mc.resolve(self, None), _tta.resolve(self, None)
+        if samples > 1:
+            return self._with_ts_hist(out, mc_validation_probs(self, out, target_rm, self._mc_probs, batch[0], samples, mode), target_rm)
+        if mode is None:
             return self._with_ts_hist(out, pred_logit_rm, target_rm)
         with torch.no_grad():
             avg = _tta.mean_prob(pred_rm.detach().contiguous(), self._logits(_tta.mirror_views(batch[0])), True)
@@ -302,7 +371,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
-        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS + RM_LOSS_KEYS
+        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS + MC_ROAD_KEYS + RM_LOSS_KEYS
                      if outputs and all(k in x for x in outputs)})
         self._calibrate(outputs, logs)
         return {"val_loss": avg["val_loss"], "log": logs}
@@ -325,6 +394,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
                        help="validation also finds the threshold with the best data-set threat score (rm_threshold)")
         add_augment_args(p)
         _tta.add_tta_args(p)
+        _mc.add_mc_args(p)
         add_ema_args(p)
         add_weight_decay_args(p)
         add_rm_loss_args(p)
@@ -365,7 +435,10 @@ class RoadMap(RoadMapBCE):
         val_loss, target_rm, pred_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, "val_ts": compute_ts_road_map(target_rm, pred_rm),
                "val_ts_rounded": ops.threat_score(target_rm.contiguous(), pred_rm.contiguous(), round_b=True)}
-        if _tta.resolve(self, None) is None:
+        samples, mode = _mc.resolve(self, None), _tta.resolve(self, None)
+        if samples > 1:      # as RoadMapBCE's: the head's probabilities are this model's output too
+            return self._with_ts_hist(out, mc_validation_probs(self, out, target_rm, self._mc_probs, batch[0], samples, mode), target_rm)
+        if mode is None:
             return self._with_ts_hist(out, pred_rm, target_rm)
         with torch.no_grad():      # ``forward`` ends in the head's sigmoid here: the mean of the two PROBABILITIES, the same bits as from the logits
             avg = _tta.mean_prob(pred_rm.detach().contiguous(), self(_tta.mirror_views(batch[0])).contiguous(), False)

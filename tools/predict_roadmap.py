@@ -2,14 +2,17 @@
 (``run_test.py --rm_ckpt_path ...``) on the HIP hot path.
 
     python tools/predict_roadmap.py --rm_ckpt_path rm.ckpt --out maps/ [--model roadmap_bce|roadmap_mse] [--frames frames.npy]
-                                    [--scenes 32] [--batch_size 32] [--threshold 0.4] [--tta_mirror] [--timing profiles/predict_timing.json]
+                                    [--scenes 32] [--batch_size 32] [--threshold 0.4] [--tta_mirror] [--mc_samples 16] [--mc_seed 0]
+                                    [--timing profiles/predict_timing.json]
 
 Input: ``--frames`` a .npy of decoded camera frames, uint8 [S,6,H,W,3], or of views as ToTensor delivers them, fp32 [S,6,3,H,W];
 without it ``--scenes`` closed-form synthetic scenes (driving_dirty_amd/synth.py) at the size the checkpoint's encoder was built
 for.  Output: ``<out>/road_map_00000.npy`` ... one bool [800,800] map per scene, from ``predict_road_map`` at ``--threshold``
 (default: the threshold the checkpoint was calibrated to, else 0.5).  ``--tta_mirror``: the maps are predicted with mirror test-time
 averaging (the mean of the scene's and the mirrored scene's probabilities, driving_dirty_amd/tta.py); without it the checkpoint's own
-``tta_mirror`` flag decides.  The timing below then has a third path, ``predict_road_map_tta``.
+``tta_mirror`` flag decides.  The timing below then has a third path, ``predict_road_map_tta``.  ``--mc_samples S``: the maps are the
+mean of S dropout draws of the encoder's tail per scene (driving_dirty_amd/mc.py), seeded by ``--mc_seed``, so the same command writes
+the same maps; without them the checkpoint's own ``mc_samples`` / ``mc_seed`` decide.  The timing then has the path ``predict_road_map_mc``.
 
 Then the first batch is timed both ways in this process: ``predict_road_map`` (encoder -> dd_linear_sigmoid_gt) and ``forward``
 followed by ``> tau`` in torch.  A window is ``--iters`` calls between two ``torch.cuda.synchronize()``; after ``--warmup``
@@ -28,7 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from driving_dirty_amd import synth, tta  # noqa: E402
+from driving_dirty_amd import mc, synth, tta  # noqa: E402
 from driving_dirty_amd.roadmap import RoadMap, RoadMapBCE  # noqa: E402
 
 MODELS = {"roadmap_bce": RoadMapBCE, "roadmap_mse": RoadMap}      # the reference's registry names
@@ -77,6 +80,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--threshold", type=float, default=None)
     ap.add_argument("--tta_mirror", action="store_true", help="mirror test-time averaging (default: as the checkpoint's hparams say)")
+    ap.add_argument("--mc_samples", type=int, default=None, help="dropout draws per scene the map is averaged over, 1 .. 64 (default: as the checkpoint's hparams say)")
+    ap.add_argument("--mc_seed", type=int, default=None, help="seed of those draws (default: as the checkpoint's hparams say, else 0)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--windows", type=int, default=7)
@@ -89,19 +94,25 @@ def main():
     tau = args.threshold if args.threshold is not None else (model.rm_threshold if model.rm_threshold is not None else 0.5)
     batches = load_scenes(args, model, dev)
     mode = tta.resolve(model, True if args.tta_mirror else None)
+    if args.mc_seed is not None:
+        model.hparams.mc_seed = args.mc_seed
+        mc.seed_of(model)      # refuses a negative one by name
+    draws = mc.resolve(model, args.mc_samples)
 
     os.makedirs(args.out, exist_ok=True)
     n = 0
     for x in batches:
-        for m in model.predict_road_map(x, tau, tta=mode is not None).cpu().numpy():
+        for m in model.predict_road_map(x, tau, mc_samples=draws, tta=mode is not None).cpu().numpy():
             np.save(os.path.join(args.out, f"road_map_{n:05d}.npy"), m)
             n += 1
 
     x = batches[0]
     b = len(x)
-    paths = {"predict_road_map": lambda: model.predict_road_map(x, tau, tta=False), "forward_then_torch_threshold": lambda: unfused(model, x, tau)}
+    paths = {"predict_road_map": lambda: model.predict_road_map(x, tau, mc_samples=1, tta=False), "forward_then_torch_threshold": lambda: unfused(model, x, tau)}
     if mode is not None:
-        paths["predict_road_map_tta"] = lambda: model.predict_road_map(x, tau, tta=True)
+        paths["predict_road_map_tta"] = lambda: model.predict_road_map(x, tau, mc_samples=1, tta=True)
+    if draws > 1:
+        paths["predict_road_map_mc"] = lambda: model.predict_road_map(x, tau, mc_samples=draws, tta=False)
     for fn in paths.values():
         for _ in range(args.warmup):
             fn()
@@ -110,7 +121,7 @@ def main():
         for k, fn in paths.items():
             secs[k].append(window(fn, args.iters))
     result = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName, "torch": torch.__version__,
-              "argv": sys.argv[1:], "model": args.model, "precision": model.ae.encoder.precision, "threshold": tau, "tta": mode, "scenes_written": n,
+              "argv": sys.argv[1:], "model": args.model, "precision": model.ae.encoder.precision, "threshold": tau, "tta": mode, "mc_samples": draws, "mc_seed": mc.seed_of(model), "scenes_written": n,
               "batch": b, "iters_per_window": args.iters, "windows": args.windows}
     for k, v in secs.items():
         rate = sorted(b * args.iters / s for s in v)
@@ -120,6 +131,8 @@ def main():
               f"{result[k]['ms_per_batch_median']:.3f} ms per batch of {b}")
     if mode is not None:
         result["tta_over_plain"] = result["predict_road_map_tta"]["ms_per_batch_median"] / result["predict_road_map"]["ms_per_batch_median"]
+    if draws > 1:
+        result["mc_over_plain"] = result["predict_road_map_mc"]["ms_per_batch_median"] / result["predict_road_map"]["ms_per_batch_median"]
     print(json.dumps(result))
     if args.timing:
         os.makedirs(os.path.dirname(os.path.abspath(args.timing)), exist_ok=True)
