@@ -31,7 +31,7 @@ EXTRA_FLAGS = {"adam_rankb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 HEADER = os.path.join(INCLUDE, "dd_hotpath.h")      # the C ABI; _lib.py derives its ctypes table from it
 _COMMON = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h")]
 _LOSS_STATS = os.path.join(CSRC, "dd_loss_stats.h")      # the device code box_loss.hip and rm_loss.hip share
-HEADERS = _COMMON + [os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "adam_rankb_kernels.inc"), _LOSS_STATS, HEADER]
+HEADERS = _COMMON + [os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "dd_conv_strip.h"), os.path.join(CSRC, "conv_wino.inc"), os.path.join(CSRC, "conv_wino2.inc"), os.path.join(CSRC, "adam_rankb_kernels.inc"), _LOSS_STATS, HEADER]
 
 # An extension library.  ``lib``: the .so; ``sources``: under csrc/; ``header``: its public header, from which the binder derives its
 # ctypes table; ``headers``: what its objects depend on; ``what``: the noun of the binder's missing-library message.

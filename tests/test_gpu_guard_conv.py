@@ -1,5 +1,5 @@
-"""Guard-band cases (tests/_guard.py) for the 3x3 convolution kernels of csrc/conv3x3.hip: the direct family (dd_conv_pack, _fwd,
-_fwd_relu_bits, _dgrad, _dgrad_relu_bits, _wgrad) and the two Winograd families (dd_conv_wino_*, dd_conv_wino2_*, with
+"""Guard-band cases (tests/_guard.py) for the fp32 3x3 convolution kernels: the direct family of csrc/conv3x3.hip (dd_conv_pack, _fwd,
+_fwd_relu_bits, _dgrad, _dgrad_relu_bits, _wgrad) and the two Winograd families of csrc/conv_wino.inc and csrc/conv_wino2.inc (dd_conv_wino_*, dd_conv_wino2_*, with
 _dgrad_w1, _wgrad_partials and _wgrad_finish) and the BatchNorm2d variant (dd_conv_fwd_stats, dd_conv_dgrad_bn, dd_conv_wgrad_bn).  Packed-weight buffers are exactly ``*_packed_floats`` floats, workspaces exactly
 their queries (76 MB of per-wave partials for the 32-channel weight gradient, whatever the image size), both left 0xFF.  What a case asserts: tests/test_gpu_guard_dense.py.  None of these launchers looks at an address.
 

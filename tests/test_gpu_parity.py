@@ -154,6 +154,28 @@ def test_conv_winograd_fwd_dgrad_wgrad(dev, b, h, w, rows):
         ops.conv_wino_pack(wd, ops.conv_desc(b, h, w, 32, 2), 0)           # stride 2 has no Winograd path
 
 
+@pytest.mark.parametrize("b,h,w", [(1, 4, 4), (2, 8, 40)])
+def test_conv_wino2_wgrad_in_two_calls(dev, b, h, w):
+    """dd_conv_wino2_wgrad_partials + dd_conv_wino2_wgrad_finish find the partials where dd_conv_wino2_wgrad's two halves do (one
+    workspace layout, csrc/conv_wino2.inc Wino2WgradWs): the same bits from both, and fp64's values -- what holds the layout: a
+    wrong offset of the bias rows or of the chunk sums gives wrong sums.  The smallest shape ops.wino2_desc accepts (one
+    workgroup: the offsets are one partial long), and 16 row tiles = four workgroups."""
+    from driving_dirty_amd import ops
+    desc = ops.wino2_desc(b, h, w)
+    assert desc is not None
+    x = hu((b, 32, h, w), f"w2x{b}{h}{w}", 0.0, 1.0).double()
+    gy = hu((b, 32, h, w), f"w2gy{b}{h}{w}").double()
+    wt = torch.zeros(32, 32, 3, 3, dtype=torch.float64, requires_grad=True)
+    bias = torch.zeros(32, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x, wt, bias, padding=1).backward(gy)
+    xd, gd = nhwc(x.float()).to(dev), nhwc(gy.float()).to(dev)
+    dw, db = ops.conv_wino2_wgrad(xd, gd, desc)
+    dw2, db2, done = ops.conv_wino2_wgrad(xd, gd, desc, finish_stream=torch.cuda.Stream())
+    torch.cuda.current_stream().wait_event(done)
+    assert torch.equal(dw2, dw) and torch.equal(db2, db)
+    assert rel_err(dw, wt.grad) < KERNEL_TOL and rel_err(db, bias.grad) < KERNEL_TOL
+
+
 def test_conv_refuses_unsupported(dev):
     from driving_dirty_amd import _lib, ops
     d = _lib.ConvDesc(1, 8, 8, 32, 32, 32, 5, 1, 2, 0)

@@ -33,7 +33,7 @@ from test_gpu_heads import CHAIN_TOL, rel_err
 pytestmark = pytest.mark.gpu
 
 WAVES_PER_CU = 32            # 8 waves on each of the 4 SIMDs: the most any kernel can keep resident on one CU
-FP32_WAVES_PER_CU = 16       # conv3x3.hip resident_grid(): per_cu <= 2 workgroups of WPB <= 8 waves
+FP32_WAVES_PER_CU = 16       # dd_conv_strip.h resident_grid(): per_cu <= 2 workgroups of WPB <= 8 waves
 FULL = 256                   # dd_set_cu_budget's default: the whole chip
 
 
