@@ -8,9 +8,10 @@ hipcc cross-compiles without a GPU.  The libraries are built IN-TREE so that the
 header is newer) and the objects are linked into their library.  An extension library holds launch functions that are not part of
 ``include/dd_hotpath.h`` (its set of functions is pinned): a header and sources of its own, the main library's flags, linked against
 the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS``, or -- a library of
-the optimizer -- of ``OPTIMIZER_EXTENSIONS``, or -- a library of the prediction path -- of ``PREDICTION_EXTENSIONS``; the module that binds it
-holds a ``_lib.Extension`` of that entry.  ``extensions()`` is the first two tables as one mapping, ``libraries()`` all three: what is built,
-and what every function here that takes an extension's name looks it up in.
+the optimizer -- of ``OPTIMIZER_EXTENSIONS``, or -- a library of the prediction path -- of ``PREDICTION_EXTENSIONS``, or -- a library of a
+training loss that is off by default -- of ``TRAINING_EXTENSIONS``; the module that binds it holds a ``_lib.Extension`` of that entry.
+``extensions()`` is the first two tables as one mapping, ``libraries()`` the first three, ``every_library()`` all four: what is built, and
+what every function here that takes an extension's name looks it up in.
 """
 import os
 import subprocess
@@ -30,7 +31,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 EXTRA_FLAGS = {"adam_rankb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 HEADER = os.path.join(INCLUDE, "dd_hotpath.h")      # the C ABI; _lib.py derives its ctypes table from it
 _COMMON = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h")]
-_LOSS_STATS = os.path.join(CSRC, "dd_loss_stats.h")      # the device code box_loss.hip and rm_loss.hip share
+_LOSS_STATS = os.path.join(CSRC, "dd_loss_stats.h")      # the device code box_loss.hip, rm_loss.hip and consistency.hip share
 HEADERS = _COMMON + [os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "dd_conv_strip.h"), os.path.join(CSRC, "conv_wino.inc"), os.path.join(CSRC, "conv_wino2.inc"), os.path.join(CSRC, "adam_rankb_kernels.inc"), _LOSS_STATS, HEADER]
 
 # An extension library.  ``lib``: the .so; ``sources``: under csrc/; ``header``: its public header, from which the binder derives its
@@ -43,7 +44,7 @@ def _extension(name, sources, what, internal=()):
     return Extension(name, os.path.join(CSRC, f"libdd_{name}.so"), sources, header, _COMMON + list(internal) + [HEADER, header], what)
 
 
-# To add an extension: a header, a source, one entry in one of the three tables below, a module that holds a ``_lib.Extension`` of the entry.
+# To add an extension: a header, a source, one entry in one of the four tables below, a module that holds a ``_lib.Extension`` of the entry.
 EXTENSIONS = {e.name: e for e in (
     _extension("augment", ["augment.hip"], "the augmentation"),                      # augment.py: the train-time augmentation
     _extension("tta", ["tta.hip"], "mirror test-time averaging"),                    # tta.py
@@ -62,6 +63,12 @@ PREDICTION_EXTENSIONS = {e.name: e for e in (
 )}
 
 
+# The libraries of the training losses that are off by default: the same kind of entry, the same rules, a table of their own.
+TRAINING_EXTENSIONS = {e.name: e for e in (
+    _extension("consistency", ["consistency.hip"], "the consistency loss", [_LOSS_STATS]),      # consistency.py: the mirror consistency loss on pairs of logit maps
+)}
+
+
 def extensions():
     """``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS`` by name."""
     return {**EXTENSIONS, **OPTIMIZER_EXTENSIONS}
@@ -70,6 +77,11 @@ def extensions():
 def libraries():
     """Every extension library by name: ``extensions()`` and then ``PREDICTION_EXTENSIONS``."""
     return {**extensions(), **PREDICTION_EXTENSIONS}
+
+
+def every_library():
+    """Every extension library by name: ``libraries()`` and then ``TRAINING_EXTENSIONS``."""
+    return {**libraries(), **TRAINING_EXTENSIONS}
 
 
 def _stale(target, deps):
@@ -84,12 +96,12 @@ def _library_stale(lib, sources, headers):
 
 
 def extension_needs_build(name):
-    e = libraries()[name]
+    e = every_library()[name]
     return _library_stale(e.lib, e.sources, e.headers)
 
 
 def needs_build():
-    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in libraries())
+    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in every_library())
 
 
 def _run(cmd, verbose):
@@ -131,9 +143,9 @@ def build_diag(verbose=True):
 
 
 def build_extension(name, force=False, verbose=True):
-    """``libraries()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
+    """``every_library()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
     beside it at load time, $ORIGIN), which therefore has to exist."""
-    e = libraries()[name]
+    e = every_library()[name]
     if not force and not extension_needs_build(name):
         return e.lib
     return _library(e.lib, e.sources, OBJ, e.headers, [], ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], force, verbose)
@@ -143,7 +155,7 @@ def build(force=False, verbose=True):
     """The main library and every extension library, each only when it is stale; returns the main library's path."""
     if force or _library_stale(LIB, SOURCES, HEADERS):
         _build_main(force, verbose)
-    for name in libraries():
+    for name in every_library():
         build_extension(name, force, verbose)
     return LIB
 

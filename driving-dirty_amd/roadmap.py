@@ -15,6 +15,7 @@ from torch.nn import functional as F
 from . import mc as _mc
 from . import ops
 from . import tta as _tta
+from . import augment as _augment
 from .augment import Augmenter, add_augment_args, current_rank
 from .adamw import add_weight_decay_args
 from .ema import add_ema_args
@@ -184,6 +185,23 @@ def road_map_loss_parts(setting, logits, target):
     return loss, probs, (bce, ts)
 
 
+def cons_config(hparams):
+    """The mirror consistency loss as the hparams ask for it: None when it is off (``cons_weight`` 0 or absent), else
+    ``(cons_weight, cons_rampup_steps)`` as ``consistency.check_hparams`` gives them; a negative or non-finite weight or a negative ramp
+    raises ValueError here, when the module is built.  With both hparams 0 or absent ``consistency`` is not imported."""
+    if not hparam(hparams, "cons_weight", 0) and not hparam(hparams, "cons_rampup_steps", 0):
+        return None
+    from . import consistency      # here, not at the top: a model with the hparams off never imports it
+    weight, rampup_steps = consistency.check_hparams(hparams)
+    return (weight, rampup_steps) if weight > 0 else None
+
+
+def refuse_consistency(hparams, who, why):
+    """For the modules the consistency loss is not built into: ValueError by name when ``hparams.cons_weight`` > 0."""
+    if cons_config(hparams) is not None:
+        raise ValueError(f"cons_weight > 0 asks for the mirror consistency loss on unlabelled scenes; {who} {why}: use RoadMapBCE")
+
+
 class CalibratedThreshold:
     """What a module with a road-map head needs to calibrate its operating point on validation data (hparams.calibrate_threshold)
     and to carry it: the ``rm_threshold`` property, the per-batch histogram and the epoch's argmax.  Shared by the road-map modules
@@ -216,14 +234,29 @@ class CalibratedThreshold:
 
 
 class RoadMapBCE(CalibratedThreshold, LightningModule):
+    """``hparams.cons_weight`` > 0 (off by default): ``training_step`` also accepts ``(sample, target, road_image,
+    unlabelled)`` and adds ``cons_weight * ramp(t) * L_cons``, the mirror consistency loss (consistency.py) on the ``B_u`` unlabelled
+    scenes, to the supervised loss of the ``B_l`` labelled ones.  The step is ONE forward over ``N = B_l + 2 B_u`` rows -- the labelled
+    scenes, the unlabelled ones, their mirrors -- and one backward:
+      * ``B_l + 2 B_u <= 64`` keeps ``TrainStep``'s fast path: past 64 rows ``HipAdam.linear_factors`` declines the rank-B pass by itself
+        and the big Linear layers' gradients are materialised;
+      * the dense blocks' BatchNorm statistics are taken over all ``N`` rows, the unlabelled ones included;
+      * ``t`` counts the steps that carried an unlabelled part.  It is a plain attribute (``cons_step``), not checkpointed: a resumed
+        run restarts the ramp;
+      * the loss is per rank; under a live ``GradSync`` nothing new is needed, but it has not been run on more than one GPU.
+    A 3-tuple is a supervised-only step, the calls of a model without the hparams; a 4-tuple under ``cons_weight`` 0 raises ValueError.
+    Validation, prediction and calibration do not know about it."""
     rm_loss = None      # rm_loss_config(hparams): None = mean BCE-with-logits, the reference's loss
     _rm_parts = None    # (L_bce, L_ts) of the last ``_run_step`` under a setting
+    cons = None         # cons_config(hparams): None = off, else (cons_weight, cons_rampup_steps)
+    cons_step = 0       # steps so far that carried unlabelled scenes: the ramp's t
 
     def __init__(self, hparams):
         super().__init__()
         self.hparams = hparams
         self.rm_loss = rm_loss_config(hparams)
         _mc.check_hparams(hparams)
+        self.cons = cons_config(hparams)
         self.output_dim = 800 * 800
         # pretrained feature extractor (roadmap_bce_v2.py:43-47); ``pretrained_ae`` lets callers hand in
         # an already-built BasicAE when no checkpoint file exists (the reference's paths are NYU-local)
@@ -291,22 +324,26 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
             return predict_map(self, lambda: self._encode(x), threshold)
         return predict_map_tta(self, self._encode, x, threshold)
 
-    def _run_step(self, batch, batch_idx, step_name, keeps=(None, None)):
+    def _run_step(self, batch, batch_idx, step_name, keeps=(None, None), logits=None):
+        """``logits``: ``(sample, keeps) -> logits`` of the rows the loss is taken on, in place of ``self._logits`` (the step with an
+        unlabelled part: the first rows of a longer forward)."""
         sample, target, road_image = batch
+        if logits is None:
+            logits = self._logits
         logging = self.logger is not None and batch_idx % self.hparams.output_img_freq == 0
         per_sample = tuple(road_image)
         if (step_name == "train" and not logging and 0 < len(per_sample) <= ops.PTR_TABLE_MAX and
                 all(t.is_cuda and t.is_contiguous() and t.dtype in (torch.bool, torch.uint8) and t.numel() % 4 == 0 for t in per_sample)):
             # the training step only needs the masks inside the loss: the kernel reads them where the collate left them
             # (a pointer table) instead of torch.stack-ing them first (roadmap_bce_v2.py:87)
-            pred_rm = self._logits(sample, keeps)
+            pred_rm = logits(sample, keeps)
             b = len(per_sample)
             loss, probs = self._loss_and_probs(pred_rm.reshape(b, -1), per_sample)
             return loss, None, pred_rm, probs.reshape(b, 800, 800)
         masks = torch.stack(per_sample, dim=0)            # bool as the dataset hands them over (data_helper.py:137-139)
         # self(sample) of the reference = (logits, probabilities); here the probabilities come out of the loss kernel's pass
         # over the logits (same values as forward()'s), which saves reading the 82 MB of logits a second time
-        pred_rm = self._logits(sample, keeps)            # names as in the reference: pred_rm = logits, pred_logit_rm = probabilities
+        pred_rm = logits(sample, keeps)                  # names as in the reference: pred_rm = logits, pred_logit_rm = probabilities
         # the loss reads the bool masks as bytes; the fp32 copy (roadmap_bce_v2.py:87) is only made where it is looked at
         target_rm = masks.float() if (logging or step_name != "train" or masks.dtype.is_floating_point) else masks
         batch_size = masks.size(0)
@@ -336,9 +373,58 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         if self.current_epoch >= self.hparams.unfreeze_epoch_no and self.frozen:
             self.frozen = False
             self.ae.unfreeze()
+        if len(batch) == 4:
+            return self._consistency_step(batch, batch_idx)
         batch = self.augment.apply(batch)
         train_loss, _, _, _ = self._run_step(batch, batch_idx, step_name="train")
         log = {"train_loss": train_loss}
+        if self.rm_loss is not None:
+            log["rm_bce"], log["rm_soft_ts"] = self._rm_parts
+        return {"loss": train_loss, "log": log}
+
+    def _consistency_draw(self, b, mirror):
+        """One draw of the model's ``Augmenter`` for ``b`` unlabelled scenes with the mirror bit cleared or set; with the augmenter
+        disabled the identity colour and no other flag, and nothing is drawn from its generator."""
+        if self.augment.enabled:
+            flags, color = self.augment.draw(b)
+        else:
+            flags, color = torch.zeros(b, dtype=torch.int64), torch.tensor([1.0, 0.0]).repeat(b, 6, 1)
+        return (flags & ~_augment.FLAG_MIRROR) | (_augment.FLAG_MIRROR if mirror else 0), color
+
+    def _consistency_step(self, batch, batch_idx):
+        """The training step on ``(sample, target, road_image, unlabelled)`` (the class docstring): ``unlabelled`` is ``B_u`` scenes in any
+        form ``forward`` takes.  The labelled triple is augmented as in a supervised step; the unlabelled scenes become two stochastic
+        views, one with the rig mirrored; all ``N = B_l + 2 B_u`` rows go through ONE ``_logits`` call.  The supervised loss reads rows
+        ``[:B_l]``, ``MirrorConsistency`` rows ``[B_l:]``.  The log gains ``cons_loss``, ``cons_disagree`` -- the share of the unlabelled
+        maps' pixels on which the two views fall on different sides of logit 0 -- and ``cons_weight_now``."""
+        if self.cons is None:
+            raise ValueError("RoadMapBCE.training_step: the batch carries unlabelled scenes (a 4-tuple) but hparams.cons_weight is 0 or absent")
+        from . import consistency
+        weight, rampup_steps = self.cons
+        sample, target, road_image = self.augment.apply(tuple(batch[:3]))
+        unlabelled = batch[3]
+        b_u = unlabelled.shape[0] if isinstance(unlabelled, torch.Tensor) else len(unlabelled)
+        views = _augment.augment_views(unlabelled, *self._consistency_draw(b_u, mirror=False))
+        mirrored = _augment.augment_views(unlabelled, *self._consistency_draw(b_u, mirror=True))
+        if ops.is_u8_frames(sample):      # one dtype for ops.sample_table: the identity draw moves a frame's values as the gather does
+            b_l = sample.shape[0] if isinstance(sample, torch.Tensor) else len(sample)
+            sample = _augment.augment_views(sample, torch.zeros(b_l, dtype=torch.int64), torch.tensor([1.0, 0.0]).repeat(b_l, 6, 1))
+        rows = tuple(sample) + tuple(views) + tuple(mirrored)      # N per-sample fp32 [6,3,H,W]
+        b_l = len(rows) - 2 * b_u
+        rest = []
+
+        def labelled_logits(x, keeps):
+            z = self._logits(x, keeps)
+            rest.append(z[b_l:])
+            return z[:b_l]
+
+        sup_loss, _, _, _ = self._run_step((rows, target, road_image), batch_idx, step_name="train", logits=labelled_logits)
+        cons_loss, stats = consistency.mirror_consistency(rest[0], return_stats=True)
+        now = weight * consistency.ramp(self.cons_step, rampup_steps)
+        self.cons_step += 1
+        train_loss = sup_loss + now * cons_loss
+        log = {"train_loss": train_loss, "cons_loss": cons_loss.detach(), "cons_disagree": stats[:, 1].sum() / (b_u * rest[0][0].numel()),
+               "cons_weight_now": now}
         if self.rm_loss is not None:
             log["rm_bce"], log["rm_soft_ts"] = self._rm_parts
         return {"loss": train_loss, "log": log}
@@ -410,6 +496,7 @@ class RoadMap(RoadMapBCE):
         if self.rm_loss is not None:
             raise ValueError("rm_pos_weight / rm_bce_weight / rm_ts_weight select a loss on the road-map head's logits; RoadMap (roadmap_mse) "
                              "trains on the MSE of its probabilities: use RoadMapBCE")
+        refuse_consistency(hparams, "RoadMap (roadmap_mse)", "takes its loss from the probabilities and has no step for them")
 
     def forward(self, x, keeps=(None, None)):
         """-> sigmoid(Linear(z)) [B,800,800], differentiable (roadmap_pretrain_ae.py:67-82)."""
