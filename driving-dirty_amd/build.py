@@ -9,9 +9,10 @@ header is newer) and the objects are linked into their library.  An extension li
 ``include/dd_hotpath.h`` (its set of functions is pinned): a header and sources of its own, the main library's flags, linked against
 the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS``, or -- a library of
 the optimizer -- of ``OPTIMIZER_EXTENSIONS``, or -- a library of the prediction path -- of ``PREDICTION_EXTENSIONS``, or -- a library of a
-training loss that is off by default -- of ``TRAINING_EXTENSIONS``; the module that binds it holds a ``_lib.Extension`` of that entry.
-``extensions()`` is the first two tables as one mapping, ``libraries()`` the first three, ``every_library()`` all four: what is built, and
-what every function here that takes an extension's name looks it up in.
+training loss that is off by default -- of ``TRAINING_EXTENSIONS``, or -- the bootstrapped road-map loss -- of ``BOOTSTRAP_EXTENSIONS``; the
+module that binds it holds a ``_lib.Extension`` of that entry.  ``extensions()`` is the first two tables as one mapping, ``libraries()`` the
+first three, ``every_library()`` the first four, ``all_libraries()`` all five: what is built, and what every function here that takes an
+extension's name looks it up in.
 """
 import os
 import subprocess
@@ -31,7 +32,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 EXTRA_FLAGS = {"adam_rankb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 HEADER = os.path.join(INCLUDE, "dd_hotpath.h")      # the C ABI; _lib.py derives its ctypes table from it
 _COMMON = [os.path.join(CSRC, "dd_common.h"), os.path.join(CSRC, "dd_device.h")]
-_LOSS_STATS = os.path.join(CSRC, "dd_loss_stats.h")      # the device code box_loss.hip, rm_loss.hip and consistency.hip share
+_LOSS_STATS = os.path.join(CSRC, "dd_loss_stats.h")      # the device code box_loss.hip, rm_loss.hip, consistency.hip and topk_loss.hip share
 HEADERS = _COMMON + [os.path.join(CSRC, "dd_adam.h"), os.path.join(CSRC, "dd_conv_strip.h"), os.path.join(CSRC, "conv_wino.inc"), os.path.join(CSRC, "conv_wino2.inc"), os.path.join(CSRC, "adam_rankb_kernels.inc"), _LOSS_STATS, HEADER]
 
 # An extension library.  ``lib``: the .so; ``sources``: under csrc/; ``header``: its public header, from which the binder derives its
@@ -44,7 +45,7 @@ def _extension(name, sources, what, internal=()):
     return Extension(name, os.path.join(CSRC, f"libdd_{name}.so"), sources, header, _COMMON + list(internal) + [HEADER, header], what)
 
 
-# To add an extension: a header, a source, one entry in one of the four tables below, a module that holds a ``_lib.Extension`` of the entry.
+# To add an extension: a header, a source, one entry in one of the five tables below, a module that holds a ``_lib.Extension`` of the entry.
 EXTENSIONS = {e.name: e for e in (
     _extension("augment", ["augment.hip"], "the augmentation"),                      # augment.py: the train-time augmentation
     _extension("tta", ["tta.hip"], "mirror test-time averaging"),                    # tta.py
@@ -69,6 +70,12 @@ TRAINING_EXTENSIONS = {e.name: e for e in (
 )}
 
 
+# The library of the bootstrapped road-map loss, off by default: the same kind of entry, the same rules, a table of its own.
+BOOTSTRAP_EXTENSIONS = {e.name: e for e in (
+    _extension("topk_loss", ["topk_loss.hip"], "the bootstrapped road-map loss", [_LOSS_STATS]),      # topk_loss.py: BCE over each sample's K hardest pixels
+)}
+
+
 def extensions():
     """``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS`` by name."""
     return {**EXTENSIONS, **OPTIMIZER_EXTENSIONS}
@@ -84,6 +91,11 @@ def every_library():
     return {**libraries(), **TRAINING_EXTENSIONS}
 
 
+def all_libraries():
+    """Every extension library by name: ``every_library()`` and then ``BOOTSTRAP_EXTENSIONS``."""
+    return {**every_library(), **BOOTSTRAP_EXTENSIONS}
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -96,12 +108,12 @@ def _library_stale(lib, sources, headers):
 
 
 def extension_needs_build(name):
-    e = every_library()[name]
+    e = all_libraries()[name]
     return _library_stale(e.lib, e.sources, e.headers)
 
 
 def needs_build():
-    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in every_library())
+    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in all_libraries())
 
 
 def _run(cmd, verbose):
@@ -143,9 +155,9 @@ def build_diag(verbose=True):
 
 
 def build_extension(name, force=False, verbose=True):
-    """``every_library()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
+    """``all_libraries()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
     beside it at load time, $ORIGIN), which therefore has to exist."""
-    e = every_library()[name]
+    e = all_libraries()[name]
     if not force and not extension_needs_build(name):
         return e.lib
     return _library(e.lib, e.sources, OBJ, e.headers, [], ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], force, verbose)
@@ -155,7 +167,7 @@ def build(force=False, verbose=True):
     """The main library and every extension library, each only when it is stale; returns the main library's path."""
     if force or _library_stale(LIB, SOURCES, HEADERS):
         _build_main(force, verbose)
-    for name in every_library():
+    for name in all_libraries():
         build_extension(name, force, verbose)
     return LIB
 

@@ -28,7 +28,7 @@ from .ema import add_ema_args
 from .autoencoder import BasicAE
 from .lightning import LightningModule, hparam, pretrained_ae
 from .roadmap import (MC_ROAD_KEYS, RM_LOSS_KEYS, TTA_ROAD_KEYS, CalibratedThreshold, add_rm_loss_args, eval_no_grad, mc_validation_probs,
-                      predict_map, predict_map_mc, predict_map_tta, prediction_threshold, refuse_consistency, rm_loss_config, road_map_loss_parts,
+                      predict_map, predict_map_mc, predict_map_tta, prediction_threshold, refuse_consistency, refuse_topk, rm_loss_config, road_map_loss_parts,
                       road_map_scores, tta_road_map_scores)
 from .spatial import (HALF_UNLESS_CALIBRATED, ONE_UNLESS_CONFIGURED, CalibratedBoxThreshold, RoadMapBoxesMergingCNN, SpatialMappingCNN,
                       add_box_args, bb_coord_to_map, box_decode_point, box_loss_config, boxes_from_map, decoded_box_ats, mean_logs,
@@ -60,6 +60,7 @@ class JointRoadMapBBox(CalibratedThreshold, CalibratedBoxThreshold, LightningMod
         self.rm_loss = rm_loss_config(hparams)        # None: mean BCE-with-logits (roadmap_bce_v2.py:106)
         _mc.check_hparams(hparams)                    # mc_samples / mc_seed: the road map from S dropout draws of the tail (mc.py)
         refuse_consistency(hparams, "JointRoadMapBBox", "has a box branch that needs labels for every scene of the batch")
+        refuse_topk(hparams, "JointRoadMapBBox", "takes its road-map loss in a step of its own, into which the selection is not built")
         self.box_rm_input = hparam(hparams, "box_rm_input", "target")
         if self.box_rm_input not in ("target", "predicted"):
             raise ValueError(f"box_rm_input must be 'target' or 'predicted', got {self.box_rm_input!r}")

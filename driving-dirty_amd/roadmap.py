@@ -202,6 +202,25 @@ def refuse_consistency(hparams, who, why):
         raise ValueError(f"cons_weight > 0 asks for the mirror consistency loss on unlabelled scenes; {who} {why}: use RoadMapBCE")
 
 
+def topk_config(hparams):
+    """The bootstrapped road-map loss as the hparams ask for it: None when it is off (``rm_topk_frac`` 1 or absent), else
+    ``(rm_topk_frac, rm_topk_warmup_steps)`` as ``topk_loss.check_hparams`` gives them; a fraction outside (0, 1] or a negative warm-up
+    raises ValueError here, when the module is built.  With the fraction 1 or absent and no warm-up ``topk_loss`` is not imported."""
+    frac = hparam(hparams, "rm_topk_frac", None)
+    if (frac is None or (not isinstance(frac, bool) and isinstance(frac, (int, float)) and frac == 1)) and not hparam(hparams, "rm_topk_warmup_steps", 0):
+        return None
+    from . import topk_loss      # here, not at the top: a model with the hparams off never imports it
+    frac, warmup_steps = topk_loss.check_hparams(hparams)
+    return (frac, warmup_steps) if frac < 1 else None
+
+
+def refuse_topk(hparams, who, why):
+    """For the modules the bootstrapped loss is not built into: ValueError by name when ``hparams.rm_topk_frac`` < 1."""
+    if topk_config(hparams) is not None:
+        raise ValueError(f"rm_topk_frac < 1 asks for the BCE over each scene's hardest pixels, a loss on the road-map head's logits; {who} {why}: "
+                         "use RoadMapBCE")
+
+
 class CalibratedThreshold:
     """What a module with a road-map head needs to calibrate its operating point on validation data (hparams.calibrate_threshold)
     and to carry it: the ``rm_threshold`` property, the per-batch histogram and the epoch's argmax.  Shared by the road-map modules
@@ -245,11 +264,22 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         run restarts the ramp;
       * the loss is per rank; under a live ``GradSync`` nothing new is needed, but it has not been run on more than one GPU.
     A 3-tuple is a supervised-only step, the calls of a model without the hparams; a 4-tuple under ``cons_weight`` 0 raises ValueError.
-    Validation, prediction and calibration do not know about it."""
+    Validation, prediction and calibration do not know about it.
+
+    ``hparams.rm_topk_frac`` < 1 (off by default): the TRAINING step's loss is the BCE averaged over each scene's K hardest
+    pixels (topk_loss.py), ``K = keep_now(rm_topk_frac, rm_topk_warmup_steps, t, 640000)`` falling from all pixels to the fraction over
+    the warm-up.  ``t`` counts the training steps taken under the setting, a plain attribute (``topk_step``), not checkpointed: a resumed
+    run restarts the anneal.  The log gains ``rm_bce_all`` (the plain mean BCE of the same pass), ``rm_topk_kept`` (the share of pixels
+    kept) and ``rm_topk_tau`` (the mean threshold margin).  Validation, prediction and calibration keep the mean BCE: ``val_loss`` stays
+    comparable between runs with and without the setting.  Together with an ``rm_*`` setting it raises ValueError; with ``cons_weight``
+    it composes: the supervised rows of the longer forward take this loss."""
     rm_loss = None      # rm_loss_config(hparams): None = mean BCE-with-logits, the reference's loss
     _rm_parts = None    # (L_bce, L_ts) of the last ``_run_step`` under a setting
     cons = None         # cons_config(hparams): None = off, else (cons_weight, cons_rampup_steps)
     cons_step = 0       # steps so far that carried unlabelled scenes: the ramp's t
+    topk = None         # topk_config(hparams): None = off, else (rm_topk_frac, rm_topk_warmup_steps)
+    topk_step = 0       # training steps so far under ``topk``: the anneal's t
+    _topk_parts = None  # (rm_bce_all, rm_topk_kept, rm_topk_tau) of the last training step under ``topk``
 
     def __init__(self, hparams):
         super().__init__()
@@ -257,6 +287,10 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         self.rm_loss = rm_loss_config(hparams)
         _mc.check_hparams(hparams)
         self.cons = cons_config(hparams)
+        self.topk = topk_config(hparams)
+        if self.topk is not None and self.rm_loss is not None:
+            raise ValueError("rm_topk_frac < 1 selects the BCE over each scene's hardest pixels; rm_pos_weight / rm_bce_weight / rm_ts_weight "
+                             "select another loss on the same logits, and the combination is not built: set one of the two")
         self.output_dim = 800 * 800
         # pretrained feature extractor (roadmap_bce_v2.py:43-47); ``pretrained_ae`` lets callers hand in
         # an already-built BasicAE when no checkpoint file exists (the reference's paths are NYU-local)
@@ -338,7 +372,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
             # (a pointer table) instead of torch.stack-ing them first (roadmap_bce_v2.py:87)
             pred_rm = logits(sample, keeps)
             b = len(per_sample)
-            loss, probs = self._loss_and_probs(pred_rm.reshape(b, -1), per_sample)
+            loss, probs = self._loss_and_probs(pred_rm.reshape(b, -1), per_sample, train=True)
             return loss, None, pred_rm, probs.reshape(b, 800, 800)
         masks = torch.stack(per_sample, dim=0)            # bool as the dataset hands them over (data_helper.py:137-139)
         # self(sample) of the reference = (logits, probabilities); here the probabilities come out of the loss kernel's pass
@@ -348,19 +382,38 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         target_rm = masks.float() if (logging or step_name != "train" or masks.dtype.is_floating_point) else masks
         batch_size = masks.size(0)
         loss_target = masks if masks.dtype in (torch.bool, torch.uint8) else target_rm
-        loss, probs = self._loss_and_probs(pred_rm.reshape(batch_size, -1), loss_target.reshape(batch_size, -1).contiguous())
+        loss, probs = self._loss_and_probs(pred_rm.reshape(batch_size, -1), loss_target.reshape(batch_size, -1).contiguous(),
+                                           train=step_name == "train")
         pred_logit_rm = probs.reshape(batch_size, 800, 800)
         if logging:
             self._log_rm_images(self.wide_stitch_six_images(sample), target_rm, pred_logit_rm, step_name)
         return loss, target_rm, pred_rm, pred_logit_rm
 
-    def _loss_and_probs(self, logits, target):
+    def _loss_and_probs(self, logits, target, train=False):
         """(loss, sigmoid(logits)) of ``logits`` [B, P] from one pass: the reference's mean BCE-with-logits, or under an ``rm_*`` setting
-        (``rm_loss_config``) the weighted BCE + soft threat score, whose two components are then kept in ``_rm_parts``."""
+        (``rm_loss_config``) the weighted BCE + soft threat score, whose two components are then kept in ``_rm_parts``; on the training
+        step (``train``) under ``rm_topk_frac`` < 1 the BCE over each sample's K hardest pixels, whose figures are kept in ``_topk_parts``."""
+        if train and self.topk is not None:
+            return self._topk_loss_and_probs(logits, target)
         if self.rm_loss is None:
             return ops.BceWithLogitsProbs.apply(logits, target)
         loss, probs, self._rm_parts = road_map_loss_parts(self.rm_loss, logits, target)
         return loss, probs
+
+    def _topk_loss_and_probs(self, logits, target):
+        from . import topk_loss      # here, not at the top: a model with the setting off never imports or loads the library
+        frac, warmup_steps = self.topk
+        b, per = logits.shape
+        keep = topk_loss.keep_now(frac, warmup_steps, self.topk_step, per)
+        self.topk_step += 1
+        loss, probs, stats = topk_loss.topk_bce(logits, target, keep)
+        self._topk_parts = ((stats[:, 3].sum() / (b * per)).float(), (stats[:, 0].sum() / (b * per)).float(), stats[:, 2].mean().float())
+        return loss, probs
+
+    def _log_topk(self, log):
+        if self.topk is not None:
+            log["rm_bce_all"], log["rm_topk_kept"], log["rm_topk_tau"] = self._topk_parts
+        return log
 
     def _log_rm_images(self, x, target_rm, pred_rm, step_name, limit=1):
         exp = self.logger.experiment
@@ -380,7 +433,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         log = {"train_loss": train_loss}
         if self.rm_loss is not None:
             log["rm_bce"], log["rm_soft_ts"] = self._rm_parts
-        return {"loss": train_loss, "log": log}
+        return {"loss": train_loss, "log": self._log_topk(log)}
 
     def _consistency_draw(self, b, mirror):
         """One draw of the model's ``Augmenter`` for ``b`` unlabelled scenes with the mirror bit cleared or set; with the augmenter
@@ -427,7 +480,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
                "cons_weight_now": now}
         if self.rm_loss is not None:
             log["rm_bce"], log["rm_soft_ts"] = self._rm_parts
-        return {"loss": train_loss, "log": log}
+        return {"loss": train_loss, "log": self._log_topk(log)}
 
     def validation_step(self, batch, batch_idx):
         """Under ``hparams.tta_mirror`` also a mirrored pass (``no_grad``) and ``val_ts_tta`` / ``val_ts_rounded_tta``, the scores of the
@@ -497,6 +550,7 @@ class RoadMap(RoadMapBCE):
             raise ValueError("rm_pos_weight / rm_bce_weight / rm_ts_weight select a loss on the road-map head's logits; RoadMap (roadmap_mse) "
                              "trains on the MSE of its probabilities: use RoadMapBCE")
         refuse_consistency(hparams, "RoadMap (roadmap_mse)", "takes its loss from the probabilities and has no step for them")
+        refuse_topk(hparams, "RoadMap (roadmap_mse)", "trains on the MSE of its probabilities")
 
     def forward(self, x, keeps=(None, None)):
         """-> sigmoid(Linear(z)) [B,800,800], differentiable (roadmap_pretrain_ae.py:67-82)."""
