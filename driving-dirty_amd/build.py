@@ -9,10 +9,11 @@ header is newer) and the objects are linked into their library.  An extension li
 ``include/dd_hotpath.h`` (its set of functions is pinned): a header and sources of its own, the main library's flags, linked against
 the main library, whose ``dd_fail`` / ``dd_last_error`` it uses.  It is declared ONCE, as an entry of ``EXTENSIONS``, or -- a library of
 the optimizer -- of ``OPTIMIZER_EXTENSIONS``, or -- a library of the prediction path -- of ``PREDICTION_EXTENSIONS``, or -- a library of a
-training loss that is off by default -- of ``TRAINING_EXTENSIONS``, or -- the bootstrapped road-map loss -- of ``BOOTSTRAP_EXTENSIONS``; the
-module that binds it holds a ``_lib.Extension`` of that entry.  ``extensions()`` is the first two tables as one mapping, ``libraries()`` the
-first three, ``every_library()`` the first four, ``all_libraries()`` all five: what is built, and what every function here that takes an
-extension's name looks it up in.
+training loss that is off by default -- of ``TRAINING_EXTENSIONS``, or -- the bootstrapped road-map loss -- of ``BOOTSTRAP_EXTENSIONS``, or --
+the sampled head's uncertainty -- of ``UNCERTAINTY_EXTENSIONS``; the module that binds it holds a ``_lib.Extension`` of that entry.
+``extensions()`` is the first two tables as one mapping, ``libraries()`` the first three, ``every_library()`` the first four,
+``all_libraries()`` the first five, ``built_libraries()`` all six: what is built, and what every function here that takes an extension's
+name looks it up in.
 """
 import os
 import subprocess
@@ -45,7 +46,7 @@ def _extension(name, sources, what, internal=()):
     return Extension(name, os.path.join(CSRC, f"libdd_{name}.so"), sources, header, _COMMON + list(internal) + [HEADER, header], what)
 
 
-# To add an extension: a header, a source, one entry in one of the five tables below, a module that holds a ``_lib.Extension`` of the entry.
+# To add an extension: a header, a source, one entry in one of the six tables below, a module that holds a ``_lib.Extension`` of the entry.
 EXTENSIONS = {e.name: e for e in (
     _extension("augment", ["augment.hip"], "the augmentation"),                      # augment.py: the train-time augmentation
     _extension("tta", ["tta.hip"], "mirror test-time averaging"),                    # tta.py
@@ -76,6 +77,12 @@ BOOTSTRAP_EXTENSIONS = {e.name: e for e in (
 )}
 
 
+# The library of the sampled head's uncertainty, off by default: the same kind of entry, the same rules, a table of its own.
+UNCERTAINTY_EXTENSIONS = {e.name: e for e in (
+    _extension("head_uncert", ["head_uncert.hip"], "the sampled head's uncertainty"),      # uncertainty.py: entropy, mutual information and variance of the S draws
+)}
+
+
 def extensions():
     """``EXTENSIONS`` and then ``OPTIMIZER_EXTENSIONS`` by name."""
     return {**EXTENSIONS, **OPTIMIZER_EXTENSIONS}
@@ -96,6 +103,11 @@ def all_libraries():
     return {**every_library(), **BOOTSTRAP_EXTENSIONS}
 
 
+def built_libraries():
+    """Every extension library by name: ``all_libraries()`` and then ``UNCERTAINTY_EXTENSIONS``."""
+    return {**all_libraries(), **UNCERTAINTY_EXTENSIONS}
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -108,12 +120,12 @@ def _library_stale(lib, sources, headers):
 
 
 def extension_needs_build(name):
-    e = all_libraries()[name]
+    e = built_libraries()[name]
     return _library_stale(e.lib, e.sources, e.headers)
 
 
 def needs_build():
-    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in all_libraries())
+    return _library_stale(LIB, SOURCES, HEADERS) or any(extension_needs_build(name) for name in built_libraries())
 
 
 def _run(cmd, verbose):
@@ -155,9 +167,9 @@ def build_diag(verbose=True):
 
 
 def build_extension(name, force=False, verbose=True):
-    """``all_libraries()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
+    """``built_libraries()[name].lib`` from its sources, when it is stale: the main library's flags; linked against ``libdd_hotpath.so`` (found
     beside it at load time, $ORIGIN), which therefore has to exist."""
-    e = all_libraries()[name]
+    e = built_libraries()[name]
     if not force and not extension_needs_build(name):
         return e.lib
     return _library(e.lib, e.sources, OBJ, e.headers, [], ["-L" + CSRC, "-l:" + os.path.basename(LIB), "-Wl,-rpath,$ORIGIN"], force, verbose)
@@ -167,7 +179,7 @@ def build(force=False, verbose=True):
     """The main library and every extension library, each only when it is stale; returns the main library's path."""
     if force or _library_stale(LIB, SOURCES, HEADERS):
         _build_main(force, verbose)
-    for name in all_libraries():
+    for name in built_libraries():
         build_extension(name, force, verbose)
     return LIB
 

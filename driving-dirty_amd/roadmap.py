@@ -94,6 +94,7 @@ def mc_road_map_scores(out, target_rm, avg_probs):
 
 
 MC_ROAD_KEYS = ("val_ts_mc", "val_ts_rounded_mc")
+VAL_UNCERTAINTY_KEYS = ("val_mc_entropy", "val_mc_mi", "val_mc_var")      # uncertainty.VAL_KEYS, under hparams.mc_uncertainty
 
 
 def tta_road_map_scores(out, target_rm, avg_probs):
@@ -118,6 +119,15 @@ def mc_validation_probs(module, out, target_rm, mc_probs, sample, samples, mode)
             avg = _tta.mean_prob(avg, mc_probs(_tta.mirror_views(sample), samples, gen), False)
             tta_road_map_scores(out, target_rm, avg)
     return avg
+
+
+def mc_uncertainty_config(hparams):
+    """``hparams.mc_uncertainty`` (off by default): False without importing ``uncertainty`` when the hparam is absent or
+    false; anything but a bool raises ValueError here, when the module is built."""
+    if hparam(hparams, "mc_uncertainty", False) is False:
+        return False
+    from . import uncertainty      # here, not at the top: a model with the flag off never imports it
+    return uncertainty.enabled(hparams)
 
 
 def compute_ts_road_map(road_map1, road_map2):
@@ -286,6 +296,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         self.hparams = hparams
         self.rm_loss = rm_loss_config(hparams)
         _mc.check_hparams(hparams)
+        mc_uncertainty_config(hparams)
         self.cons = cons_config(hparams)
         self.topk = topk_config(hparams)
         if self.topk is not None and self.rm_loss is not None:
@@ -334,6 +345,40 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
     def _mc_probs(self, sample, samples, gen):
         """Probabilities [B,800,800] averaged over ``samples`` dropout draws per scene, masks from ``gen``; for ``eval_no_grad``."""
         return _mc.head_mean_prob(self, self.ae.encoder, self._pooled(sample), samples, gen)
+
+    def _mc_probs_scored(self, out):
+        """``_mc_probs`` for the validation step under ``hparams.mc_uncertainty``: the same draws through ``dd_head_uncert`` with ``mean``
+        requested -- the bits of ``mc.mean_prob`` -- and the batch means of the three per-scene scores into ``out``."""
+        from . import uncertainty
+
+        def probs(sample, samples, gen):
+            got = uncertainty.predict(self, self.ae.encoder, self._pooled(sample), samples, gen, maps=("mean",), scores=True)
+            if VAL_UNCERTAINTY_KEYS[0] not in out:      # the first pass: under the mirror mode the mirrored batch's scores are not reported
+                uncertainty.validation_scores(out, got.scores)
+            return got.mean
+        return probs
+
+    def predict_uncertainty(self, x, mc_samples=None, maps=("mi",), scores=True):
+        """Where the model is unsure about ``x`` (whatever ``forward`` takes), from the spread of ``mc_samples`` dropout draws of the
+        encoder's tail per scene (uncertainty.py) -> a named tuple of the requested ``maps`` -- chosen from "mean",
+        "entropy", "mi", "var", fp32 [B,800,800] each -- and, under ``scores``, ``scores``: fp64 [B,3], each scene's mean entropy, mean
+        mutual information and mean variance over its pixels.  In nats.  ``mi``, the mutual information between prediction and
+        weights (BALD), is large where the draws disagree; ``entropy`` is also large where every draw says 0.5.
+
+        The path is ``predict_road_map``'s under S > 1: eval mode, ``no_grad``, the module's own generator reseeded from
+        ``hparams.mc_seed`` (the same call gives the same bits; torch's global generators are not touched), the conv stack and ``fc1``'s
+        Linear once, S draws of the tail, and ONE pass of the head, in which the statistics are taken: the draws of a call of
+        ``predict_road_map(x, mc_samples=S)`` are these draws, and "mean" is its mean.  ``mc_samples``: None = ``hparams.mc_samples``; a
+        resolved S < 2 raises ValueError (one draw has no spread).  ``hparams.tta_mirror`` is ignored: the statistics are those of the
+        unmirrored scene's draws."""
+        samples = _mc.resolve(self, mc_samples)
+        if samples < 2:
+            raise ValueError(f"predict_uncertainty: mc_samples must be at least 2 (the spread of one draw is zero), got {samples}: pass "
+                             "mc_samples= or set hparams.mc_samples")
+        from . import uncertainty      # here, not at the top: a model that is never asked never imports or loads the library
+        with eval_no_grad(self):
+            gen = _mc.generator(self, self.fc1.weight.device)
+            return uncertainty.predict(self, self.ae.encoder, self._pooled(x), samples, gen, maps, scores)
 
     def predict_road_map(self, x, threshold=None, mc_samples=None, tta=None):
         """The reference's "Predicting test images" step (run_test.py) for one batch: torch.bool [B,800,800], equal to ``forward``'s
@@ -493,12 +538,16 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         (generator reseeded from ``hparams.mc_seed``), and ``val_ts_mc`` / ``val_ts_rounded_mc``, the scores of the S-draw mean.  With
         ``hparams.tta_mirror`` as well, a mirrored pass of the same kind joins it and ``val_ts_tta`` / ``val_ts_rounded_tta`` are taken
         from the mean of the two S-draw means: what ``predict_road_map`` thresholds in that mode.  ``ts_hist`` reads the most-averaged
-        probabilities."""
+        probabilities.  With ``hparams.mc_uncertainty`` on top the same head pass also yields ``val_mc_entropy`` /
+        ``val_mc_mi`` / ``val_mc_var``: the batch means of the scenes' mean predictive entropy, mutual information and variance of the
+        draws (the unmirrored batch's); ``val_ts_mc`` keeps its bits."""
         val_loss, target_rm, pred_rm, pred_logit_rm = self._run_step(batch, batch_idx, step_name="valid")
         out = {"val_loss": val_loss, **road_map_scores(target_rm, pred_logit_rm)}
         if self.rm_loss is not None:
             out["val_rm_bce"], out["val_rm_soft_ts"] = self._rm_parts
         samples, mode = _mc.resolve(self, None), _tta.resolve(self, None)
+        if samples > 1 and mc_uncertainty_config(self.hparams):
+            return self._with_ts_hist(out, mc_validation_probs(self, out, target_rm, self._mc_probs_scored(out), batch[0], samples, mode), target_rm)
         if samples > 1:
             return self._with_ts_hist(out, mc_validation_probs(self, out, target_rm, self._mc_probs, batch[0], samples, mode), target_rm)
         if mode is None:
@@ -510,7 +559,7 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
     def validation_epoch_end(self, outputs):
         avg = {k: torch.stack([x[k] for x in outputs]).mean() for k in ("val_loss", "val_ts", "val_ts_rounded")}
         logs = {"avg_val_loss": avg["val_loss"], "avg_val_ts_rounded": avg["val_ts_rounded"], "avg_val_ts": avg["val_ts"]}
-        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS + MC_ROAD_KEYS + RM_LOSS_KEYS
+        logs.update({"avg_" + k: torch.stack([x[k] for x in outputs]).mean() for k in TTA_ROAD_KEYS + MC_ROAD_KEYS + RM_LOSS_KEYS + VAL_UNCERTAINTY_KEYS
                      if outputs and all(k in x for x in outputs)})
         self._calibrate(outputs, logs)
         return {"val_loss": avg["val_loss"], "log": logs}
@@ -540,6 +589,17 @@ class RoadMapBCE(CalibratedThreshold, LightningModule):
         return p
 
 
+class NotInherited:
+    """A class attribute that takes a base class's method out of a subclass: looking ``name`` up on the subclass or on an instance of it
+    raises AttributeError, as if it had never been there."""
+
+    def __init__(self, name, owner):
+        self.name, self.owner = name, owner
+
+    def __get__(self, obj, cls):
+        raise AttributeError(f"{cls.__name__} has no {self.name}: it is {self.owner}'s alone")
+
+
 class RoadMap(RoadMapBCE):
     """MSE twin (roadmap_pretrain_ae.py): sigmoid inside ``forward``, ``mse_loss(target, pred)``, unfreeze at epoch 30.  Its loss is taken
     from the probabilities: the ``rm_*`` hparams select a loss on logits and are refused."""
@@ -551,6 +611,10 @@ class RoadMap(RoadMapBCE):
                              "trains on the MSE of its probabilities: use RoadMapBCE")
         refuse_consistency(hparams, "RoadMap (roadmap_mse)", "takes its loss from the probabilities and has no step for them")
         refuse_topk(hparams, "RoadMap (roadmap_mse)", "trains on the MSE of its probabilities")
+        if mc_uncertainty_config(hparams):
+            raise ValueError("mc_uncertainty asks for the draws' spread in validation, which is built into RoadMapBCE only: use RoadMapBCE")
+
+    predict_uncertainty = NotInherited("predict_uncertainty", "RoadMapBCE")      # the uncertainty outputs are RoadMapBCE's alone
 
     def forward(self, x, keeps=(None, None)):
         """-> sigmoid(Linear(z)) [B,800,800], differentiable (roadmap_pretrain_ae.py:67-82)."""
