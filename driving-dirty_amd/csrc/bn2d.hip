@@ -1,9 +1,9 @@
 // BatchNorm2d pieces of the Conv -> BN2d -> ReLU encoder variant (reference src/autoencoder/components_v2.py:19-24,
 // 43-46; its `bn3 = nn.Conv2d(32)` is read as the evident `BatchNorm2d(32)`).
 //
-// The conv kernels (conv3x3.hip) write the PRE-normalisation tensor u and gather per-wave-lane sum / sum-of-squares
-// in their epilogue (lane = channel there, so no cross-lane traffic).  Here:
-//   bn2d_finalize     partials -> batch mean / inv-std (fp64), running statistics, and the (scale, shift) table the
+// The conv kernels (conv3x3.hip) write the PRE-normalisation tensor u and gather per-wave-lane moments about a pivot
+// in their epilogue (lane = channel there, so no cross-lane traffic in the loop).  Here:
+//   bn2d_finalize     per-producer (n, mean, M2) -> batch mean / inv-std (fp64), running statistics, and the (scale, shift) table the
 //                     consumers apply on the fly:  y = relu(u*scale + shift)
 //   bn2d_apply_relu   materialise y (only for the c3_only exit, where the caller wants the tensor)
 //   bn2d_bwd_reduce   dbeta = sum g, dgamma = sum g*xhat per channel: registers -> wavefront shuffles -> LDS -> partials
@@ -15,6 +15,15 @@ namespace {
 
 constexpr int kStatRows = DD_NUM_CU * 2 * 8;   // wave slots of dd_conv_fwd_stats (dd_conv_stats_floats / 128)
 
+// The statistics table: kStatRows rows of 128 floats, one per wave of dd_conv_fwd_stats or per workgroup of dd_bn2d_stats, holding what
+// that producer saw of each channel c: [c] = n (a count), [32 + c] + [96 + c] = mean (as fp32 and what fp32 rounds away of it),
+// [64 + c] = M2 = sum((v - mean)^2); the rows of idle producers are zero (n = 0).  The producers gather moments about a pivot
+// (DdMoments, dd_device.h), so a row's M2 carries the rounding of terms of the size of the channel's SPREAD, whatever its offset.
+// (Raw fp32 sums of v and v^2 round every v^2 at the size of mean^2, however exactly q/n - m^2 is then formed: measured on an MI355X
+// against fp64, inv-std came out 5e-5 .. 4e-4 wrong at |mean| = 64 sigma and 2e-3 .. 2e-2 at 512 sigma; tests/test_gpu_bn2d.py.)
+// Rows merge by Chan's formula, all at once and in fp64: with d_r = mean_r - P about ANY common P (row 0's mean here, so that the
+// d_r are of the size of the spread), mean = P + sum(n_r d_r) / N and M2 = sum(M2_r) + sum(n_r d_r^2) - (sum(n_r d_r))^2 / N.
+//
 // table layout handed to the conv kernels: [0:32) input scale, [32:64) input shift, [64:96) mask scale, [96:128) mask shift
 __global__ __launch_bounds__(256) void bn2d_finalize_kernel(const float* __restrict__ stats, double count,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -24,12 +33,15 @@ __global__ __launch_bounds__(256) void bn2d_finalize_kernel(const float* __restr
                                                             float* __restrict__ save_invstd) {
   __shared__ double red[8][32][2];
   const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const double piv = training ? (double)stats[32 + c] + (double)stats[96 + c] : 0.0;
   double s = 0.0, q = 0.0;
   if (training) {
-    for (int w = g; w < kStatRows; w += 8) {
+#pragma unroll 8
+    for (int w = g; w < kStatRows; w += 8) {      // 512 rows per thread: unrolled, so that the loads of eight rows are in flight together
       const float* row = stats + (long)w * 128;
-      s += (double)row[2 * c] + (double)row[2 * (c + 32)];          // lanes c and c+32 hold channel c
-      q += (double)row[2 * c + 1] + (double)row[2 * (c + 32) + 1];
+      const double n = (double)row[c], d = ((double)row[32 + c] - piv) + (double)row[96 + c];
+      s += n * d;
+      q += (double)row[64 + c] + n * d * d;
     }
   }
   red[g][c][0] = s;
@@ -43,8 +55,9 @@ __global__ __launch_bounds__(256) void bn2d_finalize_kernel(const float* __restr
       s += red[i][c][0];
       q += red[i][c][1];
     }
-    const double m = s / count;
-    const double var = fmax(q / count - m * m, 0.0);      // fp64: the cancellation costs nothing at these magnitudes
+    const double r = s / count;      // count is the sum of the rows' n: the table holds every value once
+    const double m = piv + r;
+    const double var = fmax(q - s * r, 0.0) / count;
     mean = (float)m;
     invstd = (float)(1.0 / sqrt(var + (double)eps));
     const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
@@ -64,41 +77,49 @@ __global__ __launch_bounds__(256) void bn2d_finalize_kernel(const float* __restr
 }
 
 // Stand-alone batch statistics of a 32-channel NHWC tensor (the v2 DECODER's ConvTranspose2d outputs come from the generic
-// conv kernels, which have no statistics epilogue): per-thread sums over a grid-stride loop, lanes with equal channel group
-// combined by wavefront shuffles, the four waves through LDS; one row of the finalize kernel's table per block, rows past
-// the grid zeroed.  Row layout: [2c] = sum, [2c+1] = sum of squares of channel c; the entries of lanes 32..63 stay zero.
+// conv kernels, which have no statistics epilogue): per-thread moments about the thread's first value over a grid-stride loop
+// (fp32), then in fp64 the lanes with equal channel group merged by wavefront shuffles and the four waves through LDS; one row of
+// the finalize kernel's table per block, rows past the grid zeroed.
 __global__ __launch_bounds__(256) void bn2d_stats_kernel(const f32x4* __restrict__ u, float* __restrict__ stats, long n4) {
-  __shared__ float red[4][8][8];
-  f32x4 ss = {0.f, 0.f, 0.f, 0.f}, sq = {0.f, 0.f, 0.f, 0.f};
+  __shared__ double red[4][32][4];
+  f32x4 pv = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f}, sq = {0.f, 0.f, 0.f, 0.f};
+  float cnt = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {   // stride % 8 == 0
     const f32x4 v = u[i];
-    ss += v;
-    sq += v * v;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int o = 8; o < 64; o <<= 1) {
-      ss[k] += __shfl_xor(ss[k], o);
-      sq[k] += __shfl_xor(sq[k], o);
-    }
+    if (cnt == 0.f) pv = v;
+    const f32x4 d = v - pv;
+    ss += d;
+    sq += d * d;
+    cnt += 1.f;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane < 8) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      red[wave][lane][k] = ss[k];
-      red[wave][lane][4 + k] = sq[k];
+  for (int k = 0; k < 4; ++k) {
+    DdMoments a = {cnt, pv[k], ss[k], sq[k]};
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+      const DdMoments b = {__shfl_xor(a.n, o), __shfl_xor(a.p, o), __shfl_xor(a.s, o), __shfl_xor(a.q, o)};
+      dd_moments_merge(a, b);
+    }
+    if (lane < 8) {
+      double* r = red[wave][4 * lane + k];
+      r[0] = a.n;
+      r[1] = a.p;
+      r[2] = a.s;
+      r[3] = a.q;
     }
   }
   __syncthreads();
-  if (threadIdx.x < 128) {
-    float v = 0.f;
-    if (threadIdx.x < 64) {      // entry 2c + j of the row: channel c = 4*grp + k, j = 0 sum / 1 sum of squares
-      const int c = threadIdx.x >> 1, j = threadIdx.x & 1, grp = c >> 2, k = (c & 3) + 4 * j;
-      v = (red[0][grp][k] + red[1][grp][k]) + (red[2][grp][k] + red[3][grp][k]);
+  if (threadIdx.x < 128) {      // entry 32 j + c of the row: j = 0 count, 1 mean, 2 M2, 3 what fp32 rounds away of the mean
+    const int c = threadIdx.x & 31, j = threadIdx.x >> 5;
+    DdMoments a = {red[0][c][0], red[0][c][1], red[0][c][2], red[0][c][3]};
+    for (int w = 1; w < 4; ++w) {
+      const DdMoments b = {red[w][c][0], red[w][c][1], red[w][c][2], red[w][c][3]};
+      dd_moments_merge(a, b);
     }
-    stats[(long)blockIdx.x * 128 + threadIdx.x] = v;
+    double mean, m2;
+    dd_moments_finish(a, mean, m2);
+    stats[(long)blockIdx.x * 128 + threadIdx.x] = j == 0 ? (float)a.n : j == 1 ? (float)mean : j == 2 ? (float)m2 : (float)(mean - (double)(float)mean);
     for (int r = blockIdx.x + gridDim.x; r < kStatRows; r += gridDim.x) stats[(long)r * 128 + threadIdx.x] = 0.f;
   }
 }

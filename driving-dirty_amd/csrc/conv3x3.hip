@@ -62,7 +62,7 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
     ash = *(const f32x4*)(aff + 32 + 4 * (lane & 7));
   }
   const float msc = (EPI == EPI_RELU_MASK_AFF) ? aff[64 + n] : 1.f, msh = (EPI == EPI_RELU_MASK_AFF) ? aff[96 + n] : 0.f;
-  float st_sum = 0.f, st_sq = 0.f;
+  float st_n = 0.f, st_piv = 0.f, st_sum = 0.f, st_sq = 0.f;   // batch statistics of this lane's channel about its first value (DdMoments)
 
   long idx, end;
   dd_range((long)B * nstrips * Ho, blockIdx.x * WPB + wave, gridDim.x * WPB, idx, end);
@@ -161,9 +161,12 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
       for (int r = 0; r < 16; ++r) {
         float v = acc[r];
         if (EPI == DD_EPI_BIAS || EPI == EPI_BIAS_STATS) v += bv;
-        if (EPI == EPI_BIAS_STATS && x0 + dd_acc_row(r, lane) < Wo) {   // batch statistics: lane = channel, no shuffles needed
-          st_sum += v;
-          st_sq += v * v;
+        if (EPI == EPI_BIAS_STATS && x0 + dd_acc_row(r, lane) < Wo) {   // batch statistics: lane = channel, no shuffles in the loop
+          if (st_n == 0.f) st_piv = v;
+          const float dv = v - st_piv;
+          st_sum += dv;
+          st_sq += dv * dv;
+          st_n += 1.f;
         }
         if (EPI == DD_EPI_BIAS_RELU || EPI == EPI_BIAS_RELU_BITS) v = fmaxf(v + bv, 0.f);
         if (EPI == DD_EPI_RELU_MASK) v = (mreg[r] > 0.f) ? v : 0.f;
@@ -185,10 +188,19 @@ __global__ __launch_bounds__(WPB * 64) void conv_strip_fwd(const float* __restri
       }
     }
   }
-  if (EPI == EPI_BIAS_STATS) {   // one partial per wave-lane; waves without work still write their zeros
-    const long gwl = ((long)(blockIdx.x * WPB + wave) * 64 + lane) * 2;
-    stats[gwl] = st_sum;
-    stats[gwl + 1] = st_sq;
+  if (EPI == EPI_BIAS_STATS) {   // one row per wave (layout: bn2d.hip): lanes c and c + 32 hold channel c; the row of a wave without
+    DdMoments a = {st_n, st_piv, st_sum, st_sq};   // work stays zero (the launcher's memset)
+    const DdMoments o = {__shfl_xor(st_n, 32), __shfl_xor(st_piv, 32), __shfl_xor(st_sum, 32), __shfl_xor(st_sq, 32)};
+    dd_moments_merge(a, o);
+    double mean, m2;
+    dd_moments_finish(a, mean, m2);
+    if (lane < 32 && a.n > 0.0) {
+      float* row = stats + (long)(blockIdx.x * WPB + wave) * 128;
+      row[lane] = (float)a.n;
+      row[32 + lane] = (float)mean;
+      row[64 + lane] = (float)m2;
+      row[96 + lane] = (float)(mean - (double)(float)mean);
+    }
   }
 }
 

@@ -12,7 +12,7 @@ constexpr int EPI_RELU_BITS = 6;        // y = conv * bit(channel) of bits[pixel
 // Conv -> BatchNorm2d -> ReLU variant (reference components_v2.py:43-46): the conv writes the PRE-normalisation value
 // and gathers the batch statistics in its epilogue; the normalise + ReLU is applied by whoever READS the tensor
 // (next conv's row loader, pool, mask tests) from a per-channel (scale, shift), so the activation is never rewritten.
-constexpr int EPI_BIAS_STATS = 7;       // u = conv + bias; per-lane sum / sum of squares of u -> stats[wave][lane][2]
+constexpr int EPI_BIAS_STATS = 7;       // u = conv + bias; per-channel (n, mean, M2) of the wave's u -> stats[wave][128] (bn2d.hip)
 constexpr int EPI_RELU_MASK_AFF = 8;    // y = conv * (mask*m_scale[c] + m_shift[c] > 0)
 constexpr int EPI_RELU_BITS_W1 = 9;     // conv_wino2_fwd only: as EPI_RELU_BITS, but y is not stored -- it feeds the 3 -> 32 layer's weight gradient in place
 

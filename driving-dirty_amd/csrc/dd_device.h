@@ -77,6 +77,28 @@ __device__ __forceinline__ float dd_bload1(__amdgpu_buffer_rsrc_t r, int off, in
 template <int AUX = 0>
 __device__ __forceinline__ void dd_bstore1(__amdgpu_buffer_rsrc_t r, int off, float v) { dd_bstore<AUX>(r, off, v); }
 
+// Batch statistics without the cancellation of sum(v^2) - sum(v)^2/n: the moments of a set of values ABOUT A PIVOT p close to them
+// (the first value a lane meets): n, s = sum(v - p), q = sum((v - p)^2).  A lane gathers them in fp32 -- the terms are of the size
+// of the spread, whatever the offset of the values -- and everything behind the lane's loop is done in fp64: two sets merge by
+// moving the second onto the first's pivot (with d = p_b - p_a: s_b' = s_b + n_b d, q_b' = q_b + d (2 s_b + n_b d), exact algebra,
+// no division), and mean = p + s/n, M2 = sum((v - mean)^2) = q - s^2/n lose nothing, since |s/n| is of the size of the spread too.
+// Merged in this form, (n, mean, M2) sets combine exactly as by Chan's pairwise formula.  An empty set is n = 0 with finite entries.
+struct DdMoments {
+  double n, p, s, q;
+};
+__device__ __forceinline__ void dd_moments_merge(DdMoments& a, const DdMoments& b) {
+  if (a.n == 0.0) a.p = b.p;      // a.s == a.q == 0: the union takes b's pivot
+  const double d = b.p - a.p;
+  a.s += b.s + b.n * d;
+  a.q += b.q + d * (2.0 * b.s + b.n * d);
+  a.n += b.n;
+}
+__device__ __forceinline__ void dd_moments_finish(const DdMoments& a, double& mean, double& m2) {
+  const double r = a.n > 0.0 ? a.s / a.n : 0.0;
+  mean = a.n > 0.0 ? a.p + r : 0.0;
+  m2 = fmax(a.q - a.s * r, 0.0);
+}
+
 // The contiguous range [idx, end) of `total` work items owned by piece `i` of `n` equal pieces (for the row tiles of the convolutions:
 // piece = global wave, idx = column * rows + row).  A piece past the end of the work gets the empty range idx == end.
 __device__ __forceinline__ void dd_range(long total, int i, int n, long& idx, long& end) {

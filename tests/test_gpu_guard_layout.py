@@ -348,8 +348,8 @@ for _n in (4, 4100):      # n % 4 == 0 is the contract
 def _bn2d(b, h, w, training):
     """dd_bn2d_stats -> dd_bn2d_finalize -> dd_bn2d_apply_relu -> dd_bn2d_bwd in one arena; the statistics table is exactly
     dd_conv_stats_floats() floats, left 0xFF: every row the finalize kernel reads must have been written by dd_bn2d_stats.
-    No kernel-level test of these four exists (they are held through the whole-model three-way checks of tests/test_gpu_round2.py /
-    test_gpu_round3.py), so the bounds are those of the BatchNorm1d kernels, which compute the same quantities
+    Their numerics at offsets, past the grid cap and with gamma of either sign: tests/test_gpu_bn2d.py (and the whole-model three-way
+    checks of tests/test_gpu_round2.py / test_gpu_round3.py); the bounds here are those of the BatchNorm1d kernels, which compute the same quantities
     (tests/test_gpu_parity.py::test_bn_relu_dropout: KERNEL_TOL, 10 x KERNEL_TOL for the gradients)."""
     def fn(arena, mode):
         eps, mom, npix = 1e-5, 0.1, b * h * w
@@ -397,8 +397,8 @@ for _b, _h, _w in ((2, 6, 10), (4, 16, 22)):
 
 
 def _pool4_bn(b, h, w):
-    """dd_pool4_bn_fwd / _bwd: the NCHW-order max_pool1d(4) over relu(u * scale + shift), the activation never stored.  No kernel-level
-    test of the pair exists; the bound is KERNEL_TOL, as for dd_bn2d_apply_relu above (the same affine + ReLU, then a selection)."""
+    """dd_pool4_bn_fwd / _bwd: the NCHW-order max_pool1d(4) over relu(u * scale + shift), the activation never stored.  Signed gamma, ties
+    and a shape past the grid cap: tests/test_gpu_bn2d.py; the bound is KERNEL_TOL, as for dd_bn2d_apply_relu above (the same affine + ReLU, then a selection)."""
     def fn(arena, mode):
         u64 = hu((b, h, w, 32), f"pbu{h}{w}", -2.0, 2.0).double()
         aff64 = torch.cat([hu((32,), "pbsc", 0.5, 1.5), hu((32,), "pbsh", -0.5, 0.5)] * 2).double()
