@@ -450,9 +450,10 @@ def test_encoder_tail_on_both_sides_of_its_row_bound(dev, monkeypatch, past, tra
 
 
 # ------------------------------------------------------------------------------------------------ 2d. rank-B Adam at 64 / 65 rows
-@pytest.mark.parametrize("rows", [64, 65])
+@pytest.mark.parametrize("rows", [33, 48, 64, 65])
 def test_rankb_adam_with_a_real_linear_at_the_row_limit(dev, rows):
-    """A real nn.Linear registered with HipAdam.fuse_linear_wgrad: one step at 64 rows (the rank-B pass: no .grad anywhere) and one at
+    """A real nn.Linear registered with HipAdam.fuse_linear_wgrad: one step at 64 rows (the rank-B pass: no .grad anywhere; 33 and 48
+    rows: the same pass with one row and with half of its second 32-row chunk filled, 48 the consistency step's batch) and one at
     65 (dd_adam_step_rankb takes at most 64 rows: the optimizer declines, dd_linear_wgrad materialises dW AND db) against
     torch.optim.Adam fed the fp64 gradient.  Bounds of tests/test_gpu_round5.py::test_adam_rankb_matches_fp64 on unsigned factors
     (every gradient element well conditioned): parameters 1e-6 of peak, first moments 2e-6."""

@@ -52,11 +52,11 @@ def frames(dev, b, seed):
     return u8.to(dev), f32.to(dev)
 
 
-def tiny_batch(dev, b_u=B_U, seed=100):
+def tiny_batch(dev, b_u=B_U, seed=100, b_l=B_L):
     """(sample, None, road_image, unlabelled): fp32 views as the collate's tuples."""
     from driving_dirty_amd import synth
-    views = synth.camera_batch(B_L, H, W, seed=seed).to(dev)
-    road = synth.road_maps(B_L, seed=seed).to(dev)
+    views = synth.camera_batch(b_l, H, W, seed=seed).to(dev)
+    road = synth.road_maps(b_l, seed=seed).to(dev)
     _, unlabelled = frames(dev, b_u, seed + 1)
     return (tuple(views), None, tuple(road), tuple(unlabelled))
 
@@ -228,6 +228,35 @@ def test_one_train_step_keeps_the_rank_b_pass(dev):
                 continue
             d = float((p.detach() - q.detach()).abs().max() / p.detach().abs().max().clamp_min(1e-30))
             assert d <= 1e-6, (k, d)
+    finally:
+        ta.close()
+        tb.close()
+
+
+def test_one_train_step_at_48_rows_keeps_the_rank_b_pass(dev):
+    """``B_l = 16``, ``B_u = 16``: ``N = 16 + 2 * 16 = 48`` rows, the production batch of the consistency step.  More than 32 rows: both big
+    Linear layers take the two-chunk form of the rank-B pass with a half-filled second chunk (the head on one k-tile per n-group, the
+    encoder's fc1 on 17).  Same twin and same bounds as ``test_one_train_step_keeps_the_rank_b_pass``."""
+    from driving_dirty_amd.train import TrainStep
+    a, b = tiny_model(dev, cons_weight=1.0), tiny_model(dev, cons_weight=1.0)
+    ta = TrainStep(a, lr=1e-2, big_numel=4096, scheduler=False, fuse_linear_wgrad=False)
+    tb = TrainStep(b, lr=1e-2, big_numel=4096, scheduler=False)
+    try:
+        batch = tiny_batch(dev, b_u=16, b_l=16)
+        la, lb = ta(batch, 0)["loss"], tb(batch, 0)["loss"]
+        torch.cuda.synchronize()
+        assert float(la.detach()) == float(lb.detach())
+        assert {id(w) for w in tb.fused} == {id(b.fc1.weight), id(b.ae.encoder.fc1.fc1.weight)} and not ta.fused
+        assert a.fc1.weight.grad is not None and tuple(a.fc1.weight.grad.shape) == (640000, 8)
+        assert b.fc1.weight.grad is None and b.fc1.bias.grad is None and b.ae.encoder.fc1.fc1.weight.grad is None
+        worst = 0.0
+        for (k, p), (_, q) in zip(a.named_parameters(), b.named_parameters()):
+            if k.endswith("fc1.fc1.bias"):
+                continue
+            d = float((p.detach() - q.detach()).abs().max() / p.detach().abs().max().clamp_min(1e-30))
+            worst = max(worst, d)
+            assert d <= 1e-6, (k, d)
+        print(f"48 rows: worst parameter difference {worst:.3e} of its tensor's peak (bound 1e-6)")
     finally:
         ta.close()
         tb.close()

@@ -120,23 +120,38 @@ def _check_rankb_sqnorm(dev, x, dy, with_bias):
 
 @pytest.mark.parametrize("with_bias", [0, 1])
 @pytest.mark.parametrize("n,k", [(4, 4), (64, 260), (132, 4100)])
-@pytest.mark.parametrize("rows", [1, 3, 32, 64])
+@pytest.mark.parametrize("rows", [1, 3, 17, 32, 33, 48, 49, 64])
 def test_rankb_sqnorm_matches_fp64(dev, rows, n, k, with_bias):
+    """Rows in 16-row blocks: 1 and 3 one block, 17 two with a ragged second, 32 two, 33 and 48 three (ragged and full: 48 is the
+    consistency step's batch under gradient_clip_val), 49 four with a ragged last, 64 four."""
     gen = torch.Generator().manual_seed(1000 * rows + n + k)
     x = torch.relu(torch.randn(rows, k, generator=gen))
     dy = 1e-3 * torch.randn(rows, n, generator=gen)
     _check_rankb_sqnorm(dev, x, dy, with_bias)
 
 
+def _cancelling_rows(rows):
+    gen = torch.Generator().manual_seed(7)
+    k, n = 4096, 64
+    x = torch.randn(1, k, generator=gen) + 1e-3 * torch.randn(rows, k, generator=gen)
+    sign = torch.tensor([1.0, -1.0]).repeat(rows // 2)[:, None]
+    dy = sign * torch.randn(1, n, generator=gen) + 1e-3 * torch.randn(rows, n, generator=gen)
+    return x, dy
+
+
 @pytest.mark.parametrize("with_bias", [0, 1])
 def test_rankb_sqnorm_on_a_batch_whose_row_gradients_cancel(dev, with_bias):
     """All rows of x nearly one vector, rows of dy one vector with alternating sign: dW = dy^T x is what is left after the rows cancel.
     A Gram matrix accumulated in fp32 loses it (24 % at a conditioning of 1e7); the derived fp64 tolerance stays below 1e-3."""
-    gen = torch.Generator().manual_seed(7)
-    rows, k, n = 32, 4096, 64
-    x = torch.randn(1, k, generator=gen) + 1e-3 * torch.randn(rows, k, generator=gen)
-    sign = torch.tensor([1.0, -1.0]).repeat(rows // 2)[:, None]
-    dy = sign * torch.randn(1, n, generator=gen) + 1e-3 * torch.randn(rows, n, generator=gen)
+    x, dy = _cancelling_rows(32)
+    _check_rankb_sqnorm(dev, x, dy, with_bias)
+
+
+@pytest.mark.parametrize("with_bias", [0, 1])
+def test_rankb_sqnorm_on_48_rows_whose_gradients_cancel(dev, with_bias):
+    """The same batch at 48 rows, the consistency step's: three 16-row blocks of the Gram matrices, and rows that cancel across the
+    blocks as well as inside one."""
+    x, dy = _cancelling_rows(48)
     _check_rankb_sqnorm(dev, x, dy, with_bias)
 
 

@@ -319,6 +319,13 @@ for _n, _k in ((20, 4), (52, 132)):      # the smallest of tests/test_gpu_round5
     for _rows, _bias in ((1, True), (7, False), (64, True)):
         case(f"dd_adam_step_rankb[{_n}x{_k},rows={_rows},bias={_bias}]", "dd_adam_step_rankb")(_adam_rankb(_n, _k, _rows, _bias, False))
 case("dd_adam_step_rankb_dev[52x132,rows=7,bias=True]", "dd_adam_step_rankb_dev")(_adam_rankb(52, 132, 7, True, True))
+# rows past M that the kernels fetch through the wave-uniform offset of the load (x rows 16 .. 31 of a 32-row chunk), not through the
+# lane's own: 20 rows (lds<1,2>), 40 (lds<2,1>, 8 rows in its second chunk), 48 on one k-tile (lds<2,1>; by device scale at the head's
+# K = 64).  The arena has NaN behind x: a row that came back as memory instead of zeros makes every element of its tile NaN.
+for _rows, _bias in ((20, True), (40, False)):
+    case(f"dd_adam_step_rankb[52x132,rows={_rows},bias={_bias}]", "dd_adam_step_rankb")(_adam_rankb(52, 132, _rows, _bias, False))
+case("dd_adam_step_rankb[20x4,rows=48,bias=True]", "dd_adam_step_rankb")(_adam_rankb(20, 4, 48, True, False))
+case("dd_adam_step_rankb_dev[640x64,rows=48,bias=True]", "dd_adam_step_rankb_dev")(_adam_rankb(640, 64, 48, True, True))
 
 
 # ------------------------------------------------------------------------------------------------ gradnorm.hip
@@ -380,6 +387,8 @@ def _rankb_sqnorm(rows, n, k, with_bias):
 for _rows in (1, 7, 64):
     for _n, _k in ((4, 4), (64, 260)):
         case(f"dd_rankb_sqnorm[rows={_rows},{_n}x{_k}]", "dd_rankb_sqnorm")(_rankb_sqnorm(_rows, _n, _k, _rows != 7))
+for _n, _k in ((4, 4), (64, 260)):      # 40 rows: three 16-row blocks, the last one half full
+    case(f"dd_rankb_sqnorm[rows=40,{_n}x{_k}]", "dd_rankb_sqnorm")(_rankb_sqnorm(40, _n, _k, True))
 
 
 def _clip_scale(max_norm, grad_scale):
